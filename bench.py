@@ -59,6 +59,9 @@ def parse():
                     help="the timed region of --steps steps is run this many times; `value` is the first, all are reported")
     ap.add_argument("--cpu-images", type=int, default=1, help="images per point of the CPU-oracle thread sweep")
     ap.add_argument("--cpu-threads", default="1,8,32,all", help="thread counts of the CPU-oracle sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, gradients, updated "
+                         "parameters) as DIR/<name>.npy (float32, <= 64 MB in all)")
     return ap.parse_args()
 
 
@@ -142,8 +145,9 @@ def make_model(dev, comer=False, seg_trans=False):
     return model
 
 
-def timed_steps(step, loader, n, world, dev):
-    """EXACTLY n steps between barrier + synchronize on both sides; returns (seconds [max over ranks], host seconds)."""
+def timed_steps(step, loader, n, world, dev, last=None):
+    """EXACTLY n steps between barrier + synchronize on both sides; returns (seconds [max over ranks], host seconds).
+    `last` (a list): receives the outputs of the last step."""
     import torch
     import torch.distributed as dist
     torch.cuda.synchronize()
@@ -151,9 +155,12 @@ def timed_steps(step, loader, n, world, dev):
         dist.barrier()
     t0 = time.perf_counter()
     c0 = time.process_time()
+    out = None
     for _ in range(n):
         img, labels = loader.next()
-        step(img, labels=labels)
+        out = step(img, labels=labels)
+    if last is not None:
+        last[:] = [out]
     t_enq = time.perf_counter() - t0          # host wall time until the last step is enqueued (includes waiting on a full queue)
     t_cpu = time.process_time() - c0          # CPU time this process burnt doing it (all threads)
     torch.cuda.synchronize()
@@ -170,8 +177,36 @@ def timed_steps(step, loader, n, world, dev):
     return dt, t_enq, t_cpu, per_rank
 
 
-def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None, warmup=None, graph=True, repeats=1):
-    """Build a model + TrainStep, warm up, time `steps` steps.  -> (dict, step, loader)"""
+DUMP_MAX_ELEMS = 7_000_000       # per array: the two parameter-sized arrays stay under 64 MB of float32 together
+
+
+def dump_outputs(out_dir, step, out):
+    """What the caller of the timed step holds after its last step: the three losses it returned, the (all-reduced)
+    gradients of the trainable parameters and those parameters after the optimizer step.  float32 .npy files; an array
+    longer than DUMP_MAX_ELEMS is replaced by a fixed, seeded sample of its elements (same indices in every run)."""
+    import numpy as np
+    import torch
+    loss, seg_loss, attn_loss = out
+    params = step.model.get_param_groups()[3]
+    if step.bucket is not None:
+        grads = step.bucket.flat
+    else:
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().flatten() for p in params])
+    arrays = {"loss": loss, "seg_loss": seg_loss, "attn_loss": attn_loss, "grads": grads,
+              "params": torch.cat([p.detach().flatten() for p in params])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
+
+
+def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None, warmup=None, graph=True, repeats=1,
+            dump_dir=None):
+    """Build a model + TrainStep, warm up, time `steps` steps.  -> (dict, step, loader)
+    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs)."""
     from weclip_vit_comer_amd.data import SyntheticVOCLoader
     from weclip_vit_comer_amd.train_step import TrainStep
     steps = args.steps if steps is None else steps
@@ -189,12 +224,15 @@ def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None,
     for _ in range(warmup):
         img, labels = loader.next()
         step(img, labels=labels)
-    dt, t_enq, t_cpu, per_rank = timed_steps(step, loader, steps, world, dev)
+    last = []
+    dt, t_enq, t_cpu, per_rank = timed_steps(step, loader, steps, world, dev, last)
     # the same region again (a 0.26 s region cannot resolve 2 %): `value` stays the FIRST region of exactly
     # `steps` steps; the repeats show the run-to-run spread inside one process on one box
     rep_ms = [dt / steps * 1e3]
     for _ in range(max(0, repeats - 1)):
-        rep_ms.append(timed_steps(step, loader, steps, world, dev)[0] / steps * 1e3)
+        rep_ms.append(timed_steps(step, loader, steps, world, dev, last)[0] / steps * 1e3)
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, step, last[0])
     # host work per step, free of back-pressure: each step enqueued onto an IDLE queue (in the timed region above the host
     # runs ahead of the GPU-bound device and then blocks in the loader's pinned-buffer event, which is waiting, not work)
     import torch
@@ -411,7 +449,7 @@ def main():
         config.precision = args.precision
 
     res, step, loader = run_leg(args, dev, rank, world, comer=args.comer, seg_trans=args.seg_trans, graph=not args.no_graph,
-                                repeats=args.repeats)
+                                repeats=args.repeats, dump_dir=args.dump_outputs)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()

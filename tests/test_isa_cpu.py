@@ -24,10 +24,10 @@ ALLOWED = {
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-def test_rewritten_kernels_issue_their_loads_together():
+def test_rewritten_kernels_issue_their_loads_together(tmp_path):
     import isa_scan
     src = os.path.join(ROOT, "weclip-vit-comer_amd", "csrc")
     with ThreadPoolExecutor(4) as ex:
-        rows = [r for part in ex.map(lambda f: isa_scan.report([os.path.join(src, f)], threshold=4), FILES) for r in part]
+        rows = [r for part in ex.map(lambda f: isa_scan.report([os.path.join(src, f)], threshold=4, out_dir=str(tmp_path)), FILES) for r in part]
     bad = [(alone, loads, f, name) for alone, loads, f, name, _ in rows if not any(a in name for a in ALLOWED)]
     assert not bad, "loads waited for one at a time (see tools/isa_scan.py): %s" % bad

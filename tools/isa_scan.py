@@ -54,11 +54,11 @@ def scan(lines):
     return loads, alone, "".join(seq)
 
 
-def report(files, threshold=3):
+def report(files, threshold=3, out_dir="/tmp/isa"):
     """[(loads waited for alone, loads, file, mangled kernel name, sequence)] of the kernels at or above the threshold."""
     rows = []
     for f in files:
-        for name, lines in kernels(disassemble(f)):
+        for name, lines in kernels(disassemble(f, out_dir)):
             loads, alone, seq = scan(lines)
             if alone >= threshold:
                 rows.append((alone, loads, os.path.basename(f), name, seq))
