@@ -393,9 +393,12 @@ int wc_colscale_split(const float* x, const float* cs, float* out32, void* hi, v
  * loc (N,Lq,M,nL,P,2) f32 in [0,1] as (x,y); attn (N,Lq,M,nL,P) f32; out (N,Lq,M*D) f32:
  * out = sum_l sum_p attn * bilinear_zero_pad(value_l, loc*size - 0.5).
  * wc_msda_bwd: gvalue (every element written once: no initialisation needed), gloc, gattn.  grad_value is a bucketed
- *              gather (count / scan / fill per pixel, then a per-pixel sum in 64-bit fixed point, scale 2^40 / max|gout|):
- *              no float atomics anywhere, the result is independent of the execution order.  gmax: workspace of one
- *              uint32; ws: workspace of N*M*S*2 + N*M*n_levels*Lq*P*8 int32; a level may have at most 16384 pixels. */
+ *              gather (count / scan / fill per pixel, then a per-pixel sum in 64-bit fixed point): every product
+ *              gout * attn * bilinear weight is rounded to a multiple of the quantum q = max|gout| max(1, max|attn|) 2^-24,
+ *              so |error| <= (pairs / 2 + 1) q + fp32 rounding per element (pairs: (sample, corner) pairs on the pixel);
+ *              holds for any finite gout / attn.  No float atomics anywhere, the result is independent of the execution
+ *              order.  gmax: workspace of two uint32 (max|gout|, max|attn|); ws: workspace of N*M*S*2 + N*M*n_levels*Lq*P*8
+ *              int32; a level may have at most 16384 pixels (checked before anything is launched). */
 int wc_msda_fwd(const float* value, const int* h_shapes, int n_levels, const float* loc, const float* attn,
                 float* out, int N, int Lq, int M, int D, int P, void* stream);
 /* The same with the value tensor as f32 or f16 (value_is_f16: half the gather traffic; needs D % 4 == 0 and M*D/4 dividing

@@ -131,7 +131,7 @@ class ComerEngine:
         S = sum(h * w for h, w in shapes)
         dev = value.device
         gv = torch.empty(value.shape, device=dev, dtype=F16)          # (value is f16 already)
-        gmax = torch.empty(1, device=dev, dtype=torch.int32)
+        gmax = torch.empty(2, device=dev, dtype=torch.int32)
         ws = torch.empty(B * M * (2 * S + nL * Lq * P * 8), device=dev, dtype=torch.int32)
         hs = _shape_array(shapes)
         lib = L.lib()

@@ -417,14 +417,17 @@ __global__ __launch_bounds__(256) void msda_bwd4f_kernel(const VT* __restrict__ 
     for (int c = 3 * M * T + j; c < ld; c += tpq) drow[c] = __float2half(0.f);      // K padding of the gradient GEMMs
 }
 
-// max |gout| as the bit pattern of a non-negative float (unsigned compare == float compare); *gmax zeroed by the caller.
-// 16-byte loads, four in flight per thread (n is a multiple of 16 / sizeof(GT), g 16-byte aligned: checked by the launcher).
+// gmax[0] = max |gout|, gmax[1] = max |attn|, as bit patterns of non-negative floats (unsigned compare == float compare);
+// gmax[0..1] zeroed by the caller.  16-byte loads, four in flight per thread (n is a multiple of 16 / sizeof(GT), g 16-byte
+// aligned: checked by the launcher); attn as 16-byte loads over its first na4 quads (na4 = 0 if attn is not 16-byte aligned)
+// and single floats after them.
 template <typename GT>
-__global__ __launch_bounds__(256) void msda_absmax_kernel(const GT* __restrict__ g, unsigned int* __restrict__ gmax, long n) {
+__global__ __launch_bounds__(256) void msda_absmax_kernel(const GT* __restrict__ g, long n, const float* __restrict__ a, long na,
+                                                          long na4, unsigned int* __restrict__ gmax) {
     constexpr int VEC = 16 / (int)sizeof(GT);
     const uint4* g4 = reinterpret_cast<const uint4*>(g);
     const long n4 = n / VEC, stride = (long)gridDim.x * 256;
-    float m = 0.f;
+    float m = 0.f, ma = 0.f;
     auto fold = [&](const uint4& u) {
         if constexpr (sizeof(GT) == 2) {
             const __half2* h = reinterpret_cast<const __half2*>(&u);
@@ -444,9 +447,25 @@ __global__ __launch_bounds__(256) void msda_absmax_kernel(const GT* __restrict__
         fold(a); fold(b); fold(c); fold(d);
     }
     for (; i < n4; i += stride) fold(g4[i]);
+    const uint4* a4 = reinterpret_cast<const uint4*>(a);
+    auto folda = [&](const uint4& u) {
+        const float* f = reinterpret_cast<const float*>(&u);
+        ma = fmaxf(fmaxf(ma, fabsf(f[0])), fmaxf(fabsf(f[1]), fmaxf(fabsf(f[2]), fabsf(f[3]))));
+    };
+    i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * stride < na4; i += 4 * stride) {
+        const uint4 p = a4[i], q = a4[i + stride], r = a4[i + 2 * stride], s = a4[i + 3 * stride];
+        folda(p); folda(q); folda(r); folda(s);
+    }
+    for (; i < na4; i += stride) folda(a4[i]);
+    for (long k = na4 * 4 + (long)blockIdx.x * 256 + threadIdx.x; k < na; k += stride) ma = fmaxf(ma, fabsf(a[k]));
     __shared__ float red[16];
     m = block_max(m, red);
-    if (threadIdx.x == 0) atomicMax(gmax, __float_as_uint(m));
+    ma = block_max(ma, red);
+    if (threadIdx.x == 0) {
+        atomicMax(gmax, __float_as_uint(m));
+        atomicMax(gmax + 1, __float_as_uint(ma));
+    }
 }
 
 // grad_value as a BUCKETED GATHER, two kernels:
@@ -457,7 +476,7 @@ __global__ __launch_bounds__(256) void msda_absmax_kernel(const GT* __restrict__
 //     pass 2  writes every pair's id into its pixel's bucket (the order inside a bucket depends on the wave scheduling);
 //   msda_gather_kernel (one group of D lanes per pixel, all pixels of all levels / heads / images in parallel):
 //     walks the pixel's bucket, recomputes the bilinear weight of each pair and accumulates
-//     attn * weight * grad_out[q, m, d] in 64-bit FIXED POINT (2^24 / max|grad_out| per product): integer sums do not depend on the
+//     attn * weight * grad_out[q, m, d] in 64-bit FIXED POINT (2^24 / (max|grad_out| max(1, max|attn|)) per product): integer sums do not depend on the
 //     order of the bucket, so the result is bit-reproducible, and every element of grad_value is written exactly once
 //     (no atomics on HBM at all).
 // LDS of the bucket kernel: 2 * H_l*W_l ints -> levels up to 16384 pixels.
@@ -570,8 +589,8 @@ __global__ __launch_bounds__(MSDA_VT) void msda_bucket_kernel(const float* __res
 // level whose buckets hold ~4 entries (the 64 x 64 map of the three-level direction: 76 % of its pixels) kept 7 of 8 slots idle
 // and paid the three dependent latencies of a pixel (bucket bounds -> entries -> rows) for 4 useful loads: 1.6 TB/s algorithmic,
 // against 7.9 TB/s for the one-level direction with ~84 entries per bucket; 4 lanes per pixel there put 8x the pixels in flight.
-// A lane accumulates its VEC channels over its slot's pairs in 64-bit FIXED POINT (2^24 / max|grad_out| per product, 64-bit
-// sums); the slots are added at the end -- integer sums, so the result does not depend on the bucket order, on the slot a pair
+// A lane accumulates its VEC channels over its slot's pairs in 64-bit FIXED POINT (2^24 / (max|grad_out| max(1, max|attn|)) per
+// product, 64-bit sums); the slots are added at the end -- integer sums, so the result does not depend on the bucket order, on the slot a pair
 // falls into or on GL (bit-reproducible).
 struct GatherPlan {
     int blk0[MSDA_MAX_LEVELS + 1];       // first workgroup of each level (+ total)
@@ -599,12 +618,15 @@ __global__ __launch_bounds__(256) void msda_gather_kernel(const GT* __restrict__
     const long pm = ((long)n * M + m) * S + s;
     const int b0 = ws[pm], nb = ws[NMS + pm];
     const int2* list = reinterpret_cast<const int2*>(ws + 2 * NMS + (((long)n * M + m) * sh.n_levels + l) * nsamp * 8) + b0;
-    const float gm = __uint_as_float(*gmax);
-    // fixed point with 2^24 / max|gout| per unit: |weight| <= 1, so a product is at most 2^24 and a lane's <= 4 * 16 / VEC
-    // products of one round of D bucket entries fit an int32 (v_rndne + v_cvt_i32 + one 32-bit add per product; the float ->
-    // int64 conversion of the round-3 form was ~10 instructions and made the kernel VALU-bound: 235 us for 6-11 M pairs); the
-    // int32 partial sums are widened into the 64-bit accumulators once per round.  Quantum = max|gout| * 2^-24 per product.
-    const float scale = gm > 0.f ? 16777216.0f / gm : 0.f;
+    const float gm = __uint_as_float(gmax[0]), am = fmaxf(1.f, __uint_as_float(gmax[1]));
+    // fixed point with 2^24 / (max|gout| max(1, max|attn|)) per unit: a pair's weight (bilinear weight <= 1 times attn) is at
+    // most max|attn|, so a product is at most 2^24 and a lane's <= 4 * 16 / VEC products of one round of D bucket entries fit
+    // an int32 for ANY finite attn (v_rndne + v_cvt_i32 + one 32-bit add per product; the float -> int64 conversion of the
+    // round-3 form was ~10 instructions and made the kernel VALU-bound: 235 us for 6-11 M pairs); the int32 partial sums are
+    // widened into the 64-bit accumulators once per round.  Quantum q = max|gout| max(1, max|attn|) 2^-24 per product.  (The
+    // scale was 2^24 / max|gout| alone: with |attn| >= 8 a round overflowed its int32.)  For max|attn| <= 1 -- soft-max weights,
+    // every CTI call -- am is exactly 1 and scale / inv are the bits of that form.
+    const float scale = gm > 0.f ? 16777216.0f / gm / am : 0.f;
     long long acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 0;
@@ -648,7 +670,7 @@ __global__ __launch_bounds__(256) void msda_gather_kernel(const GT* __restrict__
         }
     }
     if (slot == 0) {
-        const float inv = gm > 0.f ? gm / 16777216.0f : 0.f;
+        const float inv = gm > 0.f ? gm / 16777216.0f * am : 0.f;
         const long o = (((long)n * S + s) * M + m) * D + ch;
         float gv[VEC];
         __half hv[VEC];
@@ -722,7 +744,7 @@ extern "C" int wc_msda_fwd_h(const void* value, int value_is_f16, const int* h_s
     return WC_OK;
 }
 
-// gvalue needs no initialisation (every element is written exactly once); gmax: 1 x u32 workspace;
+// gvalue needs no initialisation (every element is written exactly once); gmax: 2 x u32 workspace (max|gout|, max|attn|);
 // ws: N*M*S*2 + N*M*n_levels*Lq*P*4 ints (bucket starts, sizes, and the per-pixel buckets of (sample, corner) ids).
 extern "C" int wc_msda_bwd_h(const void* value, int value_is_f16, const int* h_shapes, int n_levels, const float* loc,
                              const float* attn, const void* gout, int gout_is_f16, float* gvalue, void* gvalue16, float* gloc,
@@ -734,22 +756,32 @@ extern "C" int wc_msda_bwd(const float* value, const int* h_shapes, int n_levels
     return wc_msda_bwd_h(value, 0, h_shapes, n_levels, loc, attn, gout, 0, gvalue, nullptr, gloc, gattn, gmax, ws, N, Lq, M, D, P, stream);
 }
 
+// the value-gradient arguments, checked before the first launch of a backward call: a refused call launches nothing and
+// writes no output
+static int msda_bwd_value_check(const MsdaShapes& sh, const void* gout, int gt_size, const float* gvalue, const void* gvalue16,
+                                const void* ws, int D) {
+    int maxhw = 0;
+    for (int l = 0; l < sh.n_levels; ++l) maxhw = sh.H[l] * sh.W[l] > maxhw ? sh.H[l] * sh.W[l] : maxhw;
+    WC_CHECK_ARG(maxhw <= 16384 && ws, "wc_msda_bwd: a level may have at most 16384 pixels; ws workspace missing");
+    WC_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gvalue | (uintptr_t)gvalue16 | (uintptr_t)ws) % 16 == 0 && D % (16 / gt_size) == 0,
+                 "wc_msda_bwd: grad_out / grad_value / ws must be 16-byte aligned (16-byte gathers)");
+    WC_CHECK_ARG(D <= 64 && (D & (D - 1)) == 0 && D >= 16 / gt_size,
+                 "wc_msda_bwd: the head width must be a power of two of at most 64 (lane groups of the gather)");
+    return WC_OK;
+}
+
 template <typename GT>
 static int msda_bwd_value(const float* loc, const float* attn, const GT* gout, float* gvalue, void* gvalue16, void* gmax, void* ws,
                           const MsdaShapes& sh, int n_levels, int S, int N, int Lq, int M, int D, int P, hipStream_t st) {
-    hipMemsetAsync(gmax, 0, sizeof(unsigned int), st);
-    const long ng = (long)N * Lq * M * D;
-    WC_CHECK_ARG((uintptr_t)gout % 16 == 0 && D % (16 / (int)sizeof(GT)) == 0, "wc_msda_bwd: grad_out must be 16-byte aligned");
-    const long nv = ng / (16 / (long)sizeof(GT)) / 256 / 4 + 1;
-    hipLaunchKernelGGL(msda_absmax_kernel<GT>, dim3((unsigned)(nv > 2048 ? 2048 : nv)), dim3(256), 0, st, gout, (unsigned int*)gmax, ng);
+    hipMemsetAsync(gmax, 0, 2 * sizeof(unsigned int), st);
+    const long ng = (long)N * Lq * M * D, na = (long)N * Lq * M * n_levels * P;
+    const long na4 = (uintptr_t)attn % 16 == 0 ? na / 4 : 0;
+    const long nv = (ng / (16 / (long)sizeof(GT)) + na4) / 256 / 4 + 1;
+    hipLaunchKernelGGL(msda_absmax_kernel<GT>, dim3((unsigned)(nv > 2048 ? 2048 : nv)), dim3(256), 0, st, gout, ng, attn, na, na4,
+                       (unsigned int*)gmax);
     WC_LAUNCH_CHECK("msda_absmax_kernel");
     int maxhw = 0;
     for (int l = 0; l < n_levels; ++l) maxhw = sh.H[l] * sh.W[l] > maxhw ? sh.H[l] * sh.W[l] : maxhw;
-    WC_CHECK_ARG(maxhw <= 16384 && ws, "wc_msda_bwd: a level may have at most 16384 pixels; ws workspace missing");
-    WC_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gvalue | (uintptr_t)gvalue16 | (uintptr_t)ws) % 16 == 0 && D % (16 / (int)sizeof(GT)) == 0,
-                 "wc_msda_bwd: grad_out / grad_value / ws must be 16-byte aligned (16-byte gathers)");
-    WC_CHECK_ARG(D <= 64 && (D & (D - 1)) == 0 && D >= 16 / (int)sizeof(GT),
-                 "wc_msda_bwd: the head width must be a power of two of at most 64 (lane groups of the gather)");
     static bool attr_set = false;
     if (!attr_set) {
         WC_CHECK_ARG(hipFuncSetAttribute((const void*)msda_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 131072) == hipSuccess,
@@ -801,6 +833,10 @@ extern "C" int wc_msda_bwd_h(const void* value, int value_is_f16, const int* h_s
     const int tpq = M * D / 4;
     const bool quad = D % 4 == 0 && 256 % tpq == 0 && ((uintptr_t)value % 16 == 0) && ((uintptr_t)gout % 16 == 0);
     WC_CHECK_ARG(quad || (!value_is_f16 && !gout_is_f16), "wc_msda_bwd: f16 value / gout need the channel-quad form");
+    {
+        const int rc = msda_bwd_value_check(sh, gout, gout_is_f16 ? 2 : 4, gvalue, gvalue16, ws, D);
+        if (rc != WC_OK) return rc;
+    }
     if (quad) {
         const long NQ = (long)N * Lq;
         const dim3 gd((unsigned)wc_cdiv(NQ, 256 / tpq));
@@ -867,6 +903,10 @@ extern "C" int wc_msda_bwd_f(const void* value, int value_is_f16, const int* h_s
     WC_CHECK_ARG(fill_shapes(&sh, h_shapes, n_levels, &S) == 0 && wc_msda_fused_supported(n_levels, M, D, P) &&
                  ld >= 3 * M * n_levels * P && (uintptr_t)value % 16 == 0 && (uintptr_t)gout % 16 == 0,
                  "wc_msda_bwd_f: unsupported configuration (see wc_msda_fused_supported) or misaligned buffers");
+    {
+        const int rc = msda_bwd_value_check(sh, gout, gout_is_f16 ? 2 : 4, gvalue, gvalue16, ws, D);
+        if (rc != WC_OK) return rc;
+    }
     const long NQ = (long)N * Lq;
     const dim3 gd((unsigned)wc_cdiv(NQ, 256 / (M * D / 4)));
     hipStream_t st = (hipStream_t)stream;
