@@ -521,6 +521,38 @@ int wc_augment_workspace_ints(int B, int crop, long* n_ints);       /* HOST out-
 int wc_augment_normalize(const void* src_u8, const void* params, float* dst, int* coeff_ws, int B, int Hs, int Ws, int crop,
                          const float* mean3, const float* std3, void* stream);
 
+/* ---- dense CRF (csrc/dcrf.hip; DESIGN.md "Dense CRF") -------------------------------------------------------------- */
+/* utils/dcrf.py (`DenseCRF`, `crf_inference`, `crf_inference_label`: pydensecrf's DenseCRF2D with one Gaussian and one
+ * bilateral Potts term) as the EXACT mean-field inference of the fully connected CRF (no permutohedral lattice; parity
+ * with pydensecrf: unpinned).  Pixel i = y * W + x; img (H,W,3) HWC, uint8 (img_is_u8 = 1) or f32; every (C,H,W) plane set
+ * is f32.  k_pos(i,j) = exp(-|p_i - p_j|^2 / (2 pos_xy_std^2)), k_bil(i,j) = exp(-|p_i - p_j|^2 / (2 bi_xy_std^2)
+ * - |c_i - c_j|^2 / (2 bi_rgb_std^2)), summed over every j (j = i included); S_m(i) = sum_j k_m(i,j), n_m = S_m^-1/2.
+ * Q0 = softmax(-U); each iteration Q = softmax_l(-U + sum_m w_m n_m(i) sum_j k_m(i,j) n_m(j) Q(l,j)).
+ * Limits (WC_ERR_ARG, nothing launched): 1 <= C <= 128, 1 <= H*W <= 640*640, every std finite and > 0, iter_max >= 0,
+ * weights finite and >= 0, non-null pointers.
+ * Error model of a message element M_m(l,i) = n_m(i) sum_j k_m(i,j) n_m(j) Q(l,j) against fp64:
+ *   |M - M64| <= eps * M64 + 2^-24 with eps = 2^-10 (all terms are non-negative).  Bilateral: f32 features, exponent from
+ *   exact feature differences, v_exp_f32, f32-input MFMA, per-64-key-tile then running f32 sums (bound ~2^-11.3 at 640^2).
+ *   Gaussian: separable passes truncated at R = ceil(pos_xy_std sqrt(60 ln 2)) (dropped mass < 2^-29 S_pos(i), also in
+ *   S_pos itself), f32 taps.  Deterministic: no atomics, bit-identical results from run to run.
+ * wc_dcrf_unary_prob:   unary (C,H,W) = -ln clamp(probs (C,H,W), 1e-5, 1)   (pydensecrf.utils.unary_from_softmax).
+ * wc_dcrf_unary_label:  labels (H,W) int64: unary = -ln gt_prob where l == label, else -ln((1 - gt_prob) / (C - 1))
+ *                       (labels outside [0,C) get the second value for every l); 0 < gt_prob < 1, C >= 2.
+ * wc_dcrf_unary_logits: logits (C,h,w) -> F.interpolate to (H,W) (bilinear, align_corners=False), softmax over C, clamp,
+ *                       -ln: the crf_proc composition of test_msc_flip_voc.py:153-157; the resized logits are never written.
+ * wc_dcrf_workspace_floats: *n_floats (HOST out-parameter) = H*W*(12 + 2*CP + 3*C), CP = 32*ceil(C/32): the f32 workspace
+ *                       `ws` of the two calls below.
+ * wc_dcrf_inference:    Q (C,H,W) after iter_max mean-field updates (iter_max = 0: softmax(-U)).
+ * wc_dcrf_message:      for the given Q (C,H,W): msg_pos / msg_bil (C,H,W) = M_pos / M_bil, S (2,H,W) = [S_pos, S_bil]. */
+int wc_dcrf_unary_prob(const float* probs, float* unary, int C, int H, int W, void* stream);
+int wc_dcrf_unary_label(const int64_t* labels, float* unary, int C, int H, int W, float gt_prob, void* stream);
+int wc_dcrf_unary_logits(const float* logits, float* unary, int C, int h, int w, int H, int W, void* stream);
+int wc_dcrf_workspace_floats(int C, int H, int W, long* n_floats);
+int wc_dcrf_inference(const void* img, int img_is_u8, const float* unary, float* Q, void* ws, int C, int H, int W,
+                      int iter_max, float pos_w, float pos_xy_std, float bi_w, float bi_xy_std, float bi_rgb_std, void* stream);
+int wc_dcrf_message(const void* img, int img_is_u8, const float* Q, float* msg_pos, float* msg_bil, float* S, void* ws,
+                    int C, int H, int W, float pos_xy_std, float bi_xy_std, float bi_rgb_std, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

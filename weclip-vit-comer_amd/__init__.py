@@ -79,9 +79,10 @@ def install_dropin(reference_root=None):
         from utils import evaluate;  import clip;  from pytorch_grad_cam import GradCAM
 
     `utils` resolves to this package's `utils` (losses, camutils, optimizer, evaluate, AverageMeter: the
-    modules on the hot path or imported next to it by the training script).  `reference_root`, if given, is a
-    checkout of the reference whose `utils/` directory is appended to that package's search path, so the helper
-    modules this package does not provide (imutils, dcrf, ...) still import from the user's tree."""
+    modules on the hot path or imported next to it by the training script; dcrf: the GPU dense CRF behind the
+    eval scripts' `from utils.dcrf import DenseCRF`).  `reference_root`, if given, is a checkout of the reference
+    whose `utils/` directory is appended to that package's search path, so the helper modules this package does
+    not provide (imutils, ...) still import from the user's tree."""
     global _finder
     import importlib
     import os

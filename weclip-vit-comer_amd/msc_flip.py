@@ -48,7 +48,8 @@ def resize_argmax(seg, out_hw):
 class MscFlipEvaluator:
     """`validate` of the reference, image by image.  model: WeCLIP (COCO or VOC) in eval mode on the GPU."""
 
-    def __init__(self, model, num_classes, scales=(1.0, 0.75), resize_long=512):
+    def __init__(self, model, num_classes, scales=(1.0, 0.75), resize_long=512, crf=None):
+        """crf: optional utils.dcrf.DenseCRF for `add_with_crf` (the reference's crf_proc leg, test_msc_flip_voc.py:139-185)."""
         L.require_gpu()
         self.model, self.nc, self.resize_long = model, int(num_classes), resize_long
         self.scales = [float(s) for s in scales]
@@ -56,6 +57,9 @@ class MscFlipEvaluator:
         self.hist = torch.zeros(self.nc, self.nc, device=dev, dtype=torch.int64)        # single scale, no flip (`_preds`)
         self.msc_hist = torch.zeros(self.nc, self.nc, device=dev, dtype=torch.int64)    # multi-scale + flip (`_msc_preds`)
         self.images = 0
+        self.crf = crf
+        if crf is not None:                                                              # msc logits -> CRF -> argmax
+            self.crf_hist = torch.zeros(self.nc, self.nc, device=dev, dtype=torch.int64)
 
     @torch.no_grad()
     def logits(self, inputs):
@@ -98,13 +102,41 @@ class MscFlipEvaluator:
         self.images += 1
         return seg_pred, msc_pred
 
+    @torch.no_grad()
+    def add_with_crf(self, inputs, labels, image):
+        """`add` plus the CRF leg: image (Hl,Wl,3) HWC (uint8 or float; numpy or torch) of the label grid.  The msc logits go
+        through the logits unary (bilinear to the label size, softmax, clip, -ln: crf_proc's composition,
+        test_msc_flip_voc.py:153-157), the dense CRF and an argmax.  Returns (seg_pred, msc_pred, crf_pred) (Hl,Wl) int64
+        on the device; updates hist and msc_hist exactly as `add` does, and crf_hist."""
+        if self.crf is None:
+            raise RuntimeError("add_with_crf needs MscFlipEvaluator(..., crf=DenseCRF(...))")
+        from .utils import dcrf
+        seg1, msc = self.logits(inputs.cuda())
+        lab = labels[0].cuda().long().contiguous()
+        seg_pred = resize_argmax(seg1, tuple(lab.shape))
+        msc_pred = resize_argmax(msc, tuple(lab.shape))
+        crf_pred = self.crf.with_unary(image, dcrf.unary_from_logits(msc, tuple(lab.shape))).argmax(0)
+        evaluate.confusion_hist(lab, seg_pred, self.nc, out=self.hist)
+        evaluate.confusion_hist(lab, msc_pred, self.nc, out=self.msc_hist)
+        evaluate.confusion_hist(lab, crf_pred, self.nc, out=self.crf_hist)
+        self.images += 1
+        return seg_pred, msc_pred, crf_pred
+
     def reduce(self, group=None):
         """Sum the histograms over the data-parallel ranks (one small int64 all-reduce each)."""
         reduce_hist(self.hist, group)
         reduce_hist(self.msc_hist, group)
+        if getattr(self, "crf_hist", None) is not None:
+            reduce_hist(self.crf_hist, group)
 
     def scores(self):
         return evaluate.scores_from_hist(self.hist.cpu().numpy()), evaluate.scores_from_hist(self.msc_hist.cpu().numpy())
+
+    def crf_scores(self):
+        """Scores of the CRF leg (msc logits -> dense CRF -> argmax)."""
+        if self.crf is None:
+            raise RuntimeError("no CRF leg: MscFlipEvaluator(..., crf=None)")
+        return evaluate.scores_from_hist(self.crf_hist.cpu().numpy())
 
 
 def reduce_hist(hist, group=None):

@@ -305,5 +305,19 @@ def _ln_backward(ctx, dy):
 torch.library.register_autograd(f"{_LIB}::layer_norm", _ln_backward, setup_context=_ln_setup)
 
 
+@torch.library.custom_op(f"{_LIB}::dense_crf", mutates_args=(), device_types="cuda")
+def dense_crf(image: Tensor, probs: Tensor, iter_max: int, pos_w: float, pos_xy_std: float, bi_w: float, bi_xy_std: float,
+              bi_rgb_std: float) -> Tensor:
+    """DenseCRF(iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std)(image, probs) (reference utils/dcrf.py) as the
+    exact mean-field inference: image (H,W,3) uint8 / float, probs (C,H,W) -> Q (C,H,W) f32.  No autograd."""
+    from .utils import dcrf
+    return dcrf.inference(image, dcrf.unary_from_prob(probs), iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std)
+
+
+@dense_crf.register_fake
+def _(image, probs, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
+    return probs.new_empty(probs.shape, dtype=F32)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
-       "seg_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd")
+       "seg_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf")
