@@ -255,7 +255,8 @@ int wc_layernorm(const float* x, long ldx, const float* w, const float* b, float
  *               softmax(QK^T)V with heads merged (the `.half()` input of the out-projection,
  *               myAtt.py:319-321); out32 (optional) the same before fp16 rounding;
  *               lse (B,H,L) f32 = log2-sum-exp2 of each score row.  V is read row-major from qkv.
- * wc_attn_mean: clip/myAtt.py:325-326: mean (B,L,L) f32 = (1/H) sum_h softmax_h. */
+ * wc_attn_mean: clip/myAtt.py:325-326: mean (B,L,L) f32 = (1/H) sum_h softmax_h.
+ * qkv, out and out32 must be 16-byte aligned (WC_ERR_ARG otherwise); so must qkv, dO and o32 of wc_attn_bwd_colsum. */
 int wc_attn_fwd(const void* qkv, void* out, float* out32, float* lse, int B, int L, int H, int DH,
                 void* stream);
 int wc_attn_mean(const void* qkv, const float* lse, float* mean, int B, int L, int H, int DH,
@@ -360,7 +361,7 @@ int wc_cam_upsample(const float* R, const int* nk, float* stats, float* cams, in
 /* wc_attn_bwd: backward of clip/myAtt.py:21-64 without storing L x L tensors: from the packed qkv
  * (q pre-scaled), dO (B*L,E) fp16, o32, lse -> dqkv (B*L,3E) fp16 hi (+lo, may be NULL), gradients
  * w.r.t. the UNSCALED in-projection output.  Workspaces qt, kt, dot: B*H*DH*Lp halves each;
- * delta: B*H*L floats. */
+ * delta: B*H*L floats.  qkv, dO, o32, qt, kt, dot 16-byte aligned, dqkv_hi / dqkv_lo 8-byte. */
 int wc_attn_bwd(const void* qkv, const void* dO, const float* o32, const float* lse, void* qt, void* kt,
                 void* dot, float* delta, void* dqkv_hi, void* dqkv_lo, int B, int L, int Lp, int H, int DH,
                 void* stream);

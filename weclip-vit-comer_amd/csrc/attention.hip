@@ -631,8 +631,10 @@ static int attn_origin(int L) {
 extern "C" int wc_attn_fwd(const void* qkv, void* out, float* out32, float* lse, int B, int L, int H, int DH,
                            void* stream) {
     const int E = H * DH;
-    WC_CHECK_ARG(qkv && out && lse && B > 0 && L > 0, "wc_attn_fwd: bad argument");
+    WC_CHECK_ARG(qkv && out && lse && B > 0 && L > 0 && H > 0, "wc_attn_fwd: bad argument");
     WC_CHECK_ARG(DH == 64 || DH == 32, "wc_attn_fwd: head dim must be 32 or 64 (got %d)", DH);
+    // qkv rows are read and out / out32 rows written as 16-byte vectors
+    WC_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)out32) % 16 == 0, "wc_attn_fwd: operands must be 16-byte aligned");
     WC_CHECK_ARG(E % 8 == 0 && B <= 65535 && H <= 65535 && (long)wc_cdiv(L, 128) * H * (B + 7) < (1L << 30),
                  "wc_attn_fwd: bad shape");
     const size_t lds = DH == 64 ? 2 * (64 * (64 * 2 + 16) + 64 * 128) : 2 * (64 * (32 * 2 + 16) + 64 * 64);
@@ -667,6 +669,7 @@ extern "C" int wc_attn_mean(const void* qkv, const float* lse, float* mean, int 
     const int E = H * DH;
     WC_CHECK_ARG(qkv && lse && mean && B > 0 && L > 0 && H > 0, "wc_attn_mean: bad argument");
     WC_CHECK_ARG(DH == 64 || DH == 32, "wc_attn_mean: head dim must be 32 or 64 (got %d)", DH);
+    WC_CHECK_ARG((uintptr_t)qkv % 16 == 0, "wc_attn_mean: qkv must be 16-byte aligned");
     const int r = attn_origin(L);
     const int nt = wc_cdiv(L - r, 128);
     dim3 grid((unsigned)(nt * nt * ((B + 7) / 8 * 8)));

@@ -393,13 +393,14 @@ extern "C" int wc_attn_bwd(const void* qkv, const void* dO, const float* o32, co
                            void* dot, float* delta, void* dqkv_hi, void* dqkv_lo, int B, int L, int Lp, int H, int DH,
                            void* stream) {
     const int E = H * DH;
-    WC_CHECK_ARG(qkv && dO && o32 && lse && qt && kt && dot && delta && dqkv_hi && B > 0 && L > 0 && Lp >= L &&
+    WC_CHECK_ARG(qkv && dO && o32 && lse && qt && kt && dot && delta && dqkv_hi && B > 0 && L > 0 && H > 0 && Lp >= L &&
                      Lp % 64 == 0 && E % 64 == 0,
                  "wc_attn_bwd: bad argument (Lp %% 64 == 0, (H*DH) %% 64 == 0)");
     WC_CHECK_ARG(DH == 64 || DH == 32, "wc_attn_bwd: head dim must be 32 or 64");
     hipStream_t st = (hipStream_t)stream;
-    WC_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)dO | (uintptr_t)qt | (uintptr_t)kt | (uintptr_t)dot) % 16 == 0,
-                 "wc_attn_bwd: operands must be 16-byte aligned");
+    WC_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)dO | (uintptr_t)o32 | (uintptr_t)qt | (uintptr_t)kt | (uintptr_t)dot) % 16 == 0 &&
+                     ((uintptr_t)dqkv_hi | (uintptr_t)dqkv_lo) % 8 == 0,
+                 "wc_attn_bwd: operands must be 16-byte aligned (dqkv: 8-byte)");
     dim3 tg(Lp / 64, 3 * (E / 64), B);
     hipLaunchKernelGGL(head_transpose_kernel, tg, dim3(256), 0, st, (const __half*)qkv, (const __half*)dO, (__half*)qt, (__half*)kt,
                        (__half*)dot, L, Lp, H, DH);

@@ -763,6 +763,8 @@ extern "C" int wc_attn_bwd_colsum(const void* qkv, const void* dO, const float* 
                  "wc_attn_bwd_colsum: bad argument");
     WC_CHECK_ARG(DH == 64 || DH == 32, "wc_attn_bwd_colsum: head dim must be 32 or 64");
     WC_CHECK_ARG(P <= 65535 && H <= 65535, "wc_attn_bwd_colsum: too many pairs/heads for one launch");
+    // qkv / dO rows are read as 16-byte vectors, o32 as pairs of float4
+    WC_CHECK_ARG(((uintptr_t)qkv | (uintptr_t)dO | (uintptr_t)o32) % 16 == 0, "wc_attn_bwd_colsum: operands must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int E = H * DH;
     const long total = (long)P * L;
