@@ -21,8 +21,8 @@ The conv stem (`SpatialPrior`) stays on its autograd Functions (hip_functional.c
 engine starts from its output and hands its gradient back.  With `adapters` set (`CoMerInteraction.forward_tokens`) the four
 WeCLIP adapter MLPs of the stage blocks run inside the engine on the encoder's f16 block outputs, and with
 `CoMerInteraction.direct_grads` (set by train_step.TrainStep) every parameter gradient is written straight into the views of
-the flat all-reduce bucket.  Parity: against an fp64 CPU evaluation of the same network and the module-by-module form
-(tests/test_comer_gpu.py); no reference code exists ("parity unpinned").  Runs in `fast` precision (single fp16 operands).
+the flat all-reduce bucket (grad_sink.py).  Parity: against an fp64 CPU evaluation of the same network and the module-by-module
+form (tests/test_comer_gpu.py); no reference code exists ("parity unpinned").  Runs in `fast` precision (single fp16 operands).
 """
 import ctypes
 
@@ -30,6 +30,7 @@ import torch
 
 from . import _lib as L
 from . import config, ops
+from .grad_sink import GradSink, handback, slices
 from .ops import F16, F32, Split
 
 GS = 4096.0
@@ -276,88 +277,33 @@ class ComerEngine:
         return y, ctx
 
     # ------------------------------------------------------------------------------------------ backward
-    def _direct(self, p):
-        """Where a parameter's gradient may be WRITTEN (not accumulated): its `.grad` when the owner opted in
-        (`CoMerInteraction.direct_grads`, set by TrainStep: the flat all-reduce bucket is zeroed every step and every gradient
-        is produced exactly once per backward), else None -> a fresh tensor handed back to autograd."""
-        rng = getattr(self.net, "direct_grads", False)
-        if p is None or not rng:
-            return None
-        g = p.grad
-        if g is None or not g.is_contiguous() or g.dtype != F32 or g.data_ptr() % 16:
-            return None
-        # only views of THE bucket that opted in are overwritten: any other .grad (gradient accumulation, a second TrainStep
-        # without a bucket, a harness calling backward twice) gets a fresh tensor that autograd accumulates as usual
-        if rng is not True and not (rng[0] <= g.data_ptr() < rng[1]):
-            return None
-        return g
-
-    def _wgrad(self, dy16, x16, M, N, K, grads, pw, pb, lda=None, xmap=None):
-        """pw.grad / pb.grad (unscaled) of y = x W^T + b from the fp16 operands dy16 (M, lda >= N) [x GS] and x16 (M, K)."""
-        tiles = ops.wgrad_tiles(N, K)
-        ns = 1
-        while ns * 2 * tiles <= _WGRAD_WGS and M // (ns * 2) >= 256:
-            ns *= 2
-        part, ns = ops.wgrad_partials(dy16, x16, M, N, K, lda=lda, slices=ns, bias=True, xmap=xmap)
-        gw, gb = self._direct(pw), self._direct(pb)
-        dw = gw.view(N, K) if gw is not None else torch.empty(N, K, device=dy16.device, dtype=F32)
-        db = gb if gb is not None else torch.empty(N, device=dy16.device, dtype=F32)
-        self._pending.append((part, dw, db, ns, N, K, 0, N))
-        if pw is not None:
-            grads[id(pw)] = dw.view(pw.shape)
-        if pb is not None:
-            grads[id(pb)] = db
+    def _wgrad(self, sink, dy16, x16, M, N, K, lin, lda=None, xmap=None):
+        """lin.weight / lin.bias gradients (unscaled) of y = x W^T + b from the fp16 operands dy16 (M, lda >= N) [x GS] and
+        x16 (M, K); lin None: into fresh (N, K) / (N) tensors.  -> (dW, db)."""
+        if lin is not None:
+            dw, db = sink.dest(lin.weight), sink.dest(lin.bias)
+        else:
+            dw, db = torch.empty(N, K, device=dy16.device, dtype=F32), torch.empty(N, device=dy16.device, dtype=F32)
+        sink.wgrad(dy16, x16, M, N, K, INV, [(dw, db)], ns=slices(M, ops.wgrad_tiles(N, K), _WGRAD_WGS), lda=lda, xmap=xmap)
         return dw, db
 
-    def _flush(self):
-        import struct
-        jobs = self._pending
-        if not jobs:
-            return
-        abits = struct.unpack("<I", struct.pack("<f", INV))[0]
-        flat = []
-        for part, dw, db, ns, N, K, r0, Ntot in jobs:          # rows [r0, r0 + N) of a (ns, Ntot, K + 1) partial matrix
-            flat += [part.data_ptr() + 4 * r0 * (K + 1), dw.data_ptr(), db.data_ptr(), ns, N, K, abits, Ntot * (K + 1)]
-        arr = (ctypes.c_int64 * len(flat))(*flat)
-        L.lib().wc_sum_slices_wb_multi(arr, len(jobs), L.stream())
-
-    def backward(self, ctx, dy):
-        """dy (B*h*w, C) f32 -> (dc0 (B, S, C), [dv x 4], {id(param): grad})."""
-        self._pending = []
-        try:
-            out = self._backward(ctx, dy)
-            self._flush()
-        finally:
-            self._pending = None
-        return out
-
-    def _ln_dest(self, ln):
-        """(2, D) destination of a LayerNorm's [dgamma; dbeta]: the adjacent views of the gradient bucket, or None."""
-        gw, gb = self._direct(ln.weight), self._direct(ln.bias)
-        if gw is not None and gb is not None and gb.data_ptr() == gw.data_ptr() + 4 * gw.numel():
-            return torch.as_strided(gw, (2, gw.numel()), (gw.numel(), 1))
-        return None
-
-    def _ln_bwd2(self, dya, lna, dyb, lnb, x, add, grads):
+    def _ln_bwd2(self, sink, dya, lna, dyb, lnb, x, add):
         """Both LayerNorms of one input in one pass (csrc/train_ops.hip ln_bwd_kernel<.., true>): -> (dx f32, dx f16)."""
         dx, dx16, ga, gb = ops.layernorm_bwd2(dya, self._b(lna.weight), dyb, self._b(lnb.weight), x, add=add, want32=True,
-                                              want16=True, alpha=INV, eps=lna.eps, dgba=self._ln_dest(lna), dgbb=self._ln_dest(lnb))
-        grads[id(lna.weight)], grads[id(lna.bias)] = ga[0], ga[1]
-        grads[id(lnb.weight)], grads[id(lnb.bias)] = gb[0], gb[1]
+                                              want16=True, alpha=INV, eps=lna.eps, dgba=sink.ln_dest(lna.weight, lna.bias),
+                                              dgbb=sink.ln_dest(lnb.weight, lnb.bias))
+        sink.put((lna.weight, lna.bias), ga)
+        sink.put((lnb.weight, lnb.bias), gb)
         return dx, dx16
 
-    def _ln_bwd(self, dy, x, ln, add, grads, want16=False):
+    def _ln_bwd(self, sink, dy, x, ln, add, want16=False):
         """dx = LN_bwd(dy) + add (f32) [and its f16 copy: the next GEMMs' operand, no separate conversion pass]."""
-        gw, gb = self._direct(ln.weight), self._direct(ln.bias)
-        dest = None
-        if gw is not None and gb is not None and gb.data_ptr() == gw.data_ptr() + 4 * gw.numel():
-            dest = torch.as_strided(gw, (2, gw.numel()), (gw.numel(), 1))       # weight / bias gradients adjacent in the bucket
         dx, dx16, dgb = ops.layernorm_bwd(dy, x, self._b(ln.weight), add=add, want32=True, want16=want16, alpha=INV, eps=ln.eps,
-                                          dgb=dest)
-        grads[id(ln.weight)], grads[id(ln.bias)] = dgb[0], dgb[1]
+                                          dgb=sink.ln_dest(ln.weight, ln.bias))
+        sink.put((ln.weight, ln.bias), dgb)
         return (dx, dx16) if want16 else dx
 
-    def _backward(self, ctx, dy):
+    def _backward(self, ctx, dy, sink):
         net = self.net
         B, S, C = ctx["B"], ctx["S"], ctx["C"]
         h, w = ctx["hw"]
@@ -368,11 +314,11 @@ class ComerEngine:
         lib = L.lib()
         WT = lambda n: self.wc.wT(n)[0]
         nst = len(net.stage_blocks)
-        grads, dvs = {}, [None] * nst
+        dvs = [None] * nst
         hs3 = _shape_array(shapes)
         # ---- fuse conv: dcat pieces and the fuse weight gradient (everything from here on is multiplied by GS)
         dy16 = self._f16(dy.float().contiguous(), alpha=GS)
-        self._wgrad(dy16, ctx["cat16"], Mv, C, 2 * nst * C, grads, net.fuse.weight, net.fuse.bias)
+        self._wgrad(sink, dy16, ctx["cat16"], Mv, C, 2 * nst * C, net.fuse)
         fuseT = WT("fuse").hi                                   # (2*nst*C, ldT = C)
         pieces = []
         for j in range(2 * nst):
@@ -391,117 +337,96 @@ class ComerEngine:
             dc3_16 = self._f16(dc3)
             du16 = torch.empty(Mc, C, device=dev, dtype=F16)
             self._mm(dc3_16, WT(f"f{i}.2"), Mc, C, C, out16=du16, act=7, aux=s["u"], ldaux=C, rpg=1)
-            self._wgrad(dc3_16, s["g2"], Mc, C, C, grads, t.ffn[2].weight, t.ffn[2].bias)
+            self._wgrad(sink, dc3_16, s["g2"], Mc, C, C, t.ffn[2])
             dn3 = torch.empty(Mc, C, device=dev, dtype=F16)            # (gradients that only feed a LayerNorm backward travel as fp16)
             self._mm(du16, WT(f"f{i}.0"), Mc, C, C, out16=dn3)
-            self._wgrad(du16, s["n3"], Mc, C, C, grads, t.ffn[0].weight, t.ffn[0].bias)
-            dc2, dc2_16 = self._ln_bwd(dn3, s["c2"], t.ffn_norm, dc3, grads, want16=True)
+            self._wgrad(sink, du16, s["n3"], Mc, C, C, t.ffn[0])
+            dc2, dc2_16 = self._ln_bwd(sink, dn3, s["c2"], t.ffn_norm, dc3, want16=True)
             # ---- CTI-toC
             do2 = torch.empty(Mc, C, device=dev, dtype=F16)
             self._mm(dc2_16, WT(f"c{i}.op"), Mc, C, C, out16=do2)
-            self._wgrad(dc2_16, s["o2"], Mc, C, C, grads, t.to_c.output_proj.weight, t.to_c.output_proj.bias)
+            self._wgrad(sink, dc2_16, s["o2"], Mc, C, C, t.to_c.output_proj)
             dval2_16, dow2 = self._msda_bwd(s["val2"], [(h, w)], s["loc2"], s["at2"], do2, t.to_c, B, S, s["ld2"])
             dq2 = torch.empty(Mc, C, device=dev, dtype=F16)
             self._mm(dow2, WT(f"c{i}.ow"), Mc, C, s["ld2"], out16=dq2)
-            self._ow_grads(dow2, s["q2"], Mc, s["n2"], s["ld2"], t.to_c, grads)
+            self._ow_grads(sink, dow2, s["q2"], Mc, s["n2"], s["ld2"], t.to_c)
             # (LN_nc_q(c1) and LN_nv_f(c1) normalise the same rows: their backward runs as ONE pass below, once df1 exists)
             df2 = torch.empty(Mv, C, device=dev, dtype=F16)
             self._mm(dval2_16, WT(f"c{i}.vp"), Mv, C, C, out16=df2)
-            self._wgrad(dval2_16, s["f2"], Mv, C, C, grads, t.to_c.value_proj.weight, t.to_c.value_proj.bias)
-            dv1, dv1_16 = self._ln_bwd(df2, s["v1"], t.nc_f, pieces[2 * i], grads, want16=True)
+            self._wgrad(sink, dval2_16, s["f2"], Mv, C, C, t.to_c.value_proj)
+            dv1, dv1_16 = self._ln_bwd(sink, df2, s["v1"], t.nc_f, pieces[2 * i], want16=True)
             # ---- CTI-toV: v1 = v + gamma * (o1 Wop^T + bop)
             gam = self._b(t.gamma)
             gdv1_16 = self._f16(dv1, cs=gam.view(1, C))
             do1 = torch.empty(Mv, C, device=dev, dtype=F16)
             self._mm(gdv1_16, WT(f"v{i}.op"), Mv, C, C, out16=do1)
-            G, gsum = self._wgrad(dv1_16, s["o1"], Mv, C, C, grads, None, None)          # G = dv1^T o1, gsum = dv1^T 1 (unscaled)
+            G, gsum = self._wgrad(sink, dv1_16, s["o1"], Mv, C, C, None)          # G = dv1^T o1, gsum = dv1^T 1 (unscaled)
             self._gamma_jobs.append((t, G, gsum))
             dval1_16, dow1 = self._msda_bwd(s["val1"], shapes, s["loc1"], s["at1"], do1, t.to_v, B, nhw, s["ld1"])
             dq1 = torch.empty(Mv, C, device=dev, dtype=F16)
             self._mm(dow1, WT(f"v{i}.ow"), Mv, C, s["ld1"], out16=dq1)
-            self._ow_grads(dow1, s["q1"], Mv, s["n1"], s["ld1"], t.to_v, grads)
+            self._ow_grads(sink, dow1, s["q1"], Mv, s["n1"], s["ld1"], t.to_v)
             if "t1" in s:              # the adapter MLP behind v: v = t1 W2^T + b2, t1 = relu(x W1^T + b1); x is frozen
                 ad = self.adapters[i]
-                dvs[i], dv16 = self._ln_bwd(dq1, s["v"], t.nv_q, dv1, grads, want16=True)
-                self._wgrad(dv16, s["t1"], Mv, C, C, grads, ad.proj_2.weight, ad.proj_2.bias)
+                dvs[i], dv16 = self._ln_bwd(sink, dq1, s["v"], t.nv_q, dv1, want16=True)
+                self._wgrad(sink, dv16, s["t1"], Mv, C, C, ad.proj_2)
                 dt1 = torch.empty(Mv, C, device=dev, dtype=F16)
                 self._mm(dv16, WT(f"a{i}.p2"), Mv, C, C, out16=dt1, act=5, auxh=s["t1"], ldaux=C)
-                self._wgrad(dt1, s["x16"], Mv, C, s["x16"].shape[1], grads, ad.proj.weight, ad.proj.bias, xmap=(nhw, s["Lq"], 1))
+                self._wgrad(sink, dt1, s["x16"], Mv, C, s["x16"].shape[1], ad.proj, xmap=(nhw, s["Lq"], 1))
                 dvs[i] = None
             else:
-                dvs[i] = self._ln_bwd(dq1, s["v"], t.nv_q, dv1, grads)
+                dvs[i] = self._ln_bwd(sink, dq1, s["v"], t.nv_q, dv1)
             df1 = torch.empty(Mc, C, device=dev, dtype=F16)
             self._mm(dval1_16, WT(f"v{i}.vp"), Mc, C, C, out16=df1)
-            self._wgrad(dval1_16, s["f1"], Mc, C, C, grads, t.to_v.value_proj.weight, t.to_v.value_proj.bias)
+            self._wgrad(sink, dval1_16, s["f1"], Mc, C, C, t.to_v.value_proj)
             if t.nc_q.eps == t.nv_f.eps and C <= 256:
-                dc1, dc1_16 = self._ln_bwd2(dq2, t.nc_q, df1, t.nv_f, s["c1"], dc2, grads)
+                dc1, dc1_16 = self._ln_bwd2(sink, dq2, t.nc_q, df1, t.nv_f, s["c1"], dc2)
             else:
-                dc1 = self._ln_bwd(dq2, s["c1"], t.nc_q, dc2, grads)
-                dc1, dc1_16 = self._ln_bwd(df1, s["c1"], t.nv_f, dc1, grads, want16=True)
+                dc1 = self._ln_bwd(sink, dq2, s["c1"], t.nc_q, dc2)
+                dc1, dc1_16 = self._ln_bwd(sink, df1, s["c1"], t.nv_f, dc1, want16=True)
             # ---- MRFP
             dx2 = torch.empty(Mc, hid, device=dev, dtype=F16)          # fp16 out: the epilogue's wide (row-major) path
             self._mm(dc1_16, WT(f"m{i}.fc2"), Mc, hid, C, out16=dx2, act=7, aux=s["x2"], ldaux=hid, rpg=1)
-            self._wgrad(dc1_16, s["g16"], Mc, C, hid, grads, m.fc2.weight, m.fc2.bias)
+            self._wgrad(sink, dc1_16, s["g16"], Mc, C, hid, m.fc2)
             dx1_16 = torch.empty(Mc, hid, device=dev, dtype=F16)
-            half = hid // 2
-            dst = [self._direct(q) for q in (m.dw3.weight, m.dw3.bias, m.dw5.weight, m.dw5.bias)]
-            dw3 = dst[0].view(half, 9) if dst[0] is not None else torch.empty(half, 9, device=dev, dtype=F32)
-            db3 = dst[1] if dst[1] is not None else torch.empty(half, device=dev, dtype=F32)
-            dw5 = dst[2].view(half, 25) if dst[2] is not None else torch.empty(half, 25, device=dev, dtype=F32)
-            db5 = dst[3] if dst[3] is not None else torch.empty(half, device=dev, dtype=F32)
+            dw3, db3, dw5, db5 = (sink.dest(q) for q in (m.dw3.weight, m.dw3.bias, m.dw5.weight, m.dw5.bias))
             npart = ctypes.c_long(0)
             lib.wc_mrfp_dwconv_parts(hs3, len(shapes), B, hid, ctypes.byref(npart))
             part = torch.empty(npart.value * hid * 26, device=dev, dtype=F32)
             lib.wc_mrfp_dwconv_bwd(L.ptr(dx2), 1, L.ptr(s["x1"]), L.ptr(self._b(m.dw3.weight).view(-1), F32),
                                    L.ptr(self._b(m.dw5.weight).view(-1), F32), None, L.ptr(dx1_16), L.ptr(dw3), L.ptr(db3), L.ptr(dw5),
                                    L.ptr(db5), L.ptr(part), INV, hs3, len(shapes), B, hid, L.stream())
-            grads[id(m.dw3.weight)], grads[id(m.dw3.bias)] = dw3.view(m.dw3.weight.shape), db3
-            grads[id(m.dw5.weight)], grads[id(m.dw5.bias)] = dw5.view(m.dw5.weight.shape), db5
             dc = torch.empty(Mc, C, device=dev, dtype=F32)
             self._mm(dx1_16, WT(f"m{i}.fc1"), Mc, C, hid, out32=dc, resid=dc1)
-            self._wgrad(dx1_16, s["c16"], Mc, hid, C, grads, m.fc1.weight, m.fc1.bias)
+            self._wgrad(sink, dx1_16, s["c16"], Mc, hid, C, m.fc1)
             dc3 = dc
-        return dc3, dvs, grads
+        return dc3, dvs
 
-    def _ow_grads(self, dow16, q16, M, n, ld, att, grads):
+    def _ow_grads(self, sink, dow16, q16, M, n, ld, att):
         """Weight / bias gradients of the stacked sampling_offsets | attention_weights GEMM: ONE split-K weight-gradient GEMM over
         the stacked columns, then one reduction job per Linear over its row range of the partials, written straight into that
         parameter's gradient (the bucket view when TrainStep opted in) -- no slicing / accumulate launches afterwards."""
         K = att.d_model
-        tiles = ops.wgrad_tiles(n, K)
-        ns = 1
-        while ns * 2 * tiles <= _WGRAD_WGS and M // (ns * 2) >= 256:
-            ns *= 2
-        part, ns = ops.wgrad_partials(dow16, q16, M, n, K, lda=ld, slices=ns, bias=True)
-        r0 = 0
-        for lin in (att.sampling_offsets, att.attention_weights):
-            rows = lin.weight.shape[0]
-            gw, gb = self._direct(lin.weight), self._direct(lin.bias)
-            dw = gw.view(rows, K) if gw is not None else torch.empty(rows, K, device=dow16.device, dtype=F32)
-            db = gb if gb is not None else torch.empty(rows, device=dow16.device, dtype=F32)
-            self._pending.append((part, dw, db, ns, rows, K, r0, n))
-            grads[id(lin.weight)], grads[id(lin.bias)] = dw.view(lin.weight.shape), db
-            r0 += rows
+        outs = [(sink.dest(lin.weight), sink.dest(lin.bias)) for lin in (att.sampling_offsets, att.attention_weights)]
+        sink.wgrad(dow16, q16, M, n, K, INV, outs, ns=slices(M, ops.wgrad_tiles(n, K), _WGRAD_WGS), lda=ld)
 
     def run_backward(self, ctx, dy):
-        """backward() plus the tiny post-processing that needs the reduced partials: the stacked gradients are split into
-        their two Linears, and gamma's gradient comes out of the output projection's un-gated weight gradient
-        G = dv1^T o1:  dWop = diag(gamma) G,  dbop = gamma * s,  dgamma = rowsum(Wop * G) + bop * s  (s = dv1^T 1)."""
+        """dy (B*h*w, C) f32 -> (dc0 (B, S, C), [dv x 4], {id(param): grad}): the backward pass, its weight-gradient reductions
+        as ONE launch, then the tiny post-processing that needs the reduced partials: gamma's gradient comes out of the output
+        projection's un-gated weight gradient G = dv1^T o1:  dWop = diag(gamma) G,  dbop = gamma * s,
+        dgamma = rowsum(Wop * G) + bop * s  (s = dv1^T 1)."""
         self._gamma_jobs = []
-        dc0, dvs, grads = self.backward(ctx, dy)
+        with GradSink(self.net.direct_grads) as sink:
+            dc0, dvs = self._backward(ctx, dy, sink)
         for t, G, gsum in self._gamma_jobs:
             op = t.to_v.output_proj
-            dst = [self._direct(q) for q in (op.weight, op.bias, t.gamma)]
-            dW = dst[0] if dst[0] is not None else torch.empty_like(G)
-            db = dst[1] if dst[1] is not None else torch.empty_like(gsum)
-            dg = dst[2] if dst[2] is not None else torch.empty_like(gsum)
+            dW, db, dg = (sink.dest(q) for q in (op.weight, op.bias, t.gamma))
             L.lib().wc_cti_gate_grads(L.ptr(G, F32), L.ptr(gsum, F32), L.ptr(self._b(t.gamma), F32), L.ptr(self._b(op.weight), F32),
                                       L.ptr(self._b(op.bias), F32), L.ptr(dW, F32), L.ptr(db, F32), L.ptr(dg, F32), G.shape[0], G.shape[1],
                                       L.stream())
-            grads[id(op.weight)], grads[id(op.bias)], grads[id(t.gamma)] = dW.view(op.weight.shape), db, dg
         self._gamma_jobs = None
         B, S, C = ctx["B"], ctx["S"], ctx["C"]
-        return (dc0 * INV).view(B, S, C), [d * INV if d is not None else None for d in dvs], grads
+        return (dc0 * INV).view(B, S, C), [d * INV if d is not None else None for d in dvs], sink.grads
 
 
 class ComerFunction(torch.autograd.Function):
@@ -518,13 +443,7 @@ class ComerFunction(torch.autograd.Function):
         eng = ctx.engine
         dc0, dvs, grads = eng.run_backward(ctx.c, dy.contiguous())
         ctx.c = None
-        out = []
-        for p in eng.params():
-            g = grads.get(id(p))
-            if g is not None and p.grad is not None and g.data_ptr() == p.grad.data_ptr():
-                g = None                                   # written straight into the caller's gradient buffer (see _direct)
-            out.append(g.reshape(p.shape) if g is not None else None)
-        return (None, None, None, dc0) + tuple(d.view(s) for d, s in zip(dvs, ctx.map_shapes)) + tuple(out)
+        return (None, None, None, dc0) + tuple(d.view(s) for d, s in zip(dvs, ctx.map_shapes)) + handback(eng.params(), grads)
 
 
 class ComerTokensFunction(torch.autograd.Function):
@@ -541,10 +460,4 @@ class ComerTokensFunction(torch.autograd.Function):
         eng = ctx.engine
         dc0, _, grads = eng.run_backward(ctx.c, dy.contiguous())
         ctx.c = None
-        out = []
-        for p in eng.params():
-            g = grads.get(id(p))
-            if g is not None and p.grad is not None and g.data_ptr() == p.grad.data_ptr():
-                g = None
-            out.append(g.reshape(p.shape) if g is not None else None)
-        return (None, None, None, None, dc0, None, None, None, None) + tuple(out)
+        return (None, None, None, None, dc0, None, None, None, None) + handback(eng.params(), grads)

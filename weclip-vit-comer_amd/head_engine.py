@@ -18,6 +18,7 @@ import torch
 
 from . import config, ops
 from .clip import vit_engine as VE
+from .grad_sink import GradSink, handback, slices
 from .ops import F16, F32, Split
 
 GRAD_SCALE = 4096.0
@@ -47,8 +48,8 @@ class HeadEngine:
         self.E = dec.linear_pred.weight.shape[1]
         self.nc = dec.linear_pred.weight.shape[0]
         self.index = fuse.indexes
-        # name -> fp32 buffer the gradient of that parameter is written INTO (not accumulated) by backward();
-        # set by TrainStep to views of its flat all-reduce bucket so no per-parameter copy/add kernels run
+        # (lo, hi) address range of the gradient bucket whose `.grad` views backward() may WRITE (grad_sink.GradSink), or
+        # None; set by TrainStep so no per-parameter copy/add kernels run
         self.direct_grads = None
         self.fwd_stream = None          # set by WeCLIP.forward while the head forward runs beside the CAM chain
         self.row_gemm = True            # K = N = 256 Linears on the row-streaming GEMM kernel (False: tile kernels, for A/B)
@@ -57,15 +58,8 @@ class HeadEngine:
     def params(self):
         return list(self.fuse.parameters()) + list(self.dec.parameters())
 
-    def param_names(self):
-        return ["fuse." + n for n, _ in self.fuse.named_parameters()] + \
-               ["dec." + n for n, _ in self.dec.named_parameters()]
-
     def dec_params(self):
         return list(self.dec.parameters())
-
-    def dec_param_names(self):
-        return ["dec." + n for n, _ in self.dec.named_parameters()]
 
     def _weight_matrices(self):
         out = []
@@ -85,7 +79,7 @@ class HeadEngine:
         drop_scale (B, E) f32 = Dropout2d mask / (1 - p) or None.  Returns (seg, attn_pred, ctx).
         F_rows (B*h*w, E) f32, if given, replaces the adapters + fuse stage (the ViT-CoMer inserts produce the
         decoder input themselves): only the decoder, linear_pred and attn_pred run here, and backward() returns
-        the gradient w.r.t. F_rows under the key "__dF__"."""
+        the gradient w.r.t. F_rows too."""
         ex = config.exact()
         E, hw, M = self.E, h * w, B * h * w
         n = self.index
@@ -203,60 +197,22 @@ class HeadEngine:
 
     # ------------------------------------------------------------------------------ backward
     def backward(self, ctx, dseg, dap):
-        """dseg (B,nc,h,w) / dap (B,hw,hw) fp32 (either may be None).  Returns {param name: grad}.
-        The split-K reductions of all weight gradients are collected and run as ONE launch at the end
-        (wc_sum_slices_wb_multi; 16 launches of 5-7 us at the launch floor otherwise)."""
-        self._pending = []
+        """dseg (B,nc,h,w) / dap (B,hw,hw) fp32 (either may be None).  Returns ({id(param): grad}, the gradient w.r.t.
+        F_rows or None).  The split-K reductions of all weight gradients are collected and run as ONE launch at the end."""
         # (the weight-gradient GEMMs on a second stream beside the data-gradient chain were measured neutral in round 3: one stream)
-        try:
-            grads = self._backward_impl(ctx, dseg, dap)
-            self._flush_reductions()
-        finally:
-            self._pending = None
-        return grads
+        with GradSink(self.direct_grads) as sink:
+            dF = self._backward_impl(ctx, dseg, dap, sink)
+        return sink.grads, dF
 
-    def _partials(self, *a, **kw):
-        return ops.wgrad_partials(*a, **kw)
-
-    def _reduce(self, part, gw, gb, ns, N_, K_, alpha, groups=1, sw=0, sb=0):
-        """dW / db = alpha * sum of the `ns` split-K slices of `part`: queued while a backward pass is collecting,
-        launched right away otherwise."""
-        from . import _lib as L
-        if getattr(self, "_pending", None) is None:
-            if groups == 1:
-                L.lib().wc_sum_slices_wb(L.ptr(part, F32), L.ptr(gw, F32), L.ptr(gb, F32), ns, N_, K_, alpha, L.stream())
-            else:
-                L.lib().wc_sum_slices_wb_grouped(L.ptr(part, F32), L.ptr(gw, F32), L.ptr(gb, F32), ns, N_, K_, alpha, groups,
-                                                 sw, sb, L.stream())
-            return
-        import struct
-        abits = struct.unpack("<I", struct.pack("<f", float(alpha)))[0]
-        per = ns * N_ * (K_ + 1)
-        for g in range(groups):
-            self._pending.append((part, part.data_ptr() + 4 * g * per, gw.data_ptr() + 4 * g * sw, gb.data_ptr() + 4 * g * sb,
-                                  ns, N_, K_, abits, 0))
-
-    def _flush_reductions(self):
-        jobs = self._pending
-        if not jobs:
-            return
-        import ctypes
-        from . import _lib as L
-        flat = []
-        for j in jobs:
-            flat.extend(j[1:])
-        arr = (ctypes.c_int64 * len(flat))(*flat)
-        L.lib().wc_sum_slices_wb_multi(arr, len(jobs), L.stream())      # the partial buffers stay referenced by `jobs` until here
-
-    def _backward_impl(self, ctx, dseg, dap):
+    def _backward_impl(self, ctx, dseg, dap, sink):
         B, h, w, ex = ctx["B"], ctx["h"], ctx["w"], ctx["ex"]
         E, hw, M, nc, n = self.E, h * w, B * h * w, self.nc, self.index
         dev = ctx["F32"].device
         GS, inv = GRAD_SCALE, 1.0 / GRAD_SCALE
-        grads = {}
-        wg = lambda dy16, x16, N_, K_, wn, bn, **kw: self._wgrad(dy16, x16, M, N_, K_, inv, grads, wn, bn, **kw)
+        wg = lambda dy16, x16, N_, K_, pw, pb, **kw: self._wgrad(sink, dy16, x16, M, N_, K_, inv, pw, pb, **kw)
         # ---- linear_pred
         x3h = ctx["blocks"][-1]["x2h"]
+        pred = self.dec.linear_pred
         if dseg is not None:
             wpT, ldT = self.wcache.wT("pred")          # (E, ldT): the nc class columns, zero padded to a multiple of 64
             d = torch.zeros(M, ldT, device=dev, dtype=F32)
@@ -264,14 +220,14 @@ class HeadEngine:
             _, dS = ops.colscale_split(d, None, M, alpha=GS, want32=False, with_lo=ex)
             dx = torch.empty(M, E, device=dev, dtype=F32)
             ops.gemm(dS, wpT, M, E, ldT, out32=dx)
-            wg(dS.hi, x3h.hi, nc, E, "dec.linear_pred.weight", "dec.linear_pred.bias", lda=ldT)
+            wg(dS.hi, x3h.hi, nc, E, pred.weight, pred.bias, lda=ldT)
         else:
             dx = torch.zeros(M, E, device=dev, dtype=F32)
-            grads["dec.linear_pred.weight"] = torch.zeros(nc, E, 1, 1, device=dev)
-            grads["dec.linear_pred.bias"] = torch.zeros(nc, device=dev)
+            sink.dest(pred.weight).zero_()
+            sink.dest(pred.bias).zero_()
         # ---- decoder blocks, last to first
         for i in reversed(range(len(ctx["blocks"]))):
-            dx = self._block_bwd(ctx["blocks"][i], dx, B, hw, f"dec.transformer.resblocks.{i}.", grads, inv)
+            dx = self._block_bwd(ctx["blocks"][i], dx, B, hw, sink, inv)
         # ---- attn_pred = sigmoid(F^T F):  dF += (Z + Z^T) F
         if dap is not None:
             S = ops.sigmoid_gram_bwd(dap.contiguous(), ctx["ap"], scale=GS, with_lo=ex)
@@ -282,14 +238,13 @@ class HeadEngine:
         else:
             dF = dx
         if not ctx.get("front", True):          # decoder-only mode: the caller owns everything in front of F
-            grads["__dF__"] = dF * inv          # gradients are carried multiplied by GRAD_SCALE
-            return grads
+            return dF * inv                     # gradients are carried multiplied by GRAD_SCALE
         # ---- Dropout2d backward + fuse
         _, dFp = ops.colscale_split(dF, ctx["drop"], hw, want32=False, with_lo=ex)
         cat = ctx["cat"]
         dcat = Split(torch.empty(M, n * E, device=dev, dtype=F16), torch.empty(M, n * E, device=dev, dtype=F16) if ex else None)
         ops.gemm(dFp, self.wcache.wT("fuse")[0], M, n * E, E, out16=dcat.hi, out16lo=dcat.lo)
-        wg(dFp.hi, cat.hi, E, n * E, "fuse.linear_fuse.weight", "fuse.linear_fuse.bias")
+        wg(dFp.hi, cat.hi, E, n * E, self.fuse.linear_fuse.weight, self.fuse.linear_fuse.bias)
         # ---- adapters
         xs, Lq = ctx["xs"], ctx["L"]
         C = xs[0].hi.shape[1]
@@ -302,27 +257,18 @@ class HeadEngine:
         elif grouped:       # dt1[l] = (dcat[:, l] W2[l]) * relu'(t1[l]) for all adapters in one grouped launch
             ops.gemm(dcat, self.wcache.wT("ad0.proj_2")[0], M, E, E, lda=n * E, out16=dt1b, act=5, auxh=ctx["t1b"].hi,
                      ldaux=E, batch=n, zdiv=1, sA2=E, sW2=swT, sC2=M * E, sX2=M * E)
-        if grouped and self._adapter_wgrads_grouped(ctx, dcat, dt1b, xs, B, Lq, C, M, inv, grads):
-            return grads
+        if grouped and self._adapter_wgrads_grouped(ctx, dcat, dt1b, xs, B, Lq, C, M, inv, sink):
+            return None
         for l, mlp in enumerate(self.fuse.linears_modulelist):
-            p = f"fuse.linears_modulelist.{l}."
             dt2 = Split(dcat.hi.view(-1)[l * E:], dcat.lo.view(-1)[l * E:] if ex else None)
             t1 = ctx["t1s"][l]
             dt1_16 = dt1b[l]
             if not grouped:
                 ops.gemm(dt2, self.wcache.wT(f"ad{l}.proj_2")[0], M, E, E, lda=n * E, out16=dt1_16, act=5, auxh=t1.hi, ldaux=E)
-            wg(dt2.hi, t1.hi, E, E, p + "proj_2.weight", p + "proj_2.bias", lda=n * E)
+            wg(dt2.hi, t1.hi, E, E, mlp.proj_2.weight, mlp.proj_2.bias, lda=n * E)
             # X = the hw patch rows of every image of the (B, 1 + hw, C) encoder tokens (CLS rows skipped)
-            wg(dt1_16, xs[l].hi, E, C, p + "proj.weight", p + "proj.bias", xmap=(hw, Lq, 1))
-        return grads
-
-    def _dest(self, name, shape):
-        """Where a parameter gradient is written: the caller-provided buffer (TrainStep's flat gradient
-        bucket, `direct_grads`) or a fresh dense tensor."""
-        d = self.direct_grads.get(name) if self.direct_grads else None
-        if d is not None:
-            return d.view(shape)
-        return torch.empty(shape, device=self.dec.linear_pred.weight.device, dtype=F32)
+            wg(dt1_16, xs[l].hi, E, C, mlp.proj.weight, mlp.proj.bias, xmap=(hw, Lq, 1))
+        return None
 
     def _adapter_groups(self, xs, B, Lq, C, ex):
         """(stacked block outputs Split (n, B*L, C), element stride between consecutive adapters' `proj` / `proj_2`
@@ -343,91 +289,75 @@ class HeadEngine:
             st.append(d // 2)
         return Split(big, xs.big_lo if ex else None), st[0], st[1]
 
-    def _adapter_wgrads_grouped(self, ctx, dcat, dt1b, xs, B, Lq, C, M, inv, grads):
+    def _adapter_wgrads_grouped(self, ctx, dcat, dt1b, xs, B, Lq, C, M, inv, sink):
         """Weight / bias gradients of all n adapters in two grouped weight-gradient GEMMs + two grouped split-K
         reductions (instead of 2 n + 2 n launches), written straight into the caller's gradient bucket.  Needs the
         stacked encoder outputs and bucket views at a uniform stride between adapters; returns False otherwise."""
         n, E, hw = self.index, self.E, ctx["h"] * ctx["w"]
         big = getattr(xs, "big", None)
-        if big is None or not self.direct_grads or tuple(big.shape) != (n, B * Lq, C):
+        if big is None or tuple(big.shape) != (n, B * Lq, C):
             return False
-        names = [[f"fuse.linears_modulelist.{l}.{k}" for l in range(n)] for k in ("proj.weight", "proj.bias", "proj_2.weight", "proj_2.bias")]
-        dst = [[self.direct_grads.get(nm) for nm in row] for row in names]
-        if any(d is None or not d.is_contiguous() for row in dst for d in row):
+        mods = self.fuse.linears_modulelist
+        params = [[m.proj.weight for m in mods], [m.proj.bias for m in mods], [m.proj_2.weight for m in mods],
+                  [m.proj_2.bias for m in mods]]
+        dst = [[sink.direct(p) for p in row] for row in params]
+        if any(d is None for row in dst for d in row):
             return False
         st = [_uniform_stride(row) for row in dst]
         if any(v is None for v in st):
             return False
-        from . import _lib as L
 
         def run(dy, lda, gA, x, ldx, gX, N_, K_, xmap, gw, gb, sw, sb):
             tiles = ops.wgrad_tiles(N_, K_) * n
             ns = max(1, min(_WGRAD_WGS // tiles, M // 256))       # one round of workgroups (2 per CU), few partials
-            part, ns = self._partials(dy, x, M, N_, K_, lda=lda, ldx=ldx, slices=ns, bias=True, xmap=xmap, groups=n, gA=gA, gX=gX)
-            self._reduce(part, gw, gb, ns, N_, K_, inv, groups=n, sw=sw, sb=sb)
+            sink.wgrad(dy, x, M, N_, K_, inv, [(gw, gb)], ns=ns, lda=lda, ldx=ldx, xmap=xmap, groups=n, gA=gA, gX=gX, sw=sw, sb=sb)
 
         # proj_2: dY = dcat[:, l*E:(l+1)*E], X = t1[l];   proj: dY = dt1[l], X = patch rows of block output l
         run(dcat.hi, n * E, E, ctx["t1b"].hi, E, M * E, E, E, None, dst[2][0], dst[3][0], st[2], st[3])
         run(dt1b, E, M * E, big, C, B * Lq * C, E, C, (hw, Lq, 1), dst[0][0], dst[1][0], st[0], st[1])
-        for row, drow in zip(names, dst):
-            for nm, d in zip(row, drow):
-                grads[nm] = d
+        for row, drow in zip(params, dst):
+            sink.put(row, drow)
         return True
 
-    def _ln_dest(self, wname, bname, D):
-        """(2, D) view over the weight and bias gradient buffers of a LayerNorm when the caller's bucket holds them
-        back to back (parameters() order: weight, bias), else None (layernorm_bwd then allocates)."""
-        gw = self.direct_grads.get(wname) if self.direct_grads else None
-        gb = self.direct_grads.get(bname) if self.direct_grads else None
-        if gw is None or gb is None or not gw.is_contiguous() or gb.data_ptr() != gw.data_ptr() + 4 * D:
-            return None
-        return torch.as_strided(gw, (2, D), (D, 1))
-
-    def _wgrad(self, dy16, x16, M, N_, K_, inv, grads, wname, bname, lda=None, ldx=None, xmap=None):
+    def _wgrad(self, sink, dy16, x16, M, N_, K_, inv, pw, pb, lda=None, ldx=None, xmap=None):
         """dW (N_, K_) = inv * dY^T X and db (N_) = inv * dY^T 1 from the row-major fp16 operands as they lie
         in memory (csrc/gemm.hip gemm_km_kernel: transposing LDS reads, no operand transposes).  The output has
         few 128x128 tiles and a long contraction (all tokens), so the tokens are split over `ns` slices
-        (blockIdx.z); wc_sum_slices_wb sums them straight into the dense weight / bias gradient buffers."""
-        tiles = ops.wgrad_tiles(N_, K_)
-        ns = 1
-        while ns * 2 * tiles <= _WGRAD_WGS and M // (ns * 2) >= 256:
-            ns *= 2
-        part, ns = self._partials(dy16, x16, M, N_, K_, lda=lda, ldx=ldx, slices=ns, bias=True, xmap=xmap)
-        gw, gb = self._dest(wname, (N_, K_)), self._dest(bname, (N_,))
-        self._reduce(part, gw, gb, ns, N_, K_, inv)
-        grads[wname], grads[bname] = gw, gb
+        (blockIdx.z); the queued reduction sums them straight into the dense weight / bias gradient buffers."""
+        ns = slices(M, ops.wgrad_tiles(N_, K_), _WGRAD_WGS)
+        sink.wgrad(dy16, x16, M, N_, K_, inv, [(sink.dest(pw), sink.dest(pb))], ns=ns, lda=lda, ldx=ldx, xmap=xmap)
 
-    def _block_bwd(self, c, dx2, B, Lq, prefix, grads, inv):
+    def _block_bwd(self, c, dx2, B, Lq, sink, inv):
         pk, blk = c["pk"], c["blk"]
         M, E, H, DH = B * Lq, pk.E, pk.H, pk.DH
         dev = dx2.device
         ex = pk.exact
-        wg = lambda dy16, x16, N_, K_, wn, bn, **kw: self._wgrad(dy16, x16, M, N_, K_, inv, grads, wn, bn, **kw)
+        wg = lambda dy16, x16, N_, K_, pw, pb, **kw: self._wgrad(sink, dy16, x16, M, N_, K_, inv, pw, pb, **kw)
         # MLP
         _, dx2s = ops.colscale_split(dx2, None, M, want32=False, with_lo=ex)
         du = Split(torch.empty(M, 4 * E, device=dev, dtype=F16), torch.empty(M, 4 * E, device=dev, dtype=F16) if ex else None)
         wT = lambda k: self.wcache.wT(f"b{c['i']}.{k}")[0]
         ops.gemm(dx2s, wT("pj"), M, 4 * E, E, out16=du.hi, out16lo=du.lo, act=4, aux=c["u32"],
                  ldaux=4 * E, rpg=1)
-        wg(dx2s.hi, c["z"].hi, E, 4 * E, prefix + "mlp.c_proj.weight", prefix + "mlp.c_proj.bias")
+        wg(dx2s.hi, c["z"].hi, E, 4 * E, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias)
         da2 = torch.empty(M, E, device=dev, dtype=F32)
         ops.gemm(du, wT("fc"), M, E, 4 * E, out32=da2)
-        wg(du.hi, c["a2"].hi, 4 * E, E, prefix + "mlp.c_fc.weight", prefix + "mlp.c_fc.bias")
+        wg(du.hi, c["a2"].hi, 4 * E, E, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias)
         dx1, g16, dgb2 = ops.layernorm_bwd(da2, c["x1"], pk.ln2_w, add=dx2, want32=True, want16=True, alpha=inv,
-                                           dgb=self._ln_dest(prefix + "ln_2.weight", prefix + "ln_2.bias", E))
-        grads[prefix + "ln_2.weight"], grads[prefix + "ln_2.bias"] = dgb2[0], dgb2[1]
+                                           dgb=sink.ln_dest(blk.ln_2.weight, blk.ln_2.bias))
+        sink.put((blk.ln_2.weight, blk.ln_2.bias), dgb2)
         # forced-fp16 out-projection (clip/myAtt.py:321): gradient rounded to fp16 on both sides
         do16 = torch.empty(M, E, device=dev, dtype=F16)
         ops.gemm(g16, Split(wT("out").hi, None), M, E, E, out16=do16)
-        wg(g16, c["o16"], E, E, prefix + "attn.out_proj.weight", prefix + "attn.out_proj.bias")
+        wg(g16, c["o16"], E, E, blk.attn.out_proj.weight, blk.attn.out_proj.bias)
         # attention + in-projection
         dqkv = ops.attention_bwd(c["qkv"], do16, c["o32"], c["lse"], B, Lq, H, DH, with_lo=ex)
         da = torch.empty(M, E, device=dev, dtype=F32)
         ops.gemm(dqkv, wT("in"), M, E, 3 * E, out32=da)
-        wg(dqkv.hi, c["a"].hi, 3 * E, E, prefix + "attn.in_proj_weight", prefix + "attn.in_proj_bias")
+        wg(dqkv.hi, c["a"].hi, 3 * E, E, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
         dx, _, dgb1 = ops.layernorm_bwd(da, c["x"], pk.ln1_w, add=dx1, want32=True, alpha=inv,
-                                        dgb=self._ln_dest(prefix + "ln_1.weight", prefix + "ln_1.bias", E))
-        grads[prefix + "ln_1.weight"], grads[prefix + "ln_1.bias"] = dgb1[0], dgb1[1]
+                                        dgb=sink.ln_dest(blk.ln_1.weight, blk.ln_1.bias))
+        sink.put((blk.ln_1.weight, blk.ln_1.bias), dgb1)
         return dx
 
 
@@ -453,20 +383,10 @@ class HeadFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dseg, dap):
         eng = ctx.engine
-        g = eng.backward(ctx.c, dseg.contiguous() if dseg is not None else None,
-                         dap.contiguous() if dap is not None else None)
+        g, _ = eng.backward(ctx.c, dseg.contiguous() if dseg is not None else None,
+                            dap.contiguous() if dap is not None else None)
         ctx.c = None
-        direct = eng.direct_grads
-        out = []
-        for n, p in zip(eng.param_names(), eng.params()):
-            d = direct.get(n) if direct else None
-            if d is None:
-                out.append(g[n].reshape(p.shape))
-                continue
-            if g[n].data_ptr() != d.data_ptr():      # produced outside _wgrad (LayerNorm, zero heads)
-                d.copy_(g[n].reshape(d.shape))
-            out.append(None)                          # already in the caller's buffer
-        return (None,) * 7 + tuple(out)
+        return (None,) * 7 + handback(eng.params(), g)
 
 
 class DecoderFunction(torch.autograd.Function):
@@ -481,17 +401,7 @@ class DecoderFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dseg, dap):
         eng = ctx.engine
-        g = eng.backward(ctx.c, dseg.contiguous() if dseg is not None else None,
-                         dap.contiguous() if dap is not None else None)
+        g, dF = eng.backward(ctx.c, dseg.contiguous() if dseg is not None else None,
+                             dap.contiguous() if dap is not None else None)
         ctx.c = None
-        direct = eng.direct_grads
-        out = []
-        for n, p in zip(eng.dec_param_names(), eng.dec_params()):
-            d = direct.get(n) if direct else None
-            if d is None:
-                out.append(g[n].reshape(p.shape))
-                continue
-            if g[n].data_ptr() != d.data_ptr():
-                d.copy_(g[n].reshape(d.shape))
-            out.append(None)
-        return (None, g["__dF__"], None, None, None) + tuple(out)
+        return (None, dF, None, None, None) + handback(eng.dec_params(), g)

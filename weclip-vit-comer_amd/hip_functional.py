@@ -11,6 +11,7 @@ import torch
 
 from . import _lib as L
 from . import config, ops
+from .grad_sink import slices
 from .ops import F16, F32, Split
 
 GRAD_SCALE = 4096.0
@@ -101,10 +102,7 @@ class _Conv3x3Fn(torch.autograd.Function):
             L.lib().wc_col2im3x3(L.ptr(dcols, F32), L.ptr(dx), N, H, W, C, stride, Kp, L.stream())
         if ctx.needs_input_grad[1]:
             tiles = ((O + 127) // 128) * ((Kp + 1 + 127) // 128)
-            ns = 1
-            while ns * 2 * tiles <= 512 and M // (ns * 2) >= 256:
-                ns *= 2
-            part, ns = ops.wgrad_partials(dS.hi, cols_hi, M, O, Kp, lda=Op, slices=ns, bias=False)
+            part, ns = ops.wgrad_partials(dS.hi, cols_hi, M, O, Kp, lda=Op, slices=slices(M, tiles, 512), bias=False)
             dwm = torch.empty(O, Kp, device=dev, dtype=F32)
             L.lib().wc_sum_slices(L.ptr(part, F32), L.ptr(dwm, F32), ns, O * Kp, 1.0 / GRAD_SCALE, L.stream())
             dw = dwm[:, :9 * C].reshape(O, 3, 3, C).permute(0, 3, 1, 2).contiguous().view(wshape)

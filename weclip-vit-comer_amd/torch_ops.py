@@ -203,6 +203,7 @@ def linear_bwd(dy: Tensor, x: Tensor, weight: Tensor, y: Tensor, act: int, need_
     gemm_km_kernel, bias = extra output column); gradients travel multiplied by 2^12 so they sit in fp16's normal range."""
     from . import _lib as L
     from . import config, ops
+    from .grad_sink import slices
     M, K = x.shape
     N = weight.shape[0]
     dev = dy.device
@@ -225,11 +226,7 @@ def linear_bwd(dy: Tensor, x: Tensor, weight: Tensor, y: Tensor, act: int, need_
         ops.gemm(dS, wT, M, K, Kp, out32=dx, scale=1.0 / GRAD_SCALE, scale_cols=K)
     if need_dw:
         xhi = ops.split_f16(x.detach().float().contiguous()).hi
-        tiles = ops.wgrad_tiles(N, K)
-        ns = 1
-        while ns * 2 * tiles <= 512 and M // (ns * 2) >= 256:
-            ns *= 2
-        part, ns = ops.wgrad_partials(dS.hi, xhi, M, N, K, lda=Np, slices=ns, bias=True)
+        part, ns = ops.wgrad_partials(dS.hi, xhi, M, N, K, lda=Np, slices=slices(M, ops.wgrad_tiles(N, K), 512), bias=True)
         dw = torch.empty(N, K, device=dev, dtype=F32)
         db = torch.empty(N, device=dev, dtype=F32)
         L.lib().wc_sum_slices_wb(L.ptr(part, F32), L.ptr(dw, F32), L.ptr(db, F32), ns, N, K, 1.0 / GRAD_SCALE, L.stream())

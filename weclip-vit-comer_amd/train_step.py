@@ -81,21 +81,16 @@ class TrainStep:
         self.pad_plans = bool(pad_plans)
         self._graphs = {}
         self._pool = None
-        eng = getattr(model, "head_engine", None)
-        if self.bucket is not None and eng is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
-            # the HIP head writes every adapter/decoder gradient straight into the bucket views
-            # (the bucket is zeroed each step and each gradient is written exactly once per backward)
-            eng.direct_grads = {n: p.grad for n, p in zip(eng.param_names(), eng.params()) if p.grad is not None}
-        comer = getattr(model, "comer", None)
-        if comer is not None:
-            # the insert engine writes its parameter gradients into the views of THIS bucket (address range recorded: a .grad
-            # that lies elsewhere is accumulated through autograd as usual); a TrainStep without a bucket clears the opt-in
-            comer.direct_grads = False
-            if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
-                lo = self.bucket.flat.data_ptr()
-                comer.direct_grads = (lo, lo + 4 * self.bucket.flat.numel())
-        if eng is not None and self.bucket is None:
-            eng.direct_grads = None
+        # the HIP head and the insert engine write their gradients straight into the views of THIS bucket (zeroed each step,
+        # each gradient written exactly once per backward; a .grad that lies elsewhere is accumulated through autograd as
+        # usual); a TrainStep without a bucket clears the opt-in
+        rng = None
+        if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
+            lo = self.bucket.flat.data_ptr()
+            rng = (lo, lo + 4 * self.bucket.flat.numel())
+        for owner in (getattr(model, "head_engine", None), getattr(model, "comer", None)):
+            if owner is not None:
+                owner.direct_grads = rng
 
     def mask(self, h, w, device):
         key = (h, w, str(device))
