@@ -8,12 +8,17 @@ adapters/decoder, (DP: one RCCL all-reduce of the 5.99 M gradients), AdamW step.
 BASELINE.json metric: images/sec (train fwd+bwd) ViT-B/16 512x512; per-GPU batch 16 (configs[2]).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full      (everything the benchmark measures and checks)
     python bench.py --gpus 4 ...          (starts 4 rank processes itself when WORLD_SIZE is unset)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.
   * `value`: the timed region replays the HIP graph of the step (train_step.TrainStep(graph=True)); every step gets
     another batch from the per-rank seeded loader.
+A plain run does only what `value` needs: set-up, `--warmup` steps, ONE timed region of `--steps` steps, the outputs of
+`--dump-outputs`, the JSON line.  Everything else needs `--full`:
+  * `repeat_ms_per_step` etc. (`--repeats` timed regions, `value` stays the first), `host_work_ms_per_step_idle_queue`, and
+    at N > 1 `dp_check` / `dp_diag`.
   * `roofline`: dominant kernel family timed with HIP events on the launch stream, recorded by the C library at its
     launch sites during `--roof-steps` EAGER steps of the same workload right after the timed region (a captured
     graph has no per-launch call sites to put the event pairs at).
@@ -43,6 +48,8 @@ def parse():
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--classes-per-image", type=int, default=2)
     ap.add_argument("--precision", default=None, choices=[None, "fast", "exact"])
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeats, host / DP diagnostics, roofline, extra legs, CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the seg-trans / exact / CoMer / encoder-only legs")
     ap.add_argument("--no-graph", action="store_true", help="time eager steps (every launch through Python)")
@@ -56,12 +63,13 @@ def parse():
                     help="head forward on the step's own stream instead of beside the CAM chain (profiling passes: a kernel trace "
                          "then times every kernel alone)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region of --steps steps is run this many times; `value` is the first, all are reported")
+                    help="--full: the timed region of --steps steps is run this many times; `value` is the first, all are "
+                         "reported")
     ap.add_argument("--cpu-images", type=int, default=1, help="images per point of the CPU-oracle thread sweep")
     ap.add_argument("--cpu-threads", default="1,8,32,all", help="thread counts of the CPU-oracle sweep")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the last timed step computed (losses, gradients, updated "
-                         "parameters) as DIR/<name>.npy (float32, <= 64 MB in all)")
+                    help="after the timed steps, write what the last step of the --repeats regions computed (losses, "
+                         "gradients, updated parameters) as DIR/<name>.npy (float32, <= 64 MB in all)")
     return ap.parse_args()
 
 
@@ -204,9 +212,10 @@ def dump_outputs(out_dir, step, out):
 
 
 def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None, warmup=None, graph=True, repeats=1,
-            dump_dir=None):
-    """Build a model + TrainStep, warm up, time `steps` steps.  -> (dict, step, loader)
-    dump_dir: rank 0 writes the outputs of the last timed step there (dump_outputs)."""
+            diagnostics=True, dump_dir=None):
+    """Build a model + TrainStep, warm up, time `repeats` regions of `steps` steps.  -> (dict, step, loader)
+    diagnostics: then also the repeat spread, the host work per step on an idle queue and at N > 1 the DP checks (--full).
+    dump_dir: rank 0 writes there the outputs of the last step of `--repeats` regions (dump_outputs)."""
     from weclip_vit_comer_amd.data import SyntheticVOCLoader
     from weclip_vit_comer_amd.train_step import TrainStep
     steps = args.steps if steps is None else steps
@@ -231,8 +240,26 @@ def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None,
     rep_ms = [dt / steps * 1e3]
     for _ in range(max(0, repeats - 1)):
         rep_ms.append(timed_steps(step, loader, steps, world, dev, last)[0] / steps * 1e3)
-    if dump_dir is not None and rank == 0:
-        dump_outputs(dump_dir, step, last[0])
+    if dump_dir is not None:
+        # what is written is the state after `--repeats` regions however many of them were timed: a plain run (one timed
+        # region) runs the steps of the others here, untimed, on every rank
+        for _ in range((max(1, args.repeats) - max(1, repeats)) * steps):
+            img, labels = loader.next()
+            last[:] = [step(img, labels=labels)]
+        if rank == 0:
+            dump_outputs(dump_dir, step, last[0])
+    res = {"value": round(world * args.batch * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 3),
+           "host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 3),
+           "host_cpu_ms_per_step": round(t_cpu / steps * 1e3, 3), "steps": steps,
+           "launch_mode": "hipGraph replay" if use_graph else "eager"}
+    if diagnostics:
+        res.update(leg_diagnostics(step, loader, world, dev, steps, rep_ms, per_rank))
+    return res, step, loader
+
+
+def leg_diagnostics(step, loader, world, dev, steps, rep_ms, per_rank):
+    """--full: spread of the repeated regions, host work per step on an idle queue, at N > 1 the gradient exchange alone
+    and whether the ranks hold the same parameters."""
     # host work per step, free of back-pressure: each step enqueued onto an IDLE queue (in the timed region above the host
     # runs ahead of the GPU-bound device and then blocks in the loader's pinned-buffer event, which is waiting, not work)
     import torch
@@ -265,21 +292,16 @@ def run_leg(args, dev, rank, world, *, comer=False, seg_trans=False, steps=None,
                    "allreduce_bytes": int(step.bucket.flat.numel() * 4),
                    "rank_ms_per_step_min": round(min(per_rank) / steps * 1e3, 3),
                    "rank_ms_per_step_max": round(max(per_rank) / steps * 1e3, 3)}
-        ps = [p.detach().double() for p in model.get_param_groups()[3]]
+        ps = [p.detach().double() for p in step.model.get_param_groups()[3]]
         ck = torch.stack([sum(p.sum() for p in ps), sum((p * p).sum() for p in ps)]).to(dev)
         allck = [torch.zeros_like(ck) for _ in range(world)]
         dist.all_gather(allck, ck)
         dp_check = {"params_identical_across_ranks": bool(all(torch.equal(allck[0], c) for c in allck)),
                     "param_checksum": [float(v) for v in allck[0].tolist()]}
     srt = sorted(rep_ms)
-    res = {"value": round(world * args.batch * steps / dt, 3), "ms_per_step": round(dt / steps * 1e3, 3), "dp_check": dp_check,
-           "dp_diag": dp_diag, "repeat_ms_per_step": [round(r, 3) for r in rep_ms],
-           "repeat_median_ms": round(srt[len(srt) // 2], 3), "repeat_min_ms": round(srt[0], 3), "repeat_max_ms": round(srt[-1], 3),
-           "host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 3),
-           "host_cpu_ms_per_step": round(t_cpu / steps * 1e3, 3),
-           "host_work_ms_per_step_idle_queue": round(t_idle / 5 * 1e3, 3), "steps": steps,
-           "launch_mode": "hipGraph replay" if use_graph else "eager"}
-    return res, step, loader
+    return {"dp_check": dp_check, "dp_diag": dp_diag, "repeat_ms_per_step": [round(r, 3) for r in rep_ms],
+            "repeat_median_ms": round(srt[len(srt) // 2], 3), "repeat_min_ms": round(srt[0], 3), "repeat_max_ms": round(srt[-1], 3),
+            "host_work_ms_per_step_idle_queue": round(t_idle / 5 * 1e3, 3)}
 
 
 def roofline_leg(args, step, loader, dev, use_traffic=True, traffic_files="r*_traffic.json"):
@@ -449,7 +471,7 @@ def main():
         config.precision = args.precision
 
     res, step, loader = run_leg(args, dev, rank, world, comer=args.comer, seg_trans=args.seg_trans, graph=not args.no_graph,
-                                repeats=args.repeats, dump_dir=args.dump_outputs)
+                                repeats=args.repeats if args.full else 1, diagnostics=args.full, dump_dir=args.dump_outputs)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -457,7 +479,7 @@ def main():
 
     B, S, K = args.batch, args.size, args.classes_per_image
     roofs, roof_meta = ([], {})
-    if args.timer_stride > 0 and args.roof_steps > 0 and world == 1:
+    if args.full and args.timer_stride > 0 and args.roof_steps > 0 and world == 1:
         roofs, roof_meta = roofline_leg(args, step, loader, dev, traffic_files="r*_comer_traffic.json" if args.comer else "r*_traffic.json")
     del step, loader
     torch.cuda.empty_cache()
@@ -471,12 +493,7 @@ def main():
         "ms_per_step": res["ms_per_step"],
         "host_enqueue_ms_per_step": res["host_enqueue_ms_per_step"],
         "host_cpu_ms_per_step": res["host_cpu_ms_per_step"],
-        "host_work_ms_per_step_idle_queue": res["host_work_ms_per_step_idle_queue"],
         "launch_mode": res["launch_mode"],
-        "dp_check": res["dp_check"],
-        "dp_diag": res["dp_diag"],
-        "repeat_ms_per_step": res["repeat_ms_per_step"],
-        "repeat_median_ms": res["repeat_median_ms"], "repeat_min_ms": res["repeat_min_ms"], "repeat_max_ms": res["repeat_max_ms"],
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -491,11 +508,12 @@ def main():
                                + (" with" if args.comer else " without") + " the ViT-CoMer inserts, for which the reference has no code"
                                + ("; seg-trans affinity branch" if args.seg_trans else "") + ")",
                    "global_batch": world * B, "parallelism": f"dp{world}"},
-        "roofline": roofs[0] if roofs else None,
-        "roofline_other": roofs[1:],
     }
-    out.update(roof_meta)
-    if world == 1 and not args.no_extras:
+    if args.full:
+        out.update({k: res[k] for k in ("host_work_ms_per_step_idle_queue", "dp_check", "dp_diag", "repeat_ms_per_step",
+                                        "repeat_median_ms", "repeat_min_ms", "repeat_max_ms")})
+        out.update({"roofline": roofs[0] if roofs else None, "roofline_other": roofs[1:]}, **roof_meta)
+    if args.full and world == 1 and not args.no_extras:
         few = max(4, min(10, args.steps))
         if not args.seg_trans:
             r, _, _ = run_leg(args, dev, rank, world, seg_trans=True, steps=few, warmup=2)
@@ -538,7 +556,7 @@ def main():
             torch.cuda.empty_cache()
         out["encoder_only_b32"] = encoder_leg(args, dev)
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
     print(json.dumps(out))
     if world > 1:

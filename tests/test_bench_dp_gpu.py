@@ -19,7 +19,7 @@ def test_bench_two_ranks_share_one_gpu_and_stay_in_step():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
-           "--size", "128", "--no-extras", "--no-cpu-baseline", "--roof-steps", "0", "--timer-stride", "0"]
+           "--size", "128", "--full", "--no-extras", "--no-cpu-baseline", "--roof-steps", "0", "--timer-stride", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
