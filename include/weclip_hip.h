@@ -554,6 +554,29 @@ int wc_dcrf_inference(const void* img, int img_is_u8, const float* unary, float*
 int wc_dcrf_message(const void* img, int img_is_u8, const float* Q, float* msg_pos, float* msg_bil, float* S, void* ws,
                     int C, int H, int W, float pos_xy_std, float bi_xy_std, float bi_rgb_std, void* stream);
 
+/* ---- CLIP text tower (csrc/text.hip; DESIGN.md "Text tower") -------------------------------------------------------- */
+/* wc_text_embed:      clip/model.py:393-395 (token_embedding(text) + positional_embedding) and :403 (`text.argmax(-1)`).
+ *                     tokens (N, Lctx) int32; tok_emb (V, W) f32; pos (>= L, W) f32.  eot (N) int32 = index of the first
+ *                     maximum id of each row (over all Lctx ids); x (N*L, W) f32 = rows 0..L-1 of every prompt, or NULL
+ *                     (then L must be 0: only eot and the flag).  *bad (int32) = 1 if any id lies outside [0, V), else 0;
+ *                     such ids read embedding row 0 (never out of bounds) and the caller raises.
+ * wc_attn_fwd_causal: clip/myAtt.py:21-64 with the causal `attn_mask` of clip/model.py:333,375-381 (-inf above the
+ *                     diagonal, myAtt.py:57-58): qkv as for wc_attn_fwd (q pre-scaled by log2(e)/sqrt(DH)); out (N*L, E)
+ *                     fp16; optional out32 (N*L, E) f32, lse (N, H, L) f32 (base 2), mean (N, L, L) f32 = head-mean
+ *                     probabilities, exactly 0 above the diagonal.  1 <= L <= 128, DH == 64, H >= 1; qkv, out, out32
+ *                     16-byte aligned.
+ * wc_text_pool:       clip/model.py:399-403: feat (N, Ed) f32 = LayerNorm(x[n*L + eot[n]]; ln_w, ln_b, eps) @ proj (W, Ed)
+ *                     in fp32; x (N*L, W) f32 (eot clamped to [0, L)).  W <= 8192.
+ * wc_text_zeroshot:   WeCLIP_model/model_attn_aff_voc.py:34-46 (`zeroshot_classifier` after encode_text): feat (C*T, Ed)
+ *                     f32, T rows per class -> out (C, Ed) f32 = normalise(mean_t(normalise(feat row))).  Ed <= 8192. */
+int wc_text_embed(const int* tokens, int N, int Lctx, const float* tok_emb, int V, const float* pos, int W, int L,
+                  float* x, int* eot, int* bad, void* stream);
+int wc_attn_fwd_causal(const void* qkv, void* out, float* out32, float* lse, float* mean, int N, int L, int H, int DH,
+                       void* stream);
+int wc_text_pool(const float* x, const int* eot, int N, int L, int W, const float* ln_w, const float* ln_b, float eps,
+                 const float* proj, int Ed, float* feat, void* stream);
+int wc_text_zeroshot(const float* feat, int C, int T, int Ed, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ iteration 40000), an encoder that is not frozen by name, and `mode='val'` return
 `(seg, None, attn_pred)` right after the decoder."""
 import os
 
-from .model_attn_aff_voc import WeCLIP as _VocWeCLIP, reshape_transform  # noqa: F401
+from .model_attn_aff_voc import WeCLIP as _VocWeCLIP, reshape_transform, zeroshot_classifier  # noqa: F401
 
 
 class WeCLIP(_VocWeCLIP):
@@ -12,6 +12,7 @@ class WeCLIP(_VocWeCLIP):
     seg_trans_last = 10
     seg_trans_after = 40000
     val_runs_cam = False
+    fg_names, bg_names = "new_class_names_coco", "BACKGROUND_CATEGORY_COCO"      # reference :69-72
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)

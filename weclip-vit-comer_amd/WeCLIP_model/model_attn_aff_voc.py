@@ -21,6 +21,33 @@ from .PAR import PAR, refine_labels
 from .segformer_head import SegFormerHead
 
 
+TEMPLATES = ["a clean origami {}."]          # reference :81-82
+
+
+def zeroshot_classifier(classnames, templates, model):
+    """Reference :34-46 (one encode_text per class name) as ONE batched encode_text over all class names x templates:
+    (C, Ed) f32 rows, each the renormalised mean of its templates' unit features (csrc/text.hip wc_text_zeroshot)."""
+    from ..clip import text_engine
+    return text_engine.zeroshot(model, list(classnames), list(templates))
+
+
+def default_text_features(encoder, fg_name, bg_name):
+    """(bg, fg) rows as the reference constructor computes them (:81-82) from `clip.clip_text` -- the user's reference
+    checkout, on the clip package path after install_dropin(reference_root=...) -- or None when the name lists, the BPE
+    merges file or the text tower are not available."""
+    import importlib
+    from ..clip.tokenizer import BPENotFound, bpe_path
+    if encoder.transformer.layers == 0:
+        return None
+    try:
+        names = importlib.import_module(__name__.rsplit(".", 2)[0] + ".clip.clip_text")
+        bg, fg = getattr(names, bg_name), getattr(names, fg_name)
+        bpe_path()
+    except (ImportError, AttributeError, BPENotFound):
+        return None
+    return zeroshot_classifier(bg, TEMPLATES, encoder), zeroshot_classifier(fg, TEMPLATES, encoder)
+
+
 def reshape_transform(tensor, height=28, width=28):
     """(L, N, D) tokens -> (N, D, h, w) patch grid (reference :23-30); kept for API parity."""
     t = tensor.permute(1, 0, 2)[:, 1:, :]
@@ -32,13 +59,14 @@ class WeCLIP(nn.Module):
     seg_trans_last = 6       # maps used in the seg-trans branch (clip_tool.py:155)
     seg_trans_after = 15000  # iteration after which the seg-trans branch is used (:146)
     val_runs_cam = True      # the VOC model runs the CAM/PAR path in 'val' too (:146-155)
+    fg_names, bg_names = "new_class_names", "BACKGROUND_CATEGORY"      # clip.clip_text lists of the text rows (:81-82)
 
     def __init__(self, num_classes=None, clip_model=None, embedding_dim=256, in_channels=512,
                  dataset_root_path=None, device="cuda", text_features=None, comer=False):
-        """`text_features=(bg (n_bg, Ed), fg (n_fg, Ed))`: the zero-shot text rows.  The reference
-        computes them at construction with the CLIP text tower + tokenizer (:34-46,81-82); that
-        init-time step is outside this package, so they are passed in (or assigned later to
-        `bg_text_features` / `fg_text_features`)."""
+        """`text_features=(bg (n_bg, Ed), fg (n_fg, Ed))`: the zero-shot text rows.  Without them the rows are
+        computed here like the reference does (:34-46,81-82: clip.tokenize + CLIP.encode_text on the GPU) when the
+        reference checkout is known (install_dropin(reference_root=...) or clip.set_bpe_path plus a `clip.clip_text`
+        module); otherwise they stay None until assigned to `bg_text_features` / `fg_text_features`."""
         super().__init__()
         self.num_classes, self.embedding_dim, self.in_channels = num_classes, embedding_dim, in_channels
         self.encoder, _ = clip_load(clip_model, device=device)
@@ -47,6 +75,8 @@ class WeCLIP(nn.Module):
         self.decoder_fts_fuse = SegFormerHead(in_channels=in_channels, embedding_dim=embedding_dim,
                                               num_classes=num_classes, index=11)
         self.decoder = DecoderTransformer(width=embedding_dim, layers=3, heads=8, output_dim=num_classes)
+        if text_features is None:
+            text_features = default_text_features(self.encoder, self.fg_names, self.bg_names)
         self.bg_text_features, self.fg_text_features = (None, None) if text_features is None else text_features
         self.target_layers = [self.encoder.visual.transformer.resblocks[-1].ln_1]
         self.grad_cam = GradCAM(model=self.encoder, target_layers=self.target_layers,
@@ -215,7 +245,9 @@ class WeCLIP(nn.Module):
 
     def cam_labels(self, img, last_rows, maps, attn_pred, img_names, labels, mode, seg_trans, h, w, plan=None):
         if self.bg_text_features is None or self.fg_text_features is None:
-            raise RuntimeError("WeCLIP needs text_features=(bg, fg) (see __init__)")
+            raise RuntimeError("WeCLIP needs text_features=(bg, fg) (see __init__): pass them, or call "
+                               "install_dropin(reference_root=<reference checkout>) before constructing WeCLIP so that "
+                               "they are computed from clip.clip_text and the BPE vocabulary")
         B, _, H, W = img.shape
         if isinstance(img_names, str):
             img_names = [img_names]

@@ -82,7 +82,9 @@ def install_dropin(reference_root=None):
     modules on the hot path or imported next to it by the training script; dcrf: the GPU dense CRF behind the
     eval scripts' `from utils.dcrf import DenseCRF`).  `reference_root`, if given, is a checkout of the reference
     whose `utils/` directory is appended to that package's search path, so the helper modules this package does
-    not provide (imutils, ...) still import from the user's tree."""
+    not provide (imutils, ...) still import from the user's tree; its `clip/` directory is appended to the `clip`
+    package's path the same way (`from clip.clip_text import new_class_names, BACKGROUND_CATEGORY`, and the BPE merges
+    file `clip.tokenize` reads).  The package's own modules keep precedence."""
     global _finder
     import importlib
     import os
@@ -101,7 +103,8 @@ def install_dropin(reference_root=None):
             if k.startswith(prefix) and v is not None:
                 sys.modules[name + "." + k[len(prefix):]] = v
     if reference_root is not None:
-        extra = os.path.join(reference_root, "utils")
-        up = importlib.import_module(f"{__name__}.utils").__path__
-        if os.path.isdir(extra) and extra not in list(up):
-            up.append(extra)
+        for sub in ("utils", "clip"):
+            extra = os.path.join(reference_root, sub)
+            up = importlib.import_module(f"{__name__}.{sub}").__path__
+            if os.path.isdir(extra) and extra not in list(up):
+                up.append(extra)

@@ -6,8 +6,9 @@ from collections import OrderedDict
 import torch
 
 from .model import build_model
+from .tokenizer import set_bpe_path, tokenize
 
-__all__ = ["load", "build_model"]
+__all__ = ["load", "build_model", "tokenize", "set_bpe_path"]
 
 
 def load(name, device="cuda", jit=False, download_root=None):

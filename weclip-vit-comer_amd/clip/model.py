@@ -6,8 +6,8 @@ Differences from a plain CLIP that the reference introduced and this keeps:
   * `encode_image(..., require_all_fts=True)` runs blocks 1..layers-1 and returns the list of all
     token tensors (L,B,D) and all head-averaged attention maps (B,L,L);
   * `forward_last_layer` = last block + ln_post + patch-mean + proj + cosine softmax.
-The text tower is not on the hot path: its parameters are kept for
-checkpoint compatibility, `encode_text` is not provided.
+The text tower runs causal blocks (`build_attention_mask`, clip/model.py:333,375-381) and `encode_text` computes the
+EOT-row projection on the GPU over the first max(eot) + 1 positions only (clip/text_engine.py).
 """
 from collections import OrderedDict
 
@@ -63,23 +63,36 @@ class ResidualAttentionBlock(nn.Module):
         return self._pack
 
     def forward(self, x):
-        """x (L, N, E) -> (x', head-mean attention (N, L, L))."""
+        """x (L, N, E) -> (x', head-mean attention (N, L, L); the causal map when the block has the text mask)."""
         rows, N, Lq = VE.to_rows(x)
-        y, mean = VE.run_block(self.pack(refresh=self.training or self.fp32_mlp), rows, N, Lq)
+        y, mean = VE.run_block(self.pack(refresh=self.training or self.fp32_mlp), rows, N, Lq,
+                               causal=self.attn_mask is not None)
         return VE.from_rows(y, N, Lq).to(x.dtype), mean
+
+
+def is_causal_mask(mask):
+    """True for the reference's text mask (-inf above the diagonal, 0 elsewhere), the only mask on the HIP path."""
+    m = torch.as_tensor(mask).detach().float().cpu()
+    if m.dim() != 2 or m.shape[0] != m.shape[1]:
+        return False
+    above = torch.ones_like(m, dtype=torch.bool).triu(1)
+    return bool(torch.isneginf(m[above]).all()) and bool((m[~above] == 0).all())
 
 
 class Transformer(nn.Module):
     def __init__(self, width, layers, heads, attn_mask=None):
         super().__init__()
+        if attn_mask is not None and not is_causal_mask(attn_mask):
+            raise NotImplementedError("only the causal text mask (CLIP.build_attention_mask) is supported")
         self.width, self.layers = width, layers
+        self.causal = attn_mask is not None      # a plain attribute, like the reference's mask: no state-dict key
         self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, attn_mask)
                                          for _ in range(layers)])
 
     def run_rows(self, rows, B, Lq, n_layers, want_maps=True):
         xs, maps = [], []
         for i in range(n_layers):
-            rows, m = VE.run_block(self.resblocks[i].pack(), rows, B, Lq, want_mean=want_maps)
+            rows, m = VE.run_block(self.resblocks[i].pack(), rows, B, Lq, want_mean=want_maps, causal=self.causal)
             xs.append(rows)
             maps.append(m)
         return xs, maps
@@ -166,14 +179,19 @@ class CLIP(nn.Module):
         self.context_length = context_length
         self.visual = VisionTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
                                         vision_width // 64, embed_dim)
-        # text tower: parameters only (checkpoint compatibility); never executed here
-        self.transformer = Transformer(transformer_width, transformer_layers, transformer_heads)
+        # text tower: causal blocks (reference attn_mask=self.build_attention_mask(), clip/model.py:333)
+        self.transformer = Transformer(transformer_width, transformer_layers, transformer_heads,
+                                       attn_mask=self.build_attention_mask())
         self.vocab_size = vocab_size
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)
         self.positional_embedding = nn.Parameter(torch.empty(context_length, transformer_width))
         self.ln_final = LayerNorm(transformer_width)
         self.text_projection = nn.Parameter(torch.empty(transformer_width, embed_dim))
         self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+
+    def build_attention_mask(self):
+        """(context_length, context_length) additive mask, -inf above the diagonal (clip/model.py:375-381)."""
+        return torch.full((self.context_length, self.context_length), float("-inf")).triu_(1)
 
     @property
     def dtype(self):
@@ -182,10 +200,12 @@ class CLIP(nn.Module):
     def encode_image(self, image, H, W, require_all_fts=False):
         return self.visual(image.type(self.dtype), H, W, require_all_fts=require_all_fts)
 
-    def encode_text(self, text):
-        raise NotImplementedError(
-            "the text tower is init-time only and not on the HIP path: precompute text features "
-            "(e.g. with the reference CLIP) and pass them to WeCLIP(text_features=...)")
+    def encode_text(self, text, *, full_context=False):
+        """text (N, context_length) int32 / int64 ids, on the CPU or the GPU -> (N, embed_dim) f32 on the model's device
+        (clip/model.py:392-405).  Runs the first max(eot) + 1 positions only (exact under the causal mask);
+        `full_context=True` runs all of them."""
+        from .text_engine import encode_text
+        return encode_text(self, text, full_context=full_context)
 
     def forward_last_layer(self, image_features, text_features):
         """(L,N,D) tokens of block layers-1, (T,E) text rows -> (softmax probs (N,T), map (N,L,L)).

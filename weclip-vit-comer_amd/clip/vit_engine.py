@@ -58,8 +58,9 @@ class X16Stack(list):
         return Split(self.big[i], self.big_lo[i] if self.big_lo is not None else None)
 
 
-def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None):
+def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, causal=False):
     """x (B*L, E) fp32 -> (x_out fp32, head-mean map (B,L,L) or None).
+    `causal`: the text tower's masked attention (ops.attention_causal; L <= 128, DH = 64); the map is then the causal one.
     `keep`, if a dict, receives intermediates needed by the analytic backward.
     `tag`: bench.py's roofline group of the attention half (in-projection, attention, head-mean, out-projection)."""
     M, E, H, DH = B * L, pk.E, pk.H, pk.DH
@@ -71,10 +72,11 @@ def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None):
     qkv = torch.empty(M, 3 * E, device=dev, dtype=F16)
     ops.gemm(a, pk.in_w, M, 3 * E, E, bias=pk.in_b, out16=qkv, scale=ops.q_scale(DH), scale_cols=E)
     o32 = None
+    attn = ops.attention_causal if causal else ops.attention
     if keep is not None:
-        o16, lse, mean, o32 = ops.attention(qkv, B, L, H, DH, want_mean=want_mean, want_o32=True)
+        o16, lse, mean, o32 = attn(qkv, B, L, H, DH, want_mean=want_mean, want_o32=True)
     else:
-        o16, lse, mean = ops.attention(qkv, B, L, H, DH, want_mean=want_mean)
+        o16, lse, mean = attn(qkv, B, L, H, DH, want_mean=want_mean)
     x1 = torch.empty(M, E, device=dev, dtype=F32)
     ops.gemm(o16, pk.out_w, M, E, E, bias=pk.out_b, resid=x, out32=x1, round16=True)
     if tag:

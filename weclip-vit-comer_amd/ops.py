@@ -167,6 +167,53 @@ def attention(qkv16, B, Lq, H, DH, want_mean=True, want_o32=False):
     return o16, lse, mean
 
 
+def attention_causal(qkv16, B, Lq, H, DH, want_mean=True, want_o32=False):
+    """Causal self-attention of short sequences (csrc/text.hip, L <= 128, DH = 64): same contract as `attention`;
+    the map is the head mean of the masked softmax, exactly 0 above the diagonal."""
+    E = H * DH
+    dev = qkv16.device
+    o16 = torch.empty(B * Lq, E, device=dev, dtype=F16)
+    lse = torch.empty(B, H, Lq, device=dev, dtype=F32)
+    o32 = torch.empty(B * Lq, E, device=dev, dtype=F32) if want_o32 else None
+    mean = torch.empty(B, Lq, Lq, device=dev, dtype=F32) if want_mean else None
+    L.lib().wc_attn_fwd_causal(L.ptr(qkv16, F16, "qkv"), L.ptr(o16), L.ptr(o32), L.ptr(lse), L.ptr(mean), B, Lq, H, DH,
+                               L.stream())
+    if want_o32:
+        return o16, lse, mean, o32
+    return o16, lse, mean
+
+
+def text_embed(tokens, tok_emb, pos, L_used):
+    """tokens (N, Lctx) int32 CUDA -> (x (N*L_used, W) f32 or None when L_used == 0, eot (N) int32, bad (1) int32)."""
+    N, Lctx = tokens.shape
+    V, W = tok_emb.shape
+    dev = tokens.device
+    x = torch.empty(N * L_used, W, device=dev, dtype=F32) if L_used else None
+    flags = torch.empty(N + 1, device=dev, dtype=torch.int32)         # eot[0:N] | bad
+    L.lib().wc_text_embed(L.ptr(tokens, torch.int32, "tokens"), N, Lctx, L.ptr(tok_emb, F32, "token_embedding"), V,
+                          L.ptr(pos, F32, "positional_embedding"), W, L_used, L.ptr(x), L.ptr(flags[:N]), L.ptr(flags[N:]),
+                          L.stream())
+    return x, flags[:N], flags[N:]
+
+
+def text_pool(x, eot, N, Lq, ln_w, ln_b, proj, eps=1e-5):
+    """features (N, Ed) f32 = ln_final(x[n*Lq + eot[n]]) @ proj."""
+    W, Ed = proj.shape
+    feat = torch.empty(N, Ed, device=x.device, dtype=F32)
+    L.lib().wc_text_pool(L.ptr(x, F32, "x"), L.ptr(eot, torch.int32, "eot"), N, Lq, W, L.ptr(ln_w, F32, "ln_final.weight"),
+                         L.ptr(ln_b, F32, "ln_final.bias"), float(eps), L.ptr(proj, F32, "text_projection"), Ed, L.ptr(feat),
+                         L.stream())
+    return feat
+
+
+def text_zeroshot(feat, C, T):
+    """feat (C*T, Ed) f32 -> (C, Ed) f32: per class, normalise every row, average the T rows, renormalise."""
+    Ed = feat.shape[-1]
+    out = torch.empty(C, Ed, device=feat.device, dtype=F32)
+    L.lib().wc_text_zeroshot(L.ptr(feat, F32, "features"), C, T, Ed, L.ptr(out), L.stream())
+    return out
+
+
 def q_scale(DH):
     return LOG2E / math.sqrt(DH)
 

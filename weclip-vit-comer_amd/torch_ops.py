@@ -316,5 +316,23 @@ def _(image, probs, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
     return probs.new_empty(probs.shape, dtype=F32)
 
 
+@torch.library.custom_op(f"{_LIB}::encode_text", mutates_args=(), device_types="cuda")
+def encode_text(text: Tensor, token_embedding: Tensor, positional_embedding: Tensor, blocks: List[Tensor], heads: int,
+                ln_final_weight: Tensor, ln_final_bias: Tensor, text_projection: Tensor) -> Tensor:
+    """CLIP.encode_text (reference clip/model.py:392-405) from the text tower's tensors: text (N, Lctx) int32 / int64 ids,
+    blocks = 12 tensors per residual block in clip.text_engine.BLOCK_KEYS order -> (N, Ed) f32.  No autograd."""
+    from .clip import text_engine as TE
+    dev = token_embedding.device
+    f = lambda t: t.detach().float().contiguous()
+    with torch.no_grad():
+        return TE.run(TE._ids(text, dev), f(token_embedding), f(positional_embedding), TE.packs_from_tensors(list(blocks), heads),
+                      f(ln_final_weight), f(ln_final_bias), f(text_projection))
+
+
+@encode_text.register_fake
+def _(text, token_embedding, positional_embedding, blocks, heads, ln_final_weight, ln_final_bias, text_projection):
+    return text_projection.new_empty((text.shape[0], text_projection.shape[1]), dtype=F32)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
-       "seg_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf")
+       "seg_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text")
