@@ -106,6 +106,23 @@ int wc_seg_loss_bwd_fused(const float* seg, const int64_t* label, const float* w
 int wc_seg_loss_fwd_bwd(const float* seg, const int64_t* label, float* cnt, float* part, float* sums, float* tmp, float* grad,
                         int B, int nc, int h, int w, int H, int W, int ignore, void* stream);
 
+/* Cross-entropy with an ignore index fused with the bilinear up-sampling of the logits, training form (the supervised
+ * variant's loss: F.cross_entropy(F.interpolate(seg, (H,W), bilinear, align_corners=False), label, ignore_index=ignore)).
+ * seg (B,nc,h,w) f32, label (B,H,W) i64 at any H x W (up- or down-sampling), 1 <= nc <= 128, W <= 8192.
+ * Loss AND d loss / d seg for an upstream gradient of 1 in one pixel pass, a one-block reduce and the X pass of the
+ * separable bilinear backward; no host synchronisation, no atomics (bit-identical between calls).
+ * A label outside [0, nc) that is not `ignore` counts as ignored and is reported in sums[3].
+ * Workspaces:
+ *   part: 4 f32 per workgroup of the pixel pass = 4 * ceil(W/64) * ceil(h/4) * B * nchunk floats, 16-byte aligned,
+ *         nchunk = 1 for nc <= 32, else ceil(nc/32);
+ *   sums: 4 f32 = [loss (NaN when no pixel is valid, as F.cross_entropy), 1/N_valid (0 when N_valid == 0), N_valid,
+ *         N_bad (labels outside [0, nc) that are not ignore)] -- counts exact below 2^24;
+ *   tmp:  2 * B*nc*h*W f32;
+ *   grad: (B,nc,h,w) f32 output, (softmax - onehot) / N_valid pulled back through the up-sampling (all zero when N_valid == 0,
+ *         as torch's). */
+int wc_ce_loss_fwd_bwd(const float* seg, const int64_t* label, float* part, float* sums, float* tmp, float* grad, int B, int nc,
+                       int h, int w, int H, int W, int ignore, void* stream);
+
 /* Affinity loss fused with the affinity-label construction (reference utils/camutils.py:226-247 +
  * scripts/dist_clip_voc.py:116-133 radius mask + utils/losses.py:11-22): attn_pred (B,hw,hw) f32, cam_label (B,H,W)
  * int64 pseudo labels (nearest down-sampled to h x w inside), Chebyshev `radius`.

@@ -424,8 +424,12 @@ __global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __rest
 // values are read coalesced and parked in LDS (index x + x/16: the 32 output lanes then read their windows, 16 apart, from
 // different banks); each output lane sums its window in ascending x, the order of the per-thread form (which read global
 // memory at a 64-byte lane stride: 51 us for 22 MB).
+// SCALED (wc_ce_loss_fwd_bwd): every output is multiplied by the device scalar scale[0] (1 / N_valid, known only after the
+// pixel pass), so the per-pixel gradient is accumulated unscaled and no host synchronisation is needed.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void seg_bwd_x2_kernel(const float* __restrict__ tmpA, const float* __restrict__ tmpB,
-                                                          float* __restrict__ gsrc, long rows, int Hs, int Ws, int Wd, float sx) {
+                                                          float* __restrict__ gsrc, long rows, int Hs, int Ws, int Wd, float sx,
+                                                          const float* __restrict__ scale) {
     extern __shared__ float xrow[];                       // 4 waves x (Wd + Wd/16 + 1)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long row = (long)blockIdx.x * 4 + wave;         // (image * nc + class) * Hs + ys
@@ -438,6 +442,7 @@ __global__ __launch_bounds__(256) void seg_bwd_x2_kernel(const float* __restrict
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS writes of this wave are done before its lanes read them
     __builtin_amdgcn_wave_barrier();
     const float ix = 1.0f / sx;
+    const float sc = SCALED ? scale[0] : 1.f;
     for (int xs = lane; xs < Ws; xs += 64) {
         int x_lo = (int)floorf((xs - 1.5f) * ix) - 1, x_hi = (int)ceilf((xs + 1.5f) * ix) + 1;
         if (x_lo < 0) x_lo = 0;
@@ -450,7 +455,7 @@ __global__ __launch_bounds__(256) void seg_bwd_x2_kernel(const float* __restrict
             const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
             acc = fmaf(wx, v[x + (x >> 4)], acc);
         }
-        gsrc[row * Ws + xs] = acc;
+        gsrc[row * Ws + xs] = SCALED ? acc * sc : acc;
     }
 }
 
@@ -472,9 +477,199 @@ extern "C" int wc_seg_loss_fwd_bwd(const float* seg, const int64_t* label, float
     WC_LAUNCH_CHECK("seg_loss_reduce_kernel");
     const long rows = (long)B * nc * h;
     WC_CHECK_ARG(W <= 8192, "wc_seg_loss_fwd_bwd: W too large for the row buffer");
-    hipLaunchKernelGGL(seg_bwd_x2_kernel, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float), st,
-                       tmp, tmpB, grad, rows, h, w, W, (float)w / W);
+    hipLaunchKernelGGL(seg_bwd_x2_kernel<false>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
+                       st, tmp, tmpB, grad, rows, h, w, W, (float)w / W, nullptr);
     WC_LAUNCH_CHECK("seg_bwd_x2_kernel");
+    return WC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Plain cross-entropy with an ignore index, fused with the bilinear up-sampling of the logits (the supervised WeCLIP
+// variant's loss, WeCLIP_model/model_attn_aff_voc_seg.py in this package):
+//   loss = mean over pixels with label != ignore of  -log softmax(F.interpolate(seg, (H, W), bilinear, align_corners=False))[label]
+// = F.cross_entropy(F.interpolate(...), label, ignore_index=ignore).  Same pixel pass as seg_loss_fused_kernel (thread (x, ys)
+// walks the high-resolution rows whose upper source row is ys; gradient split over rows ys / ys + 1 into tmpA / tmpB), with
+// three differences: every valid pixel weighs 1 (the 1 / N_valid is applied by the X pass from a device scalar, so no count
+// pass runs first), H and W are free (down-sampling too: a thread with no rows writes zeros), and up to CE_MAX_C classes in
+// chunks of CH per workgroup (blockIdx.z = image * nchunk + chunk).  MULTI (nc > CH): the pixel's log-sum-exp runs over all
+// classes from memory, CE_LSE_G classes' loads at a time; the chunk's own logits stay in registers for the gradient.
+// A label outside [0, nc) that is not `ignore` is treated as ignored and counted (part[.. + 2]); it is compared, never used
+// as an index.  Block partials: (sum nll, n_valid, n_bad, 0) -- only chunk 0 counts.
+#define CE_MAX_C 128
+#define CE_LSE_G 4       // classes whose logits the MULTI log-sum-exp requests together (8: the register file overflows, loads serialise)
+template <int CH, bool MULTI>
+__global__ __launch_bounds__(256) void ce_loss_fused_kernel(const float* __restrict__ seg, const long* __restrict__ label,
+                                                             float* __restrict__ part, float* __restrict__ tmpA,
+                                                             float* __restrict__ tmpB, int nc, int nchunk, int h, int w, int H,
+                                                             int W, float sy, float sx, int ignore) {
+    __shared__ float red[16];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.z / nchunk, ck = blockIdx.z - b * nchunk, c0 = ck * CH;
+    float l_sum = 0.f, n_ok = 0.f, n_bad = 0.f;
+    if (x < W && ys < h) {
+        int x0, x1;
+        float lx;
+        bil_index(x, w, sx, x0, x1, lx);
+        const int y1s = ys + (ys < h - 1 ? 1 : 0);
+        const float* S = seg + (long)b * nc * h * w;
+        const long r0 = (long)ys * w, r1 = (long)y1s * w;
+        float av[CH], dv[CH], accT[CH], accB[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            accT[c] = accB[c] = 0.f;
+            const float* Sc = S + (long)min(c0 + c, nc - 1) * h * w;        // clamped class: no branch around the loads
+            const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
+            const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
+            av[c] = a;
+            dv[c] = bb - a;
+        }
+        const float iy = 1.0f / sy;
+        int y_lo = ys == 0 ? 0 : (int)floorf((ys + 0.5f) * iy - 0.5f) - 1;
+        int y_hi = ys == h - 1 ? H - 1 : (int)ceilf((ys + 1.5f) * iy - 0.5f) + 1;
+        if (y_lo < 0) y_lo = 0;
+        if (y_hi > H - 1) y_hi = H - 1;
+        long labs[8];
+        for (int y = y_lo; y <= y_hi; ++y) {
+            if (((y - y_lo) & 7) == 0) {               // the labels of the next 8 rows: 8 independent loads in flight
+#pragma unroll
+                for (int u = 0; u < 8; ++u) labs[u] = label[((long)b * H + min(y + u, H - 1)) * W + x];
+            }
+            int y0, y1;
+            float ly;
+            bil_index(y, h, sy, y0, y1, ly);
+            long lab = labs[0];
+#pragma unroll
+            for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;
+            if (y0 != ys) continue;                      // wave-uniform
+            float zc[CH];
+            float mx = -INFINITY, sum = 0.f, zl = 0.f;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) zc[c] = c0 + c < nc ? fmaf(ly, dv[c], av[c]) : -INFINITY;
+            if constexpr (!MULTI) {
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    mx = fmaxf(mx, zc[c]);
+                    zl = c == lab ? zc[c] : zl;
+                }
+            } else {
+                // online log-sum-exp over all nc classes, CE_LSE_G at a time (loads from clamped class indices, issued together)
+                for (int cb = 0; cb < nc; cb += CE_LSE_G) {
+                    float zz[CE_LSE_G];
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) {
+                        const float* Sc = S + (long)min(cb + u, nc - 1) * h * w;
+                        const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
+                        const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
+                        zz[u] = cb + u < nc ? fmaf(ly, bb - a, a) : -INFINITY;
+                    }
+                    float m8 = mx;
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) {
+                        m8 = fmaxf(m8, zz[u]);
+                        zl = cb + u == lab ? zz[u] : zl;
+                    }
+                    float s8 = 0.f;
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) s8 += __expf(zz[u] - m8);
+                    sum = sum * __expf(mx - m8) + s8;
+                    mx = m8;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                zc[c] = __expf(zc[c] - mx);                // class past nc: exp(-inf) = 0
+                if constexpr (!MULTI) sum += zc[c];
+            }
+            const bool valid = lab != ignore && lab >= 0 && lab < nc;
+            if (ck == 0) {
+                l_sum += valid ? mx + __logf(sum) - zl : 0.f;
+                n_ok += valid ? 1.f : 0.f;
+                n_bad += (!valid && lab != ignore) ? 1.f : 0.f;
+            }
+            const float wp = valid ? 1.f : 0.f;
+            const float u = wp / sum;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                const float gval = fmaf(u, zc[c], c0 + c == lab ? -wp : 0.f);   // [valid] * (softmax_c - [c == label])
+                accT[c] += gval;
+                accB[c] = fmaf(ly, gval, accB[c]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c)
+            if (c0 + c < nc) {
+                const long o = (((long)b * nc + c0 + c) * h) * W + x;
+                if (y1s == ys) tmpA[o + (long)ys * W] = accT[c];               // last row: both weights land on it
+                else {
+                    tmpA[o + (long)ys * W] = accT[c] - accB[c];
+                    tmpB[o + (long)y1s * W] = accB[c];
+                }
+            }
+    }
+    const float a0 = block_sum(l_sum, red), a1 = block_sum(n_ok, red), a2 = block_sum(n_bad, red);
+    if (threadIdx.x == 0) {
+        const long blk = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        *reinterpret_cast<float4*>(part + blk * 4) = make_float4(a0, a1, a2, 0.f);
+    }
+}
+
+// sums = [loss = s0 / s1 (NaN when no pixel is valid, as F.cross_entropy), 1 / s1 (0 when s1 == 0: the gradient is then 0,
+// as torch's), n_valid, n_bad]: block partials in a fixed order, accumulated in double.
+__global__ __launch_bounds__(1024) void ce_loss_reduce_kernel(const float* __restrict__ part, float* __restrict__ sums, long nblk) {
+    __shared__ double red[3][1024];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (long i = threadIdx.x; i < nblk; i += 1024) {
+        const float4 v = *reinterpret_cast<const float4*>(part + i * 4);
+        s0 += v.x; s1 += v.y; s2 += v.z;
+    }
+    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = s2;
+    __syncthreads();
+    for (int k = 512; k > 0; k >>= 1) {
+        if (threadIdx.x < k) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + k];
+            red[1][threadIdx.x] += red[1][threadIdx.x + k];
+            red[2][threadIdx.x] += red[2][threadIdx.x + k];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double nll = red[0][0], n = red[1][0];
+        sums[0] = (float)(nll / n);
+        sums[1] = n > 0.0 ? (float)(1.0 / n) : 0.f;
+        sums[2] = (float)n;
+        sums[3] = (float)red[2][0];
+    }
+}
+
+extern "C" int wc_ce_loss_fwd_bwd(const float* seg, const int64_t* label, float* part, float* sums, float* tmp, float* grad, int B,
+                                  int nc, int h, int w, int H, int W, int ignore, void* stream) {
+    WC_CHECK_ARG(seg && label && part && sums && tmp && grad, "wc_ce_loss_fwd_bwd: null pointer");
+    WC_CHECK_ARG(B > 0 && nc >= 1 && nc <= CE_MAX_C && h > 0 && w > 0 && H > 0 && W > 0 && W <= 8192,
+                 "wc_ce_loss_fwd_bwd: bad size (1 <= nc <= 128, W <= 8192)");
+    const int nchunk = nc <= 32 ? 1 : (nc + 31) / 32;
+    WC_CHECK_ARG((long)B * nchunk <= 65535 && (long)B * nc * h * W < (1L << 40), "wc_ce_loss_fwd_bwd: batch too large");
+    WC_CHECK_ARG((uintptr_t)part % 16 == 0 && ((uintptr_t)seg | (uintptr_t)sums | (uintptr_t)tmp | (uintptr_t)grad) % 4 == 0 &&
+                 (uintptr_t)label % 8 == 0, "wc_ce_loss_fwd_bwd: misaligned pointer");
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid(wc_cdiv(W, 64), wc_cdiv(h, 4), B * nchunk);
+    float* tmpB = tmp + (long)B * nc * h * W;
+    const float sy = (float)h / H, sx = (float)w / W;
+    if (nc <= 24)
+        hipLaunchKernelGGL((ce_loss_fused_kernel<24, false>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
+                           nchunk, h, w, H, W, sy, sx, ignore);
+    else if (nc <= 32)
+        hipLaunchKernelGGL((ce_loss_fused_kernel<32, false>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
+                           nchunk, h, w, H, W, sy, sx, ignore);
+    else
+        hipLaunchKernelGGL((ce_loss_fused_kernel<32, true>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
+                           nchunk, h, w, H, W, sy, sx, ignore);
+    WC_LAUNCH_CHECK("ce_loss_fused_kernel");
+    hipLaunchKernelGGL(ce_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, (long)grid.x * grid.y * grid.z);
+    WC_LAUNCH_CHECK("ce_loss_reduce_kernel");
+    const long rows = (long)B * nc * h;
+    hipLaunchKernelGGL(seg_bwd_x2_kernel<true>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
+                       st, tmp, tmpB, grad, rows, h, w, W, sx, sums + 1);
+    WC_LAUNCH_CHECK("seg_bwd_x2_kernel<scaled>");
     return WC_OK;
 }
 

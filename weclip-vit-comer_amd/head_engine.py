@@ -43,8 +43,12 @@ def _uniform_stride(ts):
 
 
 class HeadEngine:
-    def __init__(self, fuse, dec):
+    def __init__(self, fuse, dec, attn_pred=True):
+        """attn_pred=False: seg-only mode (the supervised variant, WeCLIP_model/model_attn_aff_voc_seg.py): no Gram GEMM, no
+        sigmoid and no fp16 hi/lo copy of F (only the Gram product reads it); forward returns (seg, None, ctx) and the
+        backward is the `dap is None` path.  seg and every gradient are bit-identical to the default mode's."""
         self.fuse, self.dec = fuse, dec
+        self.attn_pred = bool(attn_pred)
         self.E = dec.linear_pred.weight.shape[1]
         self.nc = dec.linear_pred.weight.shape[0]
         self.index = fuse.indexes
@@ -99,7 +103,7 @@ class HeadEngine:
             dev = F_rows.device
             ctx = dict(B=B, L=Lq, h=h, w=w, xs=None, drop=None, ex=ex, front=False)
             F32_ = F_rows.detach().float().contiguous()
-            Fh = ops.split_f16(F32_, True)
+            Fh = ops.split_f16(F32_, True) if self.attn_pred else None
             ctx.update(F32=F32_, Fh=Fh)
             return self._decode(ctx, F32_, Fh, B, h, w, ex)
         C = xs[0].hi.shape[1]
@@ -141,11 +145,12 @@ class HeadEngine:
         # fuse (1x1 conv) + Dropout2d
         F32_ = torch.empty(M, E, device=dev, dtype=F32)
         # F always carries its fp16 remainder: the Gram matrix F^T F squares the rounding error of F and sigmoid'(0) = 1/4
-        # passes it on (attn_pred abs error 6e-3 with F rounded once, 1e-3 with hi+lo; the GEMM is 8.6 GFLOP)
-        Fh = Split(torch.empty(M, E, device=dev, dtype=F16), torch.empty(M, E, device=dev, dtype=F16))
+        # passes it on (attn_pred abs error 6e-3 with F rounded once, 1e-3 with hi+lo; the GEMM is 8.6 GFLOP).  Seg-only
+        # mode: nothing reads the fp16 copy, the GEMM writes F32 alone (same values: the copy is a rounding of them)
+        Fh = Split(torch.empty(M, E, device=dev, dtype=F16), torch.empty(M, E, device=dev, dtype=F16)) if self.attn_pred else None
         wf = wc.w("fuse")
-        ops.gemm(cat, wf, hw, E, n * E, bias=_f(self.fuse.linear_fuse.bias), out32=F32_, out16=Fh.hi, out16lo=Fh.lo,
-                 batch=B, sA=hw * n * E, sW=0, sC=hw * E, cscale=drop_scale, sCS=E)
+        ops.gemm(cat, wf, hw, E, n * E, bias=_f(self.fuse.linear_fuse.bias), out32=F32_, out16=Fh.hi if Fh else None,
+                 out16lo=Fh.lo if Fh else None, batch=B, sA=hw * n * E, sW=0, sC=hw * E, cscale=drop_scale, sCS=E)
         ctx.update(cat=cat, t1s=t1s, F32=F32_, Fh=Fh)
         return self._decode(ctx, F32_, Fh, B, h, w, ex)
 
@@ -170,6 +175,9 @@ class HeadEngine:
         ops.gemm(x3, wc.w("pred"), M, self.nc, E,
                  bias=_f(self.dec.linear_pred.bias), out32=seg_rows)
         seg = seg_rows.view(B, h, w, self.nc).permute(0, 3, 1, 2).contiguous()
+        if not self.attn_pred:             # seg-only mode
+            ctx["ap"] = None
+            return seg, None, ctx
         # attn_pred = sigmoid(F^T F) per image
         ap = torch.empty(B, hw, hw, device=dev, dtype=F32)
         ops.gemm(Fh, Fh, hw, hw, E, out32=ap, act=3, batch=B, sA=hw * E, sW=hw * E, sC=hw * hw)
@@ -364,7 +372,8 @@ class HeadEngine:
 
 
 class HeadFunction(torch.autograd.Function):
-    """autograd bridge: (params...) -> (seg, attn_pred); backward = HeadEngine.backward."""
+    """autograd bridge: (params...) -> (seg, attn_pred); backward = HeadEngine.backward.  In seg-only mode
+    (HeadEngine(attn_pred=False)) the second output is None and its gradient arrives as None."""
 
     @staticmethod
     def forward(ctx, engine, xs, B, Lq, h, w, drop_scale, *params):
@@ -384,7 +393,7 @@ class HeadFunction(torch.autograd.Function):
     def backward(ctx, dseg, dap):
         eng = ctx.engine
         g, _ = eng.backward(ctx.c, dseg.contiguous() if dseg is not None else None,
-                            dap.contiguous() if dap is not None else None)
+                            dap.contiguous() if dap is not None and eng.attn_pred else None)
         ctx.c = None
         return (None,) * 7 + handback(eng.params(), g)
 

@@ -37,6 +37,11 @@ def flip_avg(segs, out, weight, accumulate):
     return out
 
 
+def _seg_of(out):
+    """seg of a model output: the VOC / COCO models return (seg, cam_labels, attn_pred), the supervised variant seg alone."""
+    return out if isinstance(out, torch.Tensor) else out[0]
+
+
 def resize_argmax(seg, out_hw):
     """argmax_c F.interpolate(seg[None], size=out_hw, bilinear)[0, c] -> (H, W) int64."""
     C, Hs, Ws = seg.shape
@@ -46,7 +51,8 @@ def resize_argmax(seg, out_hw):
 
 
 class MscFlipEvaluator:
-    """`validate` of the reference, image by image.  model: WeCLIP (COCO or VOC) in eval mode on the GPU."""
+    """`validate` of the reference, image by image.  model: WeCLIP (COCO, VOC or the supervised VOC variant, whose forward
+    returns seg alone: test_msc_flip_seg.py:31-113) in eval mode on the GPU."""
 
     def __init__(self, model, num_classes, scales=(1.0, 0.75), resize_long=512, crf=None):
         """crf: optional utils.dcrf.DenseCRF for `add_with_crf` (the reference's crf_proc leg, test_msc_flip_voc.py:139-185)."""
@@ -74,7 +80,7 @@ class MscFlipEvaluator:
             h1, w1 = H, W
             pair = scale_flip_pair(x, (H, W), 1.0, 1.0)
         base = pair[0]                                        # the resized, un-flipped input all other scales start from
-        segs, _, _ = self.model(pair, ["", ""], mode="val")
+        segs = _seg_of(self.model(pair, ["", ""], mode="val"))
         segs = segs.float().contiguous()
         seg1 = segs[0].contiguous()
         msc = torch.empty_like(seg1)
@@ -85,7 +91,7 @@ class MscFlipEvaluator:
                 continue
             hs, ws = int(h1 * s), int(w1 * s)                 # F.interpolate(scale_factor=s): floor(size * s), step 1/s
             pair_s = scale_flip_pair(base, (hs, ws), 1.0 / s, 1.0 / s)
-            segs_s, _, _ = self.model(pair_s, ["", ""], mode="val")
+            segs_s = _seg_of(self.model(pair_s, ["", ""], mode="val"))
             flip_avg(segs_s.float().contiguous(), msc, w, accumulate=True)
         return seg1, msc
 

@@ -154,6 +154,19 @@ def _(seg_lowres, label, ignore_index):
     return seg_lowres.new_empty((), dtype=F32)
 
 
+@torch.library.custom_op(f"{_LIB}::ce_loss", mutates_args=(), device_types="cuda")
+def ce_loss(seg_lowres: Tensor, label: Tensor, ignore_index: int) -> Tensor:
+    """F.cross_entropy(F.interpolate(seg, label.shape[1:], bilinear), label, ignore_index) (the supervised variant's loss),
+    forward value only (the differentiable form is utils.losses.get_ce_loss_fused)."""
+    from .utils.losses import get_ce_loss_fused
+    return get_ce_loss_fused(seg_lowres.detach(), label, ignore_index).detach()
+
+
+@ce_loss.register_fake
+def _(seg_lowres, label, ignore_index):
+    return seg_lowres.new_empty((), dtype=F32)
+
+
 @torch.library.custom_op(f"{_LIB}::aff_loss", mutates_args=(), device_types="cuda")
 def aff_loss(attn_pred: Tensor, cam_label: Tensor, radius: int, ignore_index: int) -> Tensor:
     """get_aff_loss(attn_pred, cams_to_affinity_label(cam_label, radius mask)) (reference utils/losses.py:11-22,
@@ -335,4 +348,4 @@ def _(text, token_embedding, positional_embedding, blocks, heads, ln_final_weigh
 
 
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
-       "seg_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text")
+       "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text")

@@ -11,7 +11,7 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .utils.camutils import cams_to_affinity_label, get_mask_by_radius
-from .utils.losses import get_aff_loss, get_aff_loss_fused, get_seg_loss, get_seg_loss_fused
+from .utils.losses import get_aff_loss, get_aff_loss_fused, get_ce_loss_fused, get_seg_loss, get_seg_loss_fused
 from .utils.optimizer import PolyWarmupAdamW
 
 
@@ -183,3 +183,87 @@ class TrainStep:
         m.iter_num += 1
         o = ent["out"].clone()               # the graph's pool memory is rewritten by the next replay
         return o[0], o[1], o[2]
+
+
+class SupervisedTrainStep:
+    """forward -> cross-entropy -> backward -> (DP: gradient all-reduce) -> AdamW step for the fully supervised variant
+    (WeCLIP_model/model_attn_aff_voc_seg.py), whose labels are ground-truth masks.  The loss is
+    F.cross_entropy(F.interpolate(seg, label.shape[1:], bilinear, align_corners=False), label, ignore_index): the
+    reference ships no training script for this variant, so the loss is this package's choice; on the GPU
+    it runs fused (utils.losses.get_ce_loss_fused: the up-sampled logits are never materialised).
+
+    `step(img, label)`: img (B, 3, H, W) and label (B, Hl, Wl) integer device tensors the caller has prepared (any
+    augmentation happens before); returns the detached loss.  graph=True (CUDA tensors, with a bucket): forward + loss +
+    backward are captured once per (image shape, label shape, training flag) -- the first step of a signature runs eagerly,
+    the second captures -- and replayed from static input buffers; the all-reduce and the optimizer stay outside the graph,
+    as in TrainStep."""
+
+    def __init__(self, model, optimizer=None, ignore_index=255, bucket=True, graph=False):
+        self.model = model
+        self.opt = optimizer or make_optimizer(model)
+        self.ignore = int(ignore_index)
+        self.bucket = GradBucket(model.get_param_groups()[3]) if bucket else None
+        self.graph = bool(graph)
+        self._graphs = {}
+        self._pool = None
+        rng = None
+        if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
+            lo = self.bucket.flat.data_ptr()
+            rng = (lo, lo + 4 * self.bucket.flat.numel())
+        eng = getattr(model, "head_engine", None)
+        if eng is not None:
+            eng.direct_grads = rng
+
+    _reduce_grads = TrainStep._reduce_grads
+
+    def loss(self, seg, label):
+        if seg.is_cuda:
+            return get_ce_loss_fused(seg, label, ignore_index=self.ignore)
+        segs = F.interpolate(seg, size=label.shape[1:], mode="bilinear", align_corners=False)
+        return F.cross_entropy(segs, label.long(), ignore_index=self.ignore)
+
+    def _fwd_bwd(self, img, label):
+        seg = self.model(img, mode="train")
+        loss = self.loss(seg, label)
+        if self.bucket is not None:
+            self.bucket.zero()
+        else:
+            self.opt.zero_grad()
+        loss.backward()
+        return loss.detach()
+
+    def __call__(self, img, label):
+        if self.graph and img.is_cuda and self.bucket is not None:
+            out = self._graphed(img, label)
+        else:
+            out = self._fwd_bwd(img, label)
+        self._reduce_grads()
+        self.opt.step()
+        return out
+
+    step = __call__
+
+    def _graphed(self, img, label):
+        m = self.model
+        sig = (tuple(img.shape), tuple(label.shape), bool(m.training))
+        ent = self._graphs.get(sig)
+        if ent is None:                      # first step of this signature: eager (warms lazy state), sets up the statics
+            ent = self._graphs[sig] = {"graph": None, "img": torch.empty(img.shape, device=img.device, dtype=torch.float32),
+                                       "label": torch.empty(label.shape, device=img.device, dtype=torch.int64)}
+            ent["img"].copy_(img)
+            ent["label"].copy_(label)
+            return self._fwd_bwd(ent["img"], ent["label"])
+        ent["img"].copy_(img)
+        ent["label"].copy_(label)
+        if ent["graph"] is None:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            it = m.iter_num
+            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+                ent["out"] = self._fwd_bwd(ent["img"], ent["label"])
+            m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
+            self._pool = self._pool or g.pool()
+            ent["graph"] = g
+        ent["graph"].replay()
+        m.iter_num += 1
+        return ent["out"].clone()            # the graph's pool memory is rewritten by the next replay

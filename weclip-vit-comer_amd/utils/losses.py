@@ -82,6 +82,77 @@ def get_seg_loss_fused(seg_lowres, label, ignore_index=255):
     return _SegLossFn.apply(seg_lowres, label, ignore_index)
 
 
+def _ce_check(seg, label):
+    """Host-side checks of get_ce_loss_fused, before anything is allocated or launched."""
+    if not isinstance(seg, torch.Tensor) or not isinstance(label, torch.Tensor):
+        raise TypeError("get_ce_loss_fused: seg and label must be tensors")
+    if seg.dim() != 4:
+        raise ValueError(f"get_ce_loss_fused: seg must be (B, nc, h, w), got shape {tuple(seg.shape)}")
+    if label.dim() != 3:
+        raise ValueError(f"get_ce_loss_fused: label must be (B, H, W), got shape {tuple(label.shape)}")
+    if not seg.dtype.is_floating_point:
+        raise TypeError(f"get_ce_loss_fused: seg must be a floating-point tensor, got {seg.dtype}")
+    if label.dtype.is_floating_point or label.dtype.is_complex or label.dtype == torch.bool:
+        raise TypeError(f"get_ce_loss_fused: label must be an integer tensor, got {label.dtype}")
+    if seg.shape[0] != label.shape[0]:
+        raise ValueError(f"get_ce_loss_fused: batch sizes differ (seg {seg.shape[0]}, label {label.shape[0]})")
+    if not 1 <= seg.shape[1] <= 128:
+        raise ValueError(f"get_ce_loss_fused: 1 <= nc <= 128, got {seg.shape[1]}")
+    if min(seg.shape) == 0 or min(label.shape) == 0:
+        raise ValueError("get_ce_loss_fused: empty input")
+    if seg.device != label.device:
+        raise ValueError(f"get_ce_loss_fused: seg on {seg.device}, label on {label.device}")
+
+
+class _CELossFn(torch.autograd.Function):
+    """F.cross_entropy(F.interpolate(seg, label.shape[1:], 'bilinear', align_corners=False), label, ignore_index) without
+    materialising the up-sampled logits (csrc/losses.hip wc_ce_loss_fwd_bwd): loss and the gradient for an upstream
+    gradient of 1 come out of one pixel pass; backward only scales the saved gradient (no host synchronisation, so the
+    whole training step can be captured in a graph).  `ctx.sums` keeps [loss, 1/N_valid, N_valid, N_bad] on the device."""
+
+    @staticmethod
+    def forward(ctx, seg, label, ignore_index):
+        from .. import _lib as L
+        seg = seg.float().contiguous()
+        label = label.long().contiguous()
+        B, nc, h, w = seg.shape
+        H, W = label.shape[1:]
+        nchunk = 1 if nc <= 32 else (nc + 31) // 32
+        nblk = ((W + 63) // 64) * ((h + 3) // 4) * B * nchunk
+        part = torch.empty(nblk * 4, device=seg.device, dtype=torch.float32)
+        sums = torch.empty(4, device=seg.device, dtype=torch.float32)
+        tmp = torch.empty(2 * B * nc * h * W, device=seg.device, dtype=torch.float32)
+        grad = torch.empty_like(seg)
+        L.lib().wc_ce_loss_fwd_bwd(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(part), L.ptr(sums),
+                                   L.ptr(tmp), L.ptr(grad), B, nc, h, w, H, W, int(ignore_index), L.stream())
+        ctx.save_for_backward(grad)
+        _CELossFn.last_sums = sums
+        return sums[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def get_ce_loss_fused(seg_lowres, label, ignore_index=255):
+    """== F.cross_entropy(F.interpolate(seg_lowres, label.shape[1:], mode='bilinear', align_corners=False), label,
+    ignore_index=ignore_index): the supervised variant's loss (our choice: the reference ships no training script for it).
+    seg_lowres (B, nc, h, w) floating point, 1 <= nc <= 128; label (B, H, W) integer at any H x W.  All pixels ignored: the
+    loss is NaN (as torch) and the gradient is zero (as torch).  A label outside [0, nc) that is not ignore_index is treated
+    as ignored (torch raises instead); `ce_loss_counts()` reads how many there were in the last call."""
+    _ce_check(seg_lowres, label)
+    return _CELossFn.apply(seg_lowres, label, ignore_index)
+
+
+def ce_loss_counts():
+    """(N_valid, N_bad) of the last get_ce_loss_fused call as device floats (reading them synchronises)."""
+    s = getattr(_CELossFn, "last_sums", None)
+    if s is None:
+        raise RuntimeError("get_ce_loss_fused has not run yet")
+    return s[2], s[3]
+
+
 class _AffLossFn(torch.autograd.Function):
     """get_aff_loss(attn_pred, cams_to_affinity_label(cam_label, radius mask)) in one pass (csrc/losses.hip),
     without the (B, hw, hw) label / mask tensors."""
