@@ -539,6 +539,36 @@ int wc_augment_workspace_ints(int B, int crop, long* n_ints);       /* HOST out-
 int wc_augment_normalize(const void* src_u8, const void* params, float* dst, int* coeff_ws, int B, int Hs, int Ws, int crop,
                          const float* mean3, const float* std3, void* stream);
 
+/* Label-aware variant for the fully supervised model (csrc/augment_seg.hip): the chain of
+ * `VOC12SegDataset.__transforms` (datasets/voc.py:216-251) = _img_rescaling(image, label) when enabled (datasets/transforms.py:35-51:
+ * PIL BILINEAR image, PIL NEAREST label) -> random_fliplr(image, label) (:75-88) -> PhotoMetricDistortion (:178-264) ->
+ * random_crop(image, label) (:119-176, label padded with ignore_index, crop box from get_random_cropbox :137-156) ->
+ * normalize_img (:8-15) + HWC->CHW, with every random draw made on the host and nothing read back.
+ * src_u8 (B,Hs,Ws,3) / lab_u8 (B,Hs,Ws) uint8.  params: B records of 16 x 32 bit (device memory)
+ *   {float scale; int flip, rh, rw, pad_y, pad_x; int photo; float beta, alpha_c, alpha_s; int hue; int reserved[5]}
+ *   photo: bit 0 brightness, 1 contrast, 2 saturation, 3 hue gate; bit 4 = `mode` (1: contrast before saturation, :247-251);
+ *   beta / alpha_c / alpha_s: the random.uniform amounts as float32 (`convert`, :191-195, works in float32); hue in [-18, 18).
+ * cand (B, n_cand, 2) int32 {H_start, W_start}: the candidate boxes in draw order.  For every candidate the classes of the
+ * label inside the window (flipped, rescaled, padded) are counted; the first with n_valid > 0 and 4 * max_count < 3 * n_valid
+ * is taken (np.max(cnt) / np.sum(cnt) < 0.75 over the non-ignored classes, :150-154), else the last one.
+ * Out: dst (B,3,crop,crop) f32; dst_label (B,crop,crop) int64; sel (B,4) int32 {H_start, W_start, chosen candidate, accepted};
+ * img_box (B,4) int32 as :162-166.  ws: *n_ints ints from wc_seg_augment_workspace_ints.  canvas_max: upper bound of
+ * max(crop, rh, rw) over the batch (sizes the per-coordinate tables).
+ * Saturation / hue use OpenCV's 8-bit COLOR_BGR2HSV / COLOR_HSV2BGR (mmcv.bgr2hsv / hsv2bgr) as restated in tests/photo_ref.py,
+ * applied to the RGB triple as if it were BGR like the reference does.
+ * PRECONDITIONS, refused with WC_ERR_ARG: n_cand in [1,16], crop in [1,4096], crop <= canvas_max <= 65536, Hs, Ws <= 16384,
+ * ignore_index in [0,255].  Checked on the device (records are device memory): candidates are clamped into the canvas;
+ * rh / rw outside [1, canvas_max] or down-scaling beyond 4x make the image NaN, as wc_augment_normalize does. */
+int wc_seg_augment_workspace_ints(int B, int crop, int canvas_max, int n_cand, long* n_ints);       /* HOST out-parameter */
+int wc_seg_augment(const void* src_u8, const void* lab_u8, const void* params, const int* cand, float* dst, int64_t* dst_label,
+                   int* sel, int* img_box, int* ws, int B, int Hs, int Ws, int crop, int canvas_max, int n_cand, int ignore_index,
+                   const float* mean3, const float* std3, void* stream);
+/* The candidate histogram + select stage of wc_seg_augment alone (transforms.py:137-156, :162-166): sel and img_box only. */
+int wc_seg_crop_select(const void* lab_u8, const void* params, const int* cand, int* sel, int* img_box, int* ws, int B, int Hs,
+                       int Ws, int crop, int canvas_max, int n_cand, int ignore_index, void* stream);
+/* n uint8 triples through the 8-bit BGR -> HSV (inverse = 0) or HSV -> BGR (inverse = 1) conversion used above. */
+int wc_hsv8_convert(const void* src_u8, void* dst_u8, long n, int inverse, void* stream);
+
 /* ---- dense CRF (csrc/dcrf.hip; DESIGN.md "Dense CRF") -------------------------------------------------------------- */
 /* utils/dcrf.py (`DenseCRF`, `crf_inference`, `crf_inference_label`: pydensecrf's DenseCRF2D with one Gaussian and one
  * bilateral Potts term) as the EXACT mean-field inference of the fully connected CRF (no permutohedral lattice; parity

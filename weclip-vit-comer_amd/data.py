@@ -18,7 +18,10 @@ class SyntheticVOCLoader:
     source="float": the pool holds ready normalised batches (what the parity tests feed).
     source="uint8": the pool holds uint8 (B, 375, 500, 3) "decoded JPEGs" on the device and every next() runs the
     device-side input pipeline (DeviceAugment: random rescale / flip / pad + crop / normalise, csrc/augment.hip) --
-    the per-step work of the reference's loader, minus JPEG decoding, on the GPU and inside the timed step."""
+    the per-step work of the reference's loader, minus JPEG decoding, on the GPU and inside the timed step.
+    source="seg": the fully supervised variant's input -- uint8 images plus uint8 ground-truth maps
+    (synth.make_label_maps) on the device; every next() runs DeviceSegAugment (csrc/augment_seg.hip) and yields
+    (images (B,3,S,S) f32, labels (B,S,S) int64), what SupervisedTrainStep takes."""
 
     def __init__(self, batch, size, classes_per_image=2, rank=0, world=1, seed=100, pool=4, device="cuda",
                  n_classes=20, source="float", src_hw=(375, 500)):
@@ -26,15 +29,21 @@ class SyntheticVOCLoader:
         self.images, self.labels = [], []
         for j in range(pool):
             s = seed + 1000 * j + rank            # j = 0, rank = 0 is bench.py's historical batch (seed 100 / 7)
-            if source == "uint8":
+            if source in ("uint8", "seg"):
                 f = synth.make_images(batch, src_hw[0], src_hw[1], seed=s)
                 u8 = (f * 58.0 + 118.0).clamp_(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
                 self.images.append(u8.to(device))
             else:
                 self.images.append(synth.make_images(batch, size, size, seed=s).to(device))
-            self.labels.append(synth.make_label_lists(batch, classes_per_image, n_classes=n_classes,
-                                                      seed=7 + 1000 * j + rank))
+            if source == "seg":
+                self.labels.append(synth.make_label_maps(batch, src_hw[0], src_hw[1], n_classes=n_classes + 1,
+                                                         seed=7 + 1000 * j + rank).to(device))
+            else:
+                self.labels.append(synth.make_label_lists(batch, classes_per_image, n_classes=n_classes,
+                                                          seed=7 + 1000 * j + rank))
         self.aug = DeviceAugment(crop_size=size, seed=seed + rank) if source == "uint8" else None
+        if source == "seg":
+            self.aug = DeviceSegAugment(crop_size=size, seed=seed + rank)
         self._i = 0
 
     def __len__(self):
@@ -43,6 +52,8 @@ class SyntheticVOCLoader:
     def next(self):
         i = self._i % len(self.images)
         self._i += 1
+        if self.source == "seg":
+            return self.aug(self.images[i], self.labels[i])[:2]
         if self.aug is not None:
             return self.aug(self.images[i]), self.labels[i]
         return self.images[i], self.labels[i]
@@ -126,3 +137,163 @@ class DeviceAugment:
                                      L.ptr(out), L.ptr(self._ws, torch.int32), B, H, W, self.crop,
                                      (ctypes.c_float * 3)(*self.mean), (ctypes.c_float * 3)(*self.std), L.stream())
         return out
+
+
+class DeviceSegAugment:
+    """The reference's label-aware train-time augmentation of the fully supervised variant (`VOC12SegDataset.__transforms`,
+    datasets/voc.py:216-251: random_fliplr(image, label) -> PhotoMetricDistortion -> random_crop(image, label) ->
+    normalize_img -> CHW; optionally random_scaling(image, label) first, which the reference has commented out, hence
+    rescale_range=None) with the random draws on the host and all pixel work in HIP kernels (csrc/augment_seg.hip):
+    uint8 (B,H,W,3) images and uint8 (B,H,W) label maps on the device in; float32 (B,3,crop,crop) image, int64
+    (B,crop,crop) label (ignore_index in the padding) and int32 (B,4) img_box out.  The label-aware crop box
+    (get_random_cropbox, transforms.py:137-156) is chosen on the device from `n_cand` host-drawn candidates and never
+    returns to the host; `self.sel` (B,4) int32 {H_start, W_start, chosen candidate, accepted} of the last call stays on
+    the device for inspection.
+
+    Draw order per image, from private `random.Random(seed)` / `np.random.RandomState(seed)` instances, follows the
+    reference's sources: [`random.uniform` (scale)] -> `random.random` (flip) -> the draws of
+    PhotoMetricDistortion.__call__ (`np.random.randint(2)` gates, `random.uniform` amounts, `np.random.randint(-18, 18)`
+    for hue, the `mode` draw) -> `np.random.randint` x 2 (pad) -> `random.randrange` x 2 per candidate.
+    DELIBERATE DIFFERENCE: the reference stops drawing candidates at the first accepted one; that needs the histogram
+    result on the host, so this pipeline always draws all `n_cand`.  The chosen box has the same distribution, but a
+    seeded loader does not replay a reference worker's random stream past the first image.  Given the same candidate list
+    the result is identical (tests/golden/seg_augment_ref.npz).
+
+    Pinned to the unmodified reference code, exactly: flip, brightness, contrast, pad, crop-box selection, label handling,
+    img_box, normalisation (and Pillow's BILINEAR / NEAREST when rescaling).  Saturation and hue go through OpenCV's 8-bit
+    BGR<->HSV conversions, which are pinned to a restatement (tests/photo_ref.py), UNVERIFIED AGAINST REAL OPENCV."""
+
+    N_CAND = 10                                                            # transforms.py:139
+
+    def __init__(self, crop_size=512, rescale_range=None, fliplr=True, photometric=True, ignore_index=255, seed=0, mean=MEAN,
+                 std=STD, np_seed=None, n_cand=N_CAND, brightness_delta=32, contrast_range=(0.5, 1.5),
+                 saturation_range=(0.5, 1.5), hue_delta=18):
+        import random
+        import numpy as np
+        self.crop, self.range, self.fliplr = int(crop_size), tuple(rescale_range) if rescale_range else None, bool(fliplr)
+        self.photometric, self.ignore_index, self.n_cand = bool(photometric), int(ignore_index), int(n_cand)
+        self.brightness_delta, self.contrast_range = brightness_delta, tuple(contrast_range)
+        self.saturation_range, self.hue_delta = tuple(saturation_range), int(hue_delta)
+        self.py_rng = random.Random(seed)
+        self.np_rng = np.random.RandomState(seed if np_seed is None else np_seed)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+        self.draw_names = []               # generator method names of the last draw_one(), in call order
+        self._ws = None
+        self.sel = None
+
+    def _py(self, name, *a):
+        self.draw_names.append(name)
+        return getattr(self.py_rng, name)(*a)
+
+    def _np(self, *a):
+        self.draw_names.append("randint")
+        return int(self.np_rng.randint(*a))
+
+    def draw_one(self, H, W):
+        """(scale, flip, rh, rw, pad_y, pad_x, photo, beta, alpha_c, alpha_s, hue, candidates) of one image; photo is the
+        kernel's bit set (1 brightness, 2 contrast, 4 saturation, 8 hue, 16 mode), candidates a list of (H_start, W_start)."""
+        self.draw_names = []
+        s = self._py("uniform", *self.range) if self.range else 1.0
+        rh, rw = (int(s * H), int(s * W)) if self.range else (H, W)
+        flip = int(self._py("random") > 0.5) if self.fliplr else 0
+        photo, beta, alpha_c, alpha_s, hue = 0, 0.0, 1.0, 1.0, 0
+        if self.photometric:                                               # PhotoMetricDistortion.__call__, transforms.py:235-264
+            def contrast():
+                if self._np(2):
+                    return 2, self._py("uniform", *self.contrast_range)
+                return 0, 1.0
+            if self._np(2):
+                photo |= 1
+                beta = self._py("uniform", -self.brightness_delta, self.brightness_delta)
+            mode = self._np(2)
+            photo |= 16 * mode
+            if mode == 1:
+                bit, alpha_c = contrast()
+                photo |= bit
+            if self._np(2):
+                photo |= 4
+                alpha_s = self._py("uniform", *self.saturation_range)
+            if self._np(2):
+                photo |= 8
+                hue = self._np(-self.hue_delta, self.hue_delta)
+            if mode == 0:
+                bit, alpha_c = contrast()
+                photo |= bit
+        ch, cw = max(self.crop, rh), max(self.crop, rw)                    # canvas (transforms.py:123-124)
+        pad_y, pad_x = self._np(ch - rh + 1), self._np(cw - rw + 1)
+        cands = []
+        for _ in range(self.n_cand):
+            y = self._py("randrange", 0, ch - self.crop + 1, 1)
+            cands.append((y, self._py("randrange", 0, cw - self.crop + 1, 1)))
+        return s, flip, rh, rw, pad_y, pad_x, photo, beta, alpha_c, alpha_s, hue, cands
+
+    def pack(self, draws):
+        """List of draw_one() tuples -> (int32 (B, 16) records, int32 (B, n_cand, 2) candidates) in the kernels' layout.
+        A candidate list shorter than n_cand is filled up by repeating its last entry (the selection cannot change: the
+        repeated box is accepted or rejected like the entry it repeats, and the last candidate is the fall-back)."""
+        import numpy as np
+        rec = np.zeros((len(draws), 16), np.int32)
+        cand = np.zeros((len(draws), self.n_cand, 2), np.int32)
+        f32 = lambda v: np.float32(v).view(np.int32)                       # noqa: E731
+        for b, d in enumerate(draws):
+            rec[b, 0] = f32(d[0])
+            rec[b, 1:7] = d[1:7]
+            rec[b, 7], rec[b, 8], rec[b, 9] = f32(d[7]), f32(d[8]), f32(d[9])
+            rec[b, 10] = d[10]
+            c = list(d[11])
+            if not 1 <= len(c) <= self.n_cand:
+                raise RuntimeError(f"DeviceSegAugment: 1 to {self.n_cand} candidates per image, got {len(c)}")
+            cand[b] = c + [c[-1]] * (self.n_cand - len(c))
+        return torch.from_numpy(rec), torch.from_numpy(cand)
+
+    def draw(self, B, H, W):
+        """Host-side random parameters of one batch -> (records, candidates), see pack()."""
+        return self.pack([self.draw_one(H, W) for _ in range(B)])
+
+    def canvas_max(self, H, W):
+        """Upper bound of the padded canvas side over every draw (sizes the kernels' per-coordinate tables)."""
+        hi = self.range[1] if self.range else 1.0
+        return max(self.crop, int(hi * H), int(hi * W))
+
+    def __call__(self, images_u8, labels_u8, params=None):
+        """images_u8 (B,H,W,3) / labels_u8 (B,H,W) uint8 CUDA; params: a draw() / pack() result, host or device resident
+        (default: a fresh draw).  -> (image (B,3,crop,crop) f32, label (B,crop,crop) int64, img_box (B,4) int32).
+        With device-resident params nothing here synchronises with the host: five kernels and one memset on the current
+        stream, capturable in a graph as one linear chain."""
+        import ctypes
+        from . import _lib as L
+        L.require_gpu()
+        B, H, W, C = images_u8.shape
+        if C != 3 or images_u8.dtype != torch.uint8:
+            raise RuntimeError("DeviceSegAugment expects uint8 (B, H, W, 3) images")
+        if labels_u8.dtype != torch.uint8 or tuple(labels_u8.shape) != (B, H, W):
+            raise RuntimeError("DeviceSegAugment expects uint8 (B, H, W) label maps of the images' size")
+        rec, cand = self.draw(B, H, W) if params is None else params
+        cm = self.canvas_max(H, W)
+        if tuple(rec.shape) != (B, 16) or tuple(cand.shape) != (B, self.n_cand, 2):
+            raise RuntimeError("DeviceSegAugment: params must be (B, 16) records and (B, n_cand, 2) candidates")
+        if not rec.is_cuda:
+            rhw = rec[:, 2:4]
+            if int(rhw.min()) < 1 or H > 4 * int(rhw[:, 0].min()) or W > 4 * int(rhw[:, 1].min()) or int(rhw.max()) > cm:
+                raise RuntimeError("DeviceSegAugment: rescaled size must be >= 1, within rescale_range and down-scaling at most 4x")
+            lim = (rhw.clamp(min=self.crop) - self.crop)[:, None, :]
+            if not cand.is_cuda and (int(cand.min()) < 0 or bool((cand > lim).any())):
+                raise RuntimeError("DeviceSegAugment: candidate box outside the padded canvas")
+        dev = images_u8.device
+        rec = rec if rec.is_cuda else rec.pin_memory().to(dev, non_blocking=True)
+        cand = cand if cand.is_cuda else cand.pin_memory().to(dev, non_blocking=True)
+        out = torch.empty(B, 3, self.crop, self.crop, device=dev, dtype=torch.float32)
+        lab = torch.empty(B, self.crop, self.crop, device=dev, dtype=torch.int64)
+        sel = torch.empty(B, 4, device=dev, dtype=torch.int32)
+        box = torch.empty(B, 4, device=dev, dtype=torch.int32)
+        n = ctypes.c_long(0)
+        L.lib().wc_seg_augment_workspace_ints(B, self.crop, cm, self.n_cand, ctypes.byref(n))
+        if self._ws is None or self._ws.numel() < n.value or self._ws.device != dev:
+            self._ws = torch.empty(n.value, device=dev, dtype=torch.int32)
+        L.lib().wc_seg_augment(L.ptr(images_u8.contiguous(), torch.uint8, "images"), L.ptr(labels_u8.contiguous(), torch.uint8, "labels"),
+                               L.ptr(rec, torch.int32, "params"), L.ptr(cand, torch.int32, "candidates"), L.ptr(out),
+                               L.ptr(lab, torch.int64), L.ptr(sel), L.ptr(box), L.ptr(self._ws, torch.int32), B, H, W, self.crop,
+                               cm, self.n_cand, self.ignore_index, (ctypes.c_float * 3)(*self.mean),
+                               (ctypes.c_float * 3)(*self.std), L.stream())
+        self.sel = sel
+        return out, lab, box

@@ -203,3 +203,25 @@ def make_label_lists(batch, k=2, n_classes=20, seed=7):
     """K distinct foreground class ids (0-based, sorted like np.unique) per image."""
     rs = np.random.RandomState(seed)
     return [sorted(rs.choice(n_classes, size=k, replace=False).tolist()) for _ in range(batch)]
+
+
+def make_label_maps(batch, H, W, n_classes=21, regions=6, seed=11, ignore_border=1):
+    """Piecewise-constant ground-truth maps (batch, H, W) uint8, VOC-shaped: `regions` Voronoi cells per image around
+    seeded points, cell 0 background (class 0), the others a random foreground class each, with `ignore_border` pixels of
+    255 drawn between differing classes like VOC's object outlines.  regions=1 gives a single-class map."""
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = np.zeros((batch, H, W), np.uint8)
+    for b in range(batch):
+        py, px = rs.randint(0, H, size=regions), rs.randint(0, W, size=regions)
+        cls = np.concatenate([[0], rs.randint(1, n_classes, size=regions - 1)]).astype(np.uint8)
+        d = (yy[None] - py[:, None, None]) ** 2 + (xx[None] - px[:, None, None]) ** 2
+        lab = cls[d.argmin(0)]
+        if ignore_border and regions > 1:
+            edge = np.zeros((H, W), bool)
+            for k in range(1, ignore_border + 1):
+                edge[:, :-k] |= lab[:, :-k] != lab[:, k:]
+                edge[:-k, :] |= lab[:-k, :] != lab[k:, :]
+            lab = np.where(edge, np.uint8(255), lab)
+        out[b] = lab
+    return torch.from_numpy(out)
