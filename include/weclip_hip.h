@@ -624,6 +624,35 @@ int wc_text_pool(const float* x, const int* eot, int N, int L, int W, const floa
                  const float* proj, int Ed, float* feat, void* stream);
 int wc_text_zeroshot(const float* feat, int C, int T, int Ed, float* out, void* stream);
 
+/* ---- stand-alone CAM generation (csrc/preprocess.hip) ----------------------------------------- */
+/* wc_clip_preprocess: clip/generate_cams_voc12.py:76-93 (`_transform_resize`, `img_ms_and_flip`; the same lines of
+ *   generate_cams_coco14.py): Resize((h, w), BICUBIC) -> ToTensor -> Normalize(mean, std), and torch.flip(image, [-1]).
+ *   src_u8 (B,H0,W0,3) uint8 HWC RGB, every image of one source size.  dst (B,3,h,w) f32; dst_flip (B,3,h,w) f32 or NULL;
+ *   out_u8 (B,h,w,3) uint8 or NULL: the image after the resize alone.  The resize is Pillow's 8-bit
+ *   `Image.resize((w, h), BICUBIC)` (Resample.c: separable, horizontal pass first into a uint8 intermediate; window
+ *   support = 2 * max(1, in / out) around (x + 0.5) * in / out; cubic kernel with a = -0.5; weights normalised in double
+ *   precision, then 22-bit fixed point rounded half away from zero; pixel = clip8((2^21 + sum w_i p_i) >> 22)), bit for bit.
+ *   Then x / 255, - mean, / std as three separately rounded fp32 operations.  mean3 / std3: HOST arrays of 3 floats.
+ *   ws: *n_bytes bytes of device memory from wc_clip_preprocess_workspace_bytes (weight tables + the intermediate);
+ *   ws_bytes: the size of the buffer passed, refused with WC_ERR_ARG when it is smaller than that.
+ *   Limits (WC_ERR_ARG, nothing launched): B in [1,65535], every size in [1,16384], down-scaling by at most 8 per axis.
+ * wc_cam_scale_resize_f16: pytorch_grad_cam/utils/image.py:51-61 (`scale_cam_image([cam], (ori_w, ori_h))`) followed by the
+ *   dumpers' `.astype(np.float16)` (generate_cams_voc12.py:198,215).  cam (P, gh*gw) f32, P (image, class) pairs of one
+ *   token grid; per pair m = min, (v - m) / (1e-7 + (max - m)) in fp32, bilinear resize to the pair's own (ori_h, ori_w):
+ *   src = max((dst + 0.5) * in / out - 0.5, 0), second tap clamped (OpenCV INTER_LINEAR on a float image), in fp32, stored
+ *   as fp16 (round to nearest even).  sizes (P,2) int32 {ori_h, ori_w}, offsets (P) int64 = first element of pair p in
+ *   out_f16 (both device memory); out_elems = number of fp16 elements of out_f16 (nothing is written outside it);
+ *   max_pixels >= max_p ori_h * ori_w sizes the grid.  gh * gw <= 4096, P <= 65535.
+ * wc_cam_resize_f32: the bilinear resize alone, f32 -> f32 (`cv2.resize(grayscale_cam, (ori_w, ori_h))`,
+ *   generate_cams_voc12.py:159, and GradCAM.__call__(target_size=...)); same tables. */
+int wc_clip_preprocess_workspace_bytes(int B, int H0, int W0, int h, int w, long* n_bytes);          /* HOST out-parameter */
+int wc_clip_preprocess(const void* src_u8, float* dst, float* dst_flip, void* out_u8, void* ws, long ws_bytes, int B, int H0, int W0, int h,
+                       int w, const float* mean3, const float* std3, void* stream);
+int wc_cam_scale_resize_f16(const float* cam, const int* sizes, const int64_t* offsets, void* out_f16, long out_elems, int P, int gh,
+                            int gw, int max_pixels, void* stream);
+int wc_cam_resize_f32(const float* cam, const int* sizes, const int64_t* offsets, float* out, long out_elems, int P, int gh, int gw,
+                      int max_pixels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

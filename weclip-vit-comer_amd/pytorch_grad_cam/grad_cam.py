@@ -3,7 +3,7 @@
 
     cam = GradCAM(model=clip_model, target_layers=[...resblocks[-1].ln_1], reshape_transform=fn)
     grayscale_cam, probs, attn_last = cam(input_tensor=[feats (L,N,D), text (T,Ed), h, w],
-                                          targets=[ClipOutputTarget(k)], target_size=None)
+                                          targets=[ClipOutputTarget(k)], target_size=None or (width, height))
 
 returns `grayscale_cam` np.float32 (N, h/16, w/16) in [0,1], the class probabilities (N,T) and the
 last block's head-mean attention (N,L,L).  The gradient is analytic (gradcam_engine), so hooks on
@@ -33,8 +33,8 @@ class GradCAM:
         return state.grad_cam(text_hat, text_idx, n_text, pair_img, pair_cls, Tmax)
 
     def __call__(self, input_tensor, targets=None, target_size=None, aug_smooth=False, eigen_smooth=False):
-        if aug_smooth or eigen_smooth or target_size is not None:
-            raise NotImplementedError("aug_smooth / eigen_smooth / target_size are unused by WeCLIP")
+        if aug_smooth or eigen_smooth:
+            raise NotImplementedError("aug_smooth / eigen_smooth are unused by WeCLIP")
         feats, text, H, W = input_tensor
         rows, N, Lq = VE.to_rows(feats)
         st = last_layer_forward(self.model, rows, N, Lq)
@@ -51,5 +51,14 @@ class GradCAM:
         idx = torch.arange(T, **i32).repeat(N, 1).contiguous()
         cams, probs, _ = st.grad_cam(that, idx, torch.full((N,), T, **i32), torch.arange(N, **i32),
                                      torch.tensor(cats, **i32), T)
+        if target_size is not None:
+            # base_cam.py:145,154: scale_cam_image(cam, target_size) = bilinear resize of the min-max map to (width, height),
+            # then scale_cam_image of the result; the resize is the output kernel of the CAM dumpers (csrc/preprocess.hip)
+            from ..clip.generate_cams import resize_cam_f32
+            Wt, Ht = int(target_size[0]), int(target_size[1])
+            hi = torch.stack(resize_cam_f32(cams, H // 16, W // 16, [(Ht, Wt)] * N))
+            hi = hi - hi.amin(dim=(1, 2), keepdim=True)
+            hi = hi / (1e-7 + hi.amax(dim=(1, 2), keepdim=True))
+            return hi.cpu().numpy().astype(np.float32), probs, st.mean
         cam = cams.view(N, H // 16, W // 16).cpu().numpy().astype(np.float32)
         return cam, probs, st.mean
