@@ -538,6 +538,22 @@ int wc_cti_gate_grads(const float* G, const float* gs, const float* gamma, const
 int wc_augment_workspace_ints(int B, int crop, long* n_ints);       /* HOST out-parameter */
 int wc_augment_normalize(const void* src_u8, const void* params, float* dst, int* coeff_ws, int B, int Hs, int Ws, int crop,
                          const float* mean3, const float* std3, void* stream);
+/* The same chain for a batch of images of DIFFERENT sizes, as files of VOC / COCO are (datasets/voc.py:48-67, :160-180 and
+ * datasets/coco.py:54-76, :156-167 hand every image to the transforms at its own size; datasets/transforms.py:26-49, :70-84,
+ * :119-176, :8-15 as above).  src_u8: src_bytes bytes, the images uint8 HWC back to back; offsets (B) int64: byte offset of
+ * each image (a multiple of 3); sizes (B,2) int32 {H, W}; both tables are device memory, like params.  The kernels are the
+ * ones of wc_augment_normalize instantiated with a per-image extent (csrc/augment_shape.h): a batch of equal sizes gives the
+ * same bits.  The workspace is wc_augment_workspace_ints(B, crop): it does not depend on the source sizes.
+ * Checked on the device: an image with H or W outside [1, 16384], an offset that is negative or no multiple of 3, or an
+ * extent beyond src_bytes is not read at all and its output is NaN; in/out <= 4 as above. */
+int wc_augment_normalize_ragged(const void* src_u8, long src_bytes, const int64_t* offsets, const int* sizes, const void* params,
+                                float* dst, int* coeff_ws, int B, int crop, const float* mean3, const float* std3, void* stream);
+/* The un-augmented path (aug=False: datasets/transforms.py:8-15 normalize_img + HWC->CHW, datasets/voc.py:137-143, :247-249;
+ * the label as the collated LongTensor of a stock DataLoader): src_u8 (H,W,3) uint8 -> dst (3,H,W) f32; lab_u8 (H,W) uint8 ->
+ * dst_label (H,W) int64, both NULL when there is no label.  mean3 / std3: HOST double[3] -- numpy evaluates
+ * (uint8 - float) / float in double precision and rounds once into the float32 array; this does the same. */
+int wc_normalize_u8(const void* src_u8, const void* lab_u8, float* dst, int64_t* dst_label, int H, int W, const double* mean3,
+                    const double* std3, void* stream);
 
 /* Label-aware variant for the fully supervised model (csrc/augment_seg.hip): the chain of
  * `VOC12SegDataset.__transforms` (datasets/voc.py:216-251) = _img_rescaling(image, label) when enabled (datasets/transforms.py:35-51:
@@ -563,6 +579,17 @@ int wc_seg_augment_workspace_ints(int B, int crop, int canvas_max, int n_cand, l
 int wc_seg_augment(const void* src_u8, const void* lab_u8, const void* params, const int* cand, float* dst, int64_t* dst_label,
                    int* sel, int* img_box, int* ws, int B, int Hs, int Ws, int crop, int canvas_max, int n_cand, int ignore_index,
                    const float* mean3, const float* std3, void* stream);
+/* wc_seg_augment for a batch of images of different sizes (datasets/voc.py:253-271, datasets/coco.py:232-239: every image and
+ * its label map reach `__transforms` at their own size).  src_u8 / offsets / sizes as wc_augment_normalize_ragged; lab_u8: the
+ * label maps (H,W) uint8 packed in the same order, image b's map at byte offsets[b] / 3, so the buffer holds at least
+ * src_bytes / 3 bytes.  canvas_max: max(crop, rh, rw) over the batch, which also sizes the workspace
+ * (wc_seg_augment_workspace_ints: no term depends on the source sizes, so it serves both forms).  Same kernels as
+ * wc_seg_augment (csrc/augment_shape.h).  An image that fails the device check of wc_augment_normalize_ragged comes out as
+ * NaN with an all-ignore label. */
+int wc_seg_augment_ragged(const void* src_u8, const void* lab_u8, long src_bytes, const int64_t* offsets, const int* sizes,
+                          const void* params, const int* cand, float* dst, int64_t* dst_label, int* sel, int* img_box, int* ws,
+                          int B, int crop, int canvas_max, int n_cand, int ignore_index, const float* mean3, const float* std3,
+                          void* stream);
 /* The candidate histogram + select stage of wc_seg_augment alone (transforms.py:137-156, :162-166): sel and img_box only. */
 int wc_seg_crop_select(const void* lab_u8, const void* params, const int* cand, int* sel, int* img_box, int* ws, int B, int Hs,
                        int Ws, int crop, int canvas_max, int n_cand, int ignore_index, void* stream);

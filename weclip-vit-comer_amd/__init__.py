@@ -25,6 +25,7 @@ def register_torch_ops():
 
 
 DROPIN_NAMES = ("clip", "pytorch_grad_cam", "WeCLIP_model", "utils")
+_optional_names = set()        # aliased on request only: "datasets" (install_dropin(datasets=True))
 
 
 class _AliasLoader:
@@ -54,7 +55,7 @@ class _AliasFinder:
     def find_spec(self, fullname, path=None, target=None):
         import importlib
         import importlib.util
-        if fullname.split(".", 1)[0] not in DROPIN_NAMES:
+        if fullname.split(".", 1)[0] not in DROPIN_NAMES and fullname.split(".", 1)[0] not in _optional_names:
             return None
         real_name = f"{__name__}.{fullname}"
         try:
@@ -70,7 +71,7 @@ class _AliasFinder:
 _finder = None
 
 
-def install_dropin(reference_root=None):
+def install_dropin(reference_root=None, datasets=False):
     """Make the reference's import lines (scripts/dist_clip_voc.py:17-23, test_msc_flip_*.py) resolve to this
     package from a fresh interpreter:
 
@@ -84,14 +85,21 @@ def install_dropin(reference_root=None):
     whose `utils/` directory is appended to that package's search path, so the helper modules this package does
     not provide (imutils, ...) still import from the user's tree; its `clip/` directory is appended to the `clip`
     package's path the same way (`from clip.clip_text import new_class_names, BACKGROUND_CATEGORY`, and the BPE merges
-    file `clip.tokenize` reads).  The package's own modules keep precedence."""
+    file `clip.tokenize` reads).  The package's own modules keep precedence.
+
+    datasets=True additionally maps `import datasets`, `from datasets import voc` and `from datasets import coco`
+    (scripts/dist_clip_voc.py:13, scripts/dist_clip_coco.py) onto this package's `datasets` (same class names and constructor
+    arguments; train-time batches come from `datasets.DeviceLoader`).  Off by default: the name is a common
+    one, and a script that keeps the reference's host loader must keep finding the reference's package."""
     global _finder
     import importlib
     import os
     if _finder is None:
         _finder = _AliasFinder()
         sys.meta_path.insert(0, _finder)
-    for name in DROPIN_NAMES:
+    if datasets:
+        _optional_names.add("datasets")
+    for name in DROPIN_NAMES + tuple(sorted(_optional_names)):
         stale = sys.modules.get(name)
         real = importlib.import_module(f"{__name__}.{name}")
         if stale is not None and stale is not real:

@@ -19,6 +19,7 @@
 //                     fixed-point coefficients (or "outside the rescaled image": zero padding);
 //   augment_normalize_kernel: one thread per output pixel, ny x nx taps (3 x 3 when up-scaling, 5 x 5 at scale 0.5).
 #include "common.h"
+#include "augment_shape.h"
 
 #define AUG_KMAX 9          // 2 * ceil(support) + 1 with support <= 4, i.e. down-scaling by at most 4
 #define AUG_ENT 12          // ints per table entry: first tap, count, AUG_KMAX coefficients, pad (48 B)
@@ -32,15 +33,23 @@ struct AugParams {      // one per image, 8 ints / floats = 32 B
     int crop_y, crop_x; // crop window origin in the canvas (H_start, W_start)
 };
 
-// grid (cdiv(crop, 256), 2, B); axis 0 = rows, 1 = columns
+// grid (cdiv(crop, 256), 2, B); axis 0 = rows, 1 = columns.  RAGGED: per-image source size and offset (augment_shape.h)
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void aug_coeff_kernel(const AugParams* __restrict__ params, int* __restrict__ tab, int Hs, int Ws,
-                                                         int crop) {
+                                                         int crop, const long long* __restrict__ offsets,
+                                                         const int* __restrict__ sizes, long src_bytes) {
     const int o = blockIdx.x * 256 + threadIdx.x, axis = blockIdx.y, b = blockIdx.z;
     if (o >= crop) return;
     const AugParams p = params[b];
-    const int in_size = axis ? Ws : Hs, out_size = axis ? p.rw : p.rh;
+    const AugShape sh = aug_shape<RAGGED>(b, Hs, Ws, offsets, sizes, src_bytes);
+    const int in_size = axis ? sh.W : sh.H, out_size = axis ? p.rw : p.rh;
     int r = o + (axis ? p.crop_x - p.pad_x : p.crop_y - p.pad_y);          // coordinate in the rescaled image
     int* e = tab + (((long)b * 2 + axis) * crop + o) * AUG_ENT;
+    if (RAGGED && !sh.ok) {                                                // image outside the packed buffer: POISONED,
+        e[0] = 0;                                                          // nothing of it is read
+        e[1] = -1;
+        return;
+    }
     if (r < 0 || r >= out_size) {
         e[0] = 0;
         e[1] = 0;                                                          // canvas padding
@@ -87,11 +96,21 @@ __device__ __forceinline__ int aug_clip8(int v) {
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void augment_normalize_kernel(const unsigned char* __restrict__ src, const int* __restrict__ tab,
                                                                  float* __restrict__ dst, int Hs, int Ws, int crop,
-                                                                 float m0, float m1, float m2, float s0, float s1, float s2) {
+                                                                 float m0, float m1, float m2, float s0, float s1, float s2,
+                                                                 const long long* __restrict__ offsets,
+                                                                 const int* __restrict__ sizes, long src_bytes) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (x >= crop || y >= crop) return;
+    if constexpr (RAGGED) {                                                // taps lie in [0, H) x [0, W) of a checked image
+        const AugShape sh = aug_shape<true>(b, Hs, Ws, offsets, sizes, src_bytes);
+        Ws = sh.W;
+        src += sh.off;
+    } else {
+        src += (long)b * Hs * Ws * 3;
+    }
     const int* ey = tab + (((long)b * 2 + 0) * crop + y) * AUG_ENT;       // one entry per wave
     const int* ex = tab + (((long)b * 2 + 1) * crop + x) * AUG_ENT;
     const int ymin = ey[0], ny = ey[1], xmin = ex[0], nx = ex[1];
@@ -101,7 +120,7 @@ __global__ __launch_bounds__(256) void augment_normalize_kernel(const unsigned c
     } else if (ny < 0 || nx < 0) {                                         // precondition in/out <= 4 violated (aug_coeff_kernel)
         v0 = v1 = v2 = __builtin_nanf("");
     } else {
-        const unsigned char* S = src + ((long)b * Hs * Ws + (long)ymin * Ws + xmin) * 3;
+        const unsigned char* S = src + ((long)ymin * Ws + xmin) * 3;
         int a0 = 1 << (AUG_PREC - 1), a1 = a0, a2 = a0;
         for (int j = 0; j < ny; ++j) {
             const unsigned char* row = S + (long)j * Ws * 3;
@@ -139,12 +158,58 @@ extern "C" int wc_augment_normalize(const void* src_u8, const void* params, floa
     WC_CHECK_ARG(src_u8 && params && dst && coeff_ws && mean3 && std3 && B > 0 && B <= 65535 && Hs > 0 && Ws > 0 && crop > 0,
                  "wc_augment_normalize: bad argument");
     WC_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "wc_augment_normalize: zero std");
-    hipLaunchKernelGGL(aug_coeff_kernel, dim3(wc_cdiv(crop, 256), 2, B), dim3(256), 0, (hipStream_t)stream,
-                       (const AugParams*)params, coeff_ws, Hs, Ws, crop);
+    hipLaunchKernelGGL(aug_coeff_kernel<false>, dim3(wc_cdiv(crop, 256), 2, B), dim3(256), 0, (hipStream_t)stream,
+                       (const AugParams*)params, coeff_ws, Hs, Ws, crop, nullptr, nullptr, 0L);
     WC_LAUNCH_CHECK("aug_coeff_kernel");
-    hipLaunchKernelGGL(augment_normalize_kernel, dim3(wc_cdiv(crop, 64), wc_cdiv(crop, 4), B), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned char*)src_u8, (const int*)coeff_ws, dst, Hs, Ws, crop, mean3[0], mean3[1], mean3[2],
-                       std3[0], std3[1], std3[2]);
+    hipLaunchKernelGGL(augment_normalize_kernel<false>, dim3(wc_cdiv(crop, 64), wc_cdiv(crop, 4), B), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned char*)src_u8, (const int*)coeff_ws, dst, Hs, Ws, crop, mean3[0], mean3[1],
+                       mean3[2], std3[0], std3[1], std3[2], nullptr, nullptr, 0L);
     WC_LAUNCH_CHECK("augment_normalize_kernel");
+    return WC_OK;
+}
+
+extern "C" int wc_augment_normalize_ragged(const void* src_u8, long src_bytes, const int64_t* offsets, const int* sizes,
+                                           const void* params, float* dst, int* coeff_ws, int B, int crop, const float* mean3,
+                                           const float* std3, void* stream) {
+    WC_CHECK_ARG(src_u8 && src_bytes >= 3 && offsets && sizes && params && dst && coeff_ws && mean3 && std3 && B > 0 && B <= 65535 &&
+                     crop > 0,
+                 "wc_augment_normalize_ragged: bad argument");
+    WC_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "wc_augment_normalize_ragged: zero std");
+    hipLaunchKernelGGL(aug_coeff_kernel<true>, dim3(wc_cdiv(crop, 256), 2, B), dim3(256), 0, (hipStream_t)stream,
+                       (const AugParams*)params, coeff_ws, 0, 0, crop, (const long long*)offsets, sizes, src_bytes);
+    WC_LAUNCH_CHECK("aug_coeff_kernel<ragged>");
+    hipLaunchKernelGGL(augment_normalize_kernel<true>, dim3(wc_cdiv(crop, 64), wc_cdiv(crop, 4), B), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned char*)src_u8, (const int*)coeff_ws, dst, 0, 0, crop, mean3[0], mean3[1],
+                       mean3[2], std3[0], std3[1], std3[2], (const long long*)offsets, sizes, src_bytes);
+    WC_LAUNCH_CHECK("augment_normalize_kernel<ragged>");
+    return WC_OK;
+}
+
+// aug=False path (datasets/voc.py:137-143, :247-249 without augmentation): normalize_img on the uint8 image itself.  numpy
+// evaluates (uint8 - float) / float in DOUBLE there and rounds once on the store into the float32 array; float32 arithmetic
+// differs from that in the last place for about half of the 768 (value, channel) pairs, hence double mean / std here.
+// grid cdiv(H * W, 256): one thread per pixel.
+__global__ __launch_bounds__(256) void normalize_u8_kernel(const unsigned char* __restrict__ src, const unsigned char* __restrict__ lab,
+                                                            float* __restrict__ dst, long long* __restrict__ dst_lab, long n,
+                                                            double m0, double m1, double m2, double s0, double s1, double s2) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dst[i] = (float)(((double)src[3 * i] - m0) / s0);
+    dst[n + i] = (float)(((double)src[3 * i + 1] - m1) / s1);
+    dst[2 * n + i] = (float)(((double)src[3 * i + 2] - m2) / s2);
+    if (lab) dst_lab[i] = lab[i];
+}
+
+extern "C" int wc_normalize_u8(const void* src_u8, const void* lab_u8, float* dst, int64_t* dst_label, int H, int W,
+                               const double* mean3, const double* std3, void* stream) {
+    WC_CHECK_ARG(src_u8 && dst && mean3 && std3 && H > 0 && W > 0 && H <= AUG_MAX_SIDE && W <= AUG_MAX_SIDE,
+                 "wc_normalize_u8: bad argument");
+    WC_CHECK_ARG((lab_u8 == nullptr) == (dst_label == nullptr), "wc_normalize_u8: lab_u8 and dst_label go together");
+    WC_CHECK_ARG(std3[0] != 0.0 && std3[1] != 0.0 && std3[2] != 0.0, "wc_normalize_u8: zero std");
+    const long n = (long)H * W;
+    hipLaunchKernelGGL(normalize_u8_kernel, dim3(wc_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)src_u8,
+                       (const unsigned char*)lab_u8, dst, (long long*)dst_label, n, mean3[0], mean3[1], mean3[2], std3[0], std3[1],
+                       std3[2]);
+    WC_LAUNCH_CHECK("normalize_u8_kernel");
     return WC_OK;
 }

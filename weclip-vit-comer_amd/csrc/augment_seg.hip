@@ -19,6 +19,7 @@
 //   segaug_gather_kernel one thread per output pixel: image taps -> photometric chain on the uint8 triple -> normalise;
 //                        label through the index tables
 #include "common.h"
+#include "augment_shape.h"
 
 #define SEG_KMAX 9          // as augment.hip: 2 * ceil(support) + 1 taps, down-scaling by at most 4
 #define SEG_ENT 12
@@ -148,15 +149,19 @@ __global__ __launch_bounds__(256) void seg_hsv8_kernel(const u8* __restrict__ sr
 
 // ---- geometry ----------------------------------------------------------------------------------------------------
 // grid (cdiv(CM, 256), 2, B).  idx[(b * 2 + axis) * CM + u]: source row / column of the label behind canvas coordinate u.
+// RAGGED: per-image source size and offset (augment_shape.h); an image outside the packed buffer is all padding here.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segaug_index_kernel(const SegAugParams* __restrict__ params, int* __restrict__ idx, int Hs,
-                                                            int Ws, int crop, int CM) {
+                                                            int Ws, int crop, int CM, const long long* __restrict__ offsets,
+                                                            const int* __restrict__ sizes, long src_bytes) {
     const int u = blockIdx.x * 256 + threadIdx.x, axis = blockIdx.y, b = blockIdx.z;
     if (u >= CM) return;
     const SegAugParams p = params[b];
-    const int in_size = axis ? Ws : Hs, out_size = axis ? p.rw : p.rh;
+    const AugShape sh = aug_shape<RAGGED>(b, Hs, Ws, offsets, sizes, src_bytes);
+    const int in_size = axis ? sh.W : sh.H, out_size = axis ? p.rw : p.rh;
     int r = u - (axis ? p.pad_x : p.pad_y);
     int v = -1;
-    if (r >= 0 && r < out_size && out_size <= CM) {
+    if (r >= 0 && r < out_size && out_size <= CM && sh.ok) {
         if (axis && p.flip) r = out_size - 1 - r;
         if (out_size == in_size) {
             v = r;
@@ -182,10 +187,12 @@ __device__ __forceinline__ void seg_candidate(const SegAugParams& p, const int* 
 
 // grid (cdiv(crop, SEG_SLAB), NC, B).  Label maps are piecewise constant, so a wave's 64 lanes would all hit one bin: every
 // thread folds SEG_RUN consecutive pixels into runs first (one LDS atomic per run), into its wave's private 256 bins.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segaug_hist_kernel(const u8* __restrict__ lab, const SegAugParams* __restrict__ params,
                                                            const int* __restrict__ cand, const int* __restrict__ idx,
                                                            int* __restrict__ hist, int Hs, int Ws, int crop, int CM, int NC,
-                                                           int ignore) {
+                                                           int ignore, const long long* __restrict__ offsets,
+                                                           const int* __restrict__ sizes, long src_bytes) {
     __shared__ int h[4][256];
     const int t = threadIdx.x, w = t >> 6, c = blockIdx.y, b = blockIdx.z;
     h[0][t] = h[1][t] = h[2][t] = h[3][t] = 0;
@@ -195,7 +202,14 @@ __global__ __launch_bounds__(256) void segaug_hist_kernel(const u8* __restrict__
     seg_candidate(p, cand, b, c, NC, crop, CM, cy, cx);
     const int* ty = idx + ((long)b * 2 + 0) * CM + cy;
     const int* tx = idx + ((long)b * 2 + 1) * CM + cx;
-    const u8* L = lab + (long)b * Hs * Ws;
+    if constexpr (RAGGED) {                                                // indices lie in [0, H) x [0, W) of a checked image
+        const AugShape sh = aug_shape<true>(b, Hs, Ws, offsets, sizes, src_bytes);
+        Ws = sh.W;
+        lab += sh.off / 3;
+    } else {
+        lab += (long)b * Hs * Ws;
+    }
+    const u8* L = lab;
     const int nseg = (crop + SEG_RUN - 1) / SEG_RUN, y0 = blockIdx.x * SEG_SLAB;
     for (int i = t; i < SEG_SLAB * nseg; i += 256) {
         const int y = y0 + i / nseg, xs = (i % nseg) * SEG_RUN;
@@ -281,15 +295,19 @@ __global__ __launch_bounds__(256) void segaug_select_kernel(const SegAugParams* 
 }
 
 // grid (cdiv(crop, 256), 2, B): augment.hip's aug_coeff_kernel with the crop origin read from sel
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segaug_coeff_kernel(const SegAugParams* __restrict__ params, const int* __restrict__ sel,
-                                                            int* __restrict__ tab, int Hs, int Ws, int crop, int CM) {
+                                                            int* __restrict__ tab, int Hs, int Ws, int crop, int CM,
+                                                            const long long* __restrict__ offsets, const int* __restrict__ sizes,
+                                                            long src_bytes) {
     const int o = blockIdx.x * 256 + threadIdx.x, axis = blockIdx.y, b = blockIdx.z;
     if (o >= crop) return;
     const SegAugParams p = params[b];
-    const int in_size = axis ? Ws : Hs, out_size = axis ? p.rw : p.rh;
+    const AugShape sh = aug_shape<RAGGED>(b, Hs, Ws, offsets, sizes, src_bytes);
+    const int in_size = axis ? sh.W : sh.H, out_size = axis ? p.rw : p.rh;
     int r = o + sel[b * 4 + axis] - (axis ? p.pad_x : p.pad_y);           // coordinate in the rescaled image
     int* e = tab + (((long)b * 2 + axis) * crop + o) * SEG_ENT;
-    if (p.rh < 1 || p.rw < 1 || p.rh > CM || p.rw > CM) {                  // record outside the checked preconditions: poison
+    if (p.rh < 1 || p.rw < 1 || p.rh > CM || p.rw > CM || !sh.ok) {        // record outside the checked preconditions: poison
         e[0] = 0;
         e[1] = -1;
         return;
@@ -341,19 +359,30 @@ __device__ __forceinline__ int seg_clip8(int v) {
 }
 
 // grid (cdiv(crop, 64), cdiv(crop, 4), B): one thread per output pixel
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void segaug_gather_kernel(const u8* __restrict__ src, const u8* __restrict__ lab,
                                                              const SegAugParams* __restrict__ params, const int* __restrict__ sel,
                                                              const int* __restrict__ idx, const int* __restrict__ tab,
                                                              float* __restrict__ dst, long long* __restrict__ dst_lab, int Hs, int Ws,
                                                              int crop, int CM, int ignore, float m0, float m1, float m2, float s0,
-                                                             float s1, float s2) {
+                                                             float s1, float s2, const long long* __restrict__ offsets,
+                                                             const int* __restrict__ sizes, long src_bytes) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (x >= crop || y >= crop) return;
+    if constexpr (RAGGED) {
+        const AugShape sh = aug_shape<true>(b, Hs, Ws, offsets, sizes, src_bytes);
+        Ws = sh.W;
+        src += sh.off;
+        lab += sh.off / 3;
+    } else {
+        src += (long)b * Hs * Ws * 3;
+        lab += (long)b * Hs * Ws;
+    }
     const SegAugParams p = params[b];
     const int cy = sel[b * 4], cx = sel[b * 4 + 1];                        // clamped into the canvas by segaug_select_kernel
     // label: pad -> flip -> NEAREST through the index tables
     const int iy = idx[((long)b * 2 + 0) * CM + cy + y], ix = idx[((long)b * 2 + 1) * CM + cx + x];
-    const int lv = lab[(long)b * Hs * Ws + (long)max(iy, 0) * Ws + max(ix, 0)];
+    const int lv = lab[(long)max(iy, 0) * Ws + max(ix, 0)];
     const long plane = (long)crop * crop;
     dst_lab[(long)b * plane + (long)y * crop + x] = (iy < 0 || ix < 0) ? ignore : lv;
 
@@ -365,7 +394,7 @@ __global__ __launch_bounds__(256) void segaug_gather_kernel(const u8* __restrict
     } else if (ny < 0 || nx < 0) {
         v0 = v1 = v2 = __builtin_nanf("");
     } else {
-        const u8* S = src + ((long)b * Hs * Ws + (long)ymin * Ws + xmin) * 3;
+        const u8* S = src + ((long)ymin * Ws + xmin) * 3;
         int a0 = 1 << (SEG_PREC - 1), a1 = a0, a2 = a0;
         for (int j = 0; j < ny; ++j) {
             const u8* row = S + (long)j * Ws * 3;
@@ -409,19 +438,22 @@ extern "C" int wc_seg_augment_workspace_ints(int B, int crop, int canvas_max, in
     return WC_OK;
 }
 
+template <bool RAGGED>
 static int seg_select_launch(const void* lab_u8, const void* params, const int* cand, int* sel, int* img_box, int* ws, int B, int Hs,
-                             int Ws, int crop, int CM, int NC, int ignore, hipStream_t st) {
+                             int Ws, int crop, int CM, int NC, int ignore, hipStream_t st, const long long* offsets,
+                             const int* sizes, long src_bytes) {
     int* idx = ws;
     int* hist = ws + (long)B * 2 * CM;
-    hipLaunchKernelGGL(segaug_index_kernel, dim3(wc_cdiv(CM, 256), 2, B), dim3(256), 0, st, (const SegAugParams*)params, idx, Hs, Ws,
-                       crop, CM);
+    hipLaunchKernelGGL(segaug_index_kernel<RAGGED>, dim3(wc_cdiv(CM, 256), 2, B), dim3(256), 0, st, (const SegAugParams*)params, idx,
+                       Hs, Ws, crop, CM, offsets, sizes, src_bytes);
     WC_LAUNCH_CHECK("segaug_index_kernel");
     if (hipMemsetAsync(hist, 0, sizeof(int) * (size_t)B * NC * 256, st) != hipSuccess) {
         wc_set_error("wc_seg_augment: hipMemsetAsync failed");
         return WC_ERR_HIP;
     }
-    hipLaunchKernelGGL(segaug_hist_kernel, dim3(wc_cdiv(crop, SEG_SLAB), NC, B), dim3(256), 0, st, (const u8*)lab_u8,
-                       (const SegAugParams*)params, cand, (const int*)idx, hist, Hs, Ws, crop, CM, NC, ignore);
+    hipLaunchKernelGGL(segaug_hist_kernel<RAGGED>, dim3(wc_cdiv(crop, SEG_SLAB), NC, B), dim3(256), 0, st, (const u8*)lab_u8,
+                       (const SegAugParams*)params, cand, (const int*)idx, hist, Hs, Ws, crop, CM, NC, ignore, offsets, sizes,
+                       src_bytes);
     WC_LAUNCH_CHECK("segaug_hist_kernel");
     hipLaunchKernelGGL(segaug_select_kernel, dim3(B), dim3(256), 0, st, (const SegAugParams*)params, cand, (const int*)hist, sel,
                        img_box, crop, CM, NC, ignore);
@@ -433,8 +465,29 @@ extern "C" int wc_seg_crop_select(const void* lab_u8, const void* params, const 
                                   int Hs, int Ws, int crop, int canvas_max, int n_cand, int ignore_index, void* stream) {
     WC_CHECK_ARG(lab_u8 && params && cand && sel && img_box && ws, "wc_seg_crop_select: bad argument");
     if (int rc = seg_check_shape("wc_seg_crop_select", B, Hs, Ws, crop, canvas_max, n_cand, ignore_index)) return rc;
-    return seg_select_launch(lab_u8, params, cand, sel, img_box, ws, B, Hs, Ws, crop, canvas_max, n_cand, ignore_index,
-                             (hipStream_t)stream);
+    return seg_select_launch<false>(lab_u8, params, cand, sel, img_box, ws, B, Hs, Ws, crop, canvas_max, n_cand, ignore_index,
+                                    (hipStream_t)stream, nullptr, nullptr, 0L);
+}
+
+template <bool RAGGED>
+static int seg_augment_launch(const void* src_u8, const void* lab_u8, const void* params, const int* cand, float* dst,
+                              int64_t* dst_label, int* sel, int* img_box, int* ws, int B, int Hs, int Ws, int crop, int CM, int n_cand,
+                              int ignore_index, const float* mean3, const float* std3, hipStream_t st, const long long* offsets,
+                              const int* sizes, long src_bytes) {
+    if (int rc = seg_select_launch<RAGGED>(lab_u8, params, cand, sel, img_box, ws, B, Hs, Ws, crop, CM, n_cand, ignore_index, st,
+                                           offsets, sizes, src_bytes))
+        return rc;
+    const int* idx = ws;
+    int* tab = ws + (long)B * 2 * CM + (long)B * n_cand * 256;
+    hipLaunchKernelGGL(segaug_coeff_kernel<RAGGED>, dim3(wc_cdiv(crop, 256), 2, B), dim3(256), 0, st, (const SegAugParams*)params,
+                       (const int*)sel, tab, Hs, Ws, crop, CM, offsets, sizes, src_bytes);
+    WC_LAUNCH_CHECK("segaug_coeff_kernel");
+    hipLaunchKernelGGL(segaug_gather_kernel<RAGGED>, dim3(wc_cdiv(crop, 64), wc_cdiv(crop, 4), B), dim3(256), 0, st, (const u8*)src_u8,
+                       (const u8*)lab_u8, (const SegAugParams*)params, (const int*)sel, idx, (const int*)tab, dst,
+                       (long long*)dst_label, Hs, Ws, crop, CM, ignore_index, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2],
+                       offsets, sizes, src_bytes);
+    WC_LAUNCH_CHECK("segaug_gather_kernel");
+    return WC_OK;
 }
 
 extern "C" int wc_seg_augment(const void* src_u8, const void* lab_u8, const void* params, const int* cand, float* dst,
@@ -444,19 +497,21 @@ extern "C" int wc_seg_augment(const void* src_u8, const void* lab_u8, const void
                  "wc_seg_augment: bad argument");
     if (int rc = seg_check_shape("wc_seg_augment", B, Hs, Ws, crop, canvas_max, n_cand, ignore_index)) return rc;
     WC_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "wc_seg_augment: zero std");
-    hipStream_t st = (hipStream_t)stream;
-    const int CM = canvas_max;
-    if (int rc = seg_select_launch(lab_u8, params, cand, sel, img_box, ws, B, Hs, Ws, crop, CM, n_cand, ignore_index, st)) return rc;
-    const int* idx = ws;
-    int* tab = ws + (long)B * 2 * CM + (long)B * n_cand * 256;
-    hipLaunchKernelGGL(segaug_coeff_kernel, dim3(wc_cdiv(crop, 256), 2, B), dim3(256), 0, st, (const SegAugParams*)params,
-                       (const int*)sel, tab, Hs, Ws, crop, CM);
-    WC_LAUNCH_CHECK("segaug_coeff_kernel");
-    hipLaunchKernelGGL(segaug_gather_kernel, dim3(wc_cdiv(crop, 64), wc_cdiv(crop, 4), B), dim3(256), 0, st, (const u8*)src_u8,
-                       (const u8*)lab_u8, (const SegAugParams*)params, (const int*)sel, idx, (const int*)tab, dst,
-                       (long long*)dst_label, Hs, Ws, crop, CM, ignore_index, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
-    WC_LAUNCH_CHECK("segaug_gather_kernel");
-    return WC_OK;
+    return seg_augment_launch<false>(src_u8, lab_u8, params, cand, dst, dst_label, sel, img_box, ws, B, Hs, Ws, crop, canvas_max,
+                                     n_cand, ignore_index, mean3, std3, (hipStream_t)stream, nullptr, nullptr, 0L);
+}
+
+extern "C" int wc_seg_augment_ragged(const void* src_u8, const void* lab_u8, long src_bytes, const int64_t* offsets,
+                                     const int* sizes, const void* params, const int* cand, float* dst, int64_t* dst_label, int* sel,
+                                     int* img_box, int* ws, int B, int crop, int canvas_max, int n_cand, int ignore_index,
+                                     const float* mean3, const float* std3, void* stream) {
+    WC_CHECK_ARG(src_u8 && lab_u8 && src_bytes >= 3 && offsets && sizes && params && cand && dst && dst_label && sel && img_box && ws &&
+                     mean3 && std3,
+                 "wc_seg_augment_ragged: bad argument");
+    if (int rc = seg_check_shape("wc_seg_augment_ragged", B, 1, 1, crop, canvas_max, n_cand, ignore_index)) return rc;
+    WC_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "wc_seg_augment_ragged: zero std");
+    return seg_augment_launch<true>(src_u8, lab_u8, params, cand, dst, dst_label, sel, img_box, ws, B, 0, 0, crop, canvas_max, n_cand,
+                                    ignore_index, mean3, std3, (hipStream_t)stream, (const long long*)offsets, sizes, src_bytes);
 }
 
 extern "C" int wc_hsv8_convert(const void* src_u8, void* dst_u8, long n, int inverse, void* stream) {

@@ -138,6 +138,63 @@ class DeviceAugment:
                                      (ctypes.c_float * 3)(*self.mean), (ctypes.c_float * 3)(*self.std), L.stream())
         return out
 
+    def check_ragged(self, params, sizes):
+        """Host-side precondition of the kernels for host-resident records and a list of (H, W): raises, never poisons."""
+        for b, (H, W) in enumerate(sizes):
+            rh, rw = int(params[b, 2]), int(params[b, 3])
+            if rh < 1 or rw < 1 or H > 4 * rh or W > 4 * rw:
+                raise RuntimeError(f"DeviceAugment: image {b} ({H}x{W} -> {rh}x{rw}): rescaled size must be >= 1 and "
+                                   "down-scaling at most 4x")
+
+    def ragged(self, src_u8, offsets, sizes, params):
+        """A batch of images of different sizes (csrc/augment.hip, wc_augment_normalize_ragged): src_u8 flat uint8 CUDA, the
+        images HWC back to back; offsets (B) int64 / sizes (B,2) int32 {H, W} / params (B,8) int32 CUDA tensors (views of one
+        buffer are fine).  -> (B,3,crop,crop) f32 on the current stream; nothing synchronises with the host."""
+        import ctypes
+        from . import _lib as L
+        L.require_gpu()
+        B = int(offsets.shape[0])
+        if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or tuple(sizes.shape) != (B, 2) or tuple(params.shape) != (B, 8):
+            raise RuntimeError("DeviceAugment.ragged expects a flat uint8 source, (B) offsets, (B,2) sizes, (B,8) params")
+        out = torch.empty(B, 3, self.crop, self.crop, device=src_u8.device, dtype=torch.float32)
+        n = ctypes.c_long(0)
+        L.lib().wc_augment_workspace_ints(B, self.crop, ctypes.byref(n))
+        if self._ws is None or self._ws.numel() < n.value or self._ws.device != src_u8.device:
+            self._ws = torch.empty(n.value, device=src_u8.device, dtype=torch.int32)
+        L.lib().wc_augment_normalize_ragged(L.ptr(src_u8, torch.uint8, "src"), src_u8.numel(), L.ptr(offsets, torch.int64, "offsets"),
+                                            L.ptr(sizes, torch.int32, "sizes"), L.ptr(params, torch.int32, "params"), L.ptr(out),
+                                            L.ptr(self._ws, torch.int32), B, self.crop, (ctypes.c_float * 3)(*self.mean),
+                                            (ctypes.c_float * 3)(*self.std), L.stream())
+        return out
+
+    @staticmethod
+    def img_box(draw, crop):
+        """`img_box` of random_crop (datasets/transforms.py:162-166) from one draw_one() tuple, int16 like the reference's."""
+        import numpy as np
+        _, _, rh, rw, pad_y, pad_x, crop_y, crop_x = draw
+        return np.asarray([max(pad_y - crop_y, 0), min(crop_y + crop, pad_y + rh), max(pad_x - crop_x, 0),
+                           min(crop_x + crop, pad_x + rw)], dtype=np.int16)
+
+
+def normalize_u8(image_u8, label_u8=None, mean=MEAN, std=STD):
+    """The aug=False path on the device (wc_normalize_u8): image (H,W,3) uint8 CUDA -> (3,H,W) f32 `normalize_img`
+    (datasets/transforms.py:8-15, evaluated in double precision and rounded once, as numpy does for a uint8 image) and, if
+    given, label (H,W) uint8 -> int64.  -> image or (image, label)."""
+    import ctypes
+    from . import _lib as L
+    L.require_gpu()
+    H, W, C = image_u8.shape
+    if C != 3 or image_u8.dtype != torch.uint8:
+        raise RuntimeError("normalize_u8 expects a uint8 (H, W, 3) image")
+    if label_u8 is not None and (label_u8.dtype != torch.uint8 or tuple(label_u8.shape) != (H, W)):
+        raise RuntimeError("normalize_u8 expects a uint8 (H, W) label map of the image's size")
+    out = torch.empty(3, H, W, device=image_u8.device, dtype=torch.float32)
+    lab = None if label_u8 is None else torch.empty(H, W, device=image_u8.device, dtype=torch.int64)
+    L.lib().wc_normalize_u8(L.ptr(image_u8, torch.uint8, "image"), L.ptr(label_u8, torch.uint8, "label"), L.ptr(out),
+                            L.ptr(lab, torch.int64, "label out"), H, W, (ctypes.c_double * 3)(*[float(v) for v in mean]),
+                            (ctypes.c_double * 3)(*[float(v) for v in std]), L.stream())
+    return out if lab is None else (out, lab)
+
 
 class DeviceSegAugment:
     """The reference's label-aware train-time augmentation of the fully supervised variant (`VOC12SegDataset.__transforms`,
@@ -295,5 +352,49 @@ class DeviceSegAugment:
                                L.ptr(lab, torch.int64), L.ptr(sel), L.ptr(box), L.ptr(self._ws, torch.int32), B, H, W, self.crop,
                                cm, self.n_cand, self.ignore_index, (ctypes.c_float * 3)(*self.mean),
                                (ctypes.c_float * 3)(*self.std), L.stream())
+        self.sel = sel
+        return out, lab, box
+
+    def check_ragged(self, rec, cand, sizes):
+        """Host-side preconditions for host-resident records and a list of (H, W); -> canvas_max of the batch."""
+        cm = self.crop
+        for b, (H, W) in enumerate(sizes):
+            rh, rw = int(rec[b, 2]), int(rec[b, 3])
+            if rh < 1 or rw < 1 or H > 4 * rh or W > 4 * rw:
+                raise RuntimeError(f"DeviceSegAugment: image {b} ({H}x{W} -> {rh}x{rw}): rescaled size must be >= 1 and "
+                                   "down-scaling at most 4x")
+            lim = torch.tensor([max(rh, self.crop) - self.crop, max(rw, self.crop) - self.crop], dtype=cand.dtype)
+            if int(cand[b].min()) < 0 or bool((cand[b] > lim).any()):
+                raise RuntimeError("DeviceSegAugment: candidate box outside the padded canvas")
+            cm = max(cm, rh, rw)
+        return cm
+
+    def ragged(self, src_u8, lab_u8, offsets, sizes, rec, cand, canvas_max):
+        """A batch of images of different sizes (csrc/augment_seg.hip, wc_seg_augment_ragged): src_u8 flat uint8 CUDA, the
+        images HWC back to back, lab_u8 their label maps in the same order (map b at byte offsets[b] / 3); offsets (B) int64,
+        sizes (B,2) int32, rec (B,16) int32, cand (B,n_cand,2) int32 CUDA tensors; canvas_max: max(crop, rh, rw) over the
+        batch (check_ragged).  -> (image, label, img_box) as __call__, on the current stream, without host synchronisation."""
+        import ctypes
+        from . import _lib as L
+        L.require_gpu()
+        B, dev = int(offsets.shape[0]), src_u8.device
+        if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or lab_u8.dim() != 1 or 3 * lab_u8.numel() < src_u8.numel():
+            raise RuntimeError("DeviceSegAugment.ragged expects flat uint8 buffers, the labels one third of the images")
+        if tuple(sizes.shape) != (B, 2) or tuple(rec.shape) != (B, 16) or tuple(cand.shape) != (B, self.n_cand, 2):
+            raise RuntimeError("DeviceSegAugment.ragged: (B,2) sizes, (B,16) records, (B,n_cand,2) candidates")
+        out = torch.empty(B, 3, self.crop, self.crop, device=dev, dtype=torch.float32)
+        lab = torch.empty(B, self.crop, self.crop, device=dev, dtype=torch.int64)
+        sel = torch.empty(B, 4, device=dev, dtype=torch.int32)
+        box = torch.empty(B, 4, device=dev, dtype=torch.int32)
+        n = ctypes.c_long(0)
+        L.lib().wc_seg_augment_workspace_ints(B, self.crop, int(canvas_max), self.n_cand, ctypes.byref(n))
+        if self._ws is None or self._ws.numel() < n.value or self._ws.device != dev:
+            self._ws = torch.empty(n.value, device=dev, dtype=torch.int32)
+        L.lib().wc_seg_augment_ragged(L.ptr(src_u8, torch.uint8, "images"), L.ptr(lab_u8, torch.uint8, "labels"), src_u8.numel(),
+                                      L.ptr(offsets, torch.int64, "offsets"), L.ptr(sizes, torch.int32, "sizes"),
+                                      L.ptr(rec, torch.int32, "params"), L.ptr(cand, torch.int32, "candidates"), L.ptr(out),
+                                      L.ptr(lab, torch.int64), L.ptr(sel), L.ptr(box), L.ptr(self._ws, torch.int32), B, self.crop,
+                                      int(canvas_max), self.n_cand, self.ignore_index, (ctypes.c_float * 3)(*self.mean),
+                                      (ctypes.c_float * 3)(*self.std), L.stream())
         self.sel = sel
         return out, lab, box
