@@ -680,6 +680,23 @@ int wc_cam_scale_resize_f16(const float* cam, const int* sizes, const int64_t* o
 int wc_cam_resize_f32(const float* cam, const int* sizes, const int64_t* offsets, float* out, long out_elems, int P, int gh, int gw,
                       int max_pixels, void* stream);
 
+/* ---- training driver: validation histograms and the step metric (csrc/trainlog.hip) ----------- */
+/* wc_val_pair_hist: one validated image of scripts/dist_clip_voc.py:71-102 in one launch.  seg (C,Hs,Ws) f32 low-resolution
+ *   logits, cam (Hl,Wl) int64 or NULL, gt (Hl,Wl) int64.  Over the pixels with 0 <= gt < nc:
+ *   seg_hist[gt*nc + p] += 1 with p = argmax_c bilinear(seg)[c] (align_corners=False, scale = in / out, first maximum wins:
+ *   the value wc_resize_argmax writes, which is never stored here) and, when cam is given, cam_hist[gt*nc + cam] += 1.
+ *   A p or cam value outside [0, nc) is skipped in its own histogram and sets flag[0] (wc_confusion_hist's contract).
+ *   seg_hist / cam_hist (nc,nc) int64, accumulated with integer atomics (per-workgroup LDS histograms while both fit in
+ *   64 KiB, global atomics otherwise); cam_hist may be NULL when cam is.  nc <= 4096.
+ * wc_label_match_count: the pseudo_seg_mAcc of :274-277.  seg (B,C,Hs,Ws) f32, label (B,H,W) int64 (255 = ignore, which no
+ *   arg-max equals).  counts int64[2] is OVERWRITTEN: counts[0] = #pixels with argmax_c bilinear(seg)[c] == label,
+ *   counts[1] = B*H*W.  The entry zeroes counts on `stream` and launches one kernel: no allocation, no host read, so it may
+ *   be called while `stream` is being captured into a HIP graph. */
+int wc_val_pair_hist(const float* seg, const long* cam, const long* gt, long* seg_hist, long* cam_hist, int* flag, int C, int Hs,
+                     int Ws, int Hl, int Wl, int nc, void* stream);
+int wc_label_match_count(const float* seg, const long* label, long* counts, int B, int C, int Hs, int Ws, int H, int W,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,450 @@
+"""The training driver: `train()` and `validate()` of the reference's scripts (scripts/dist_clip_voc.py:71-102, 137-296,
+scripts/dist_clip_coco.py) around this package's graph-replayed step.
+
+    python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
+        [--dataset voc|coco] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
+
+The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
+into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is counted by `wc_label_match_count`
+(csrc/trainlog.hip) inside the captured step; every `log_iters` ONE read fetches both.  Validation is `validate.Validator`.
+Under `python -m torch.distributed.run` every rank trains on its share of each epoch (DeviceLoader rank / world), gradients
+are averaged through `GradBucket`, every rank validates its share of the images, and rank 0 alone logs and saves.
+
+Two optional keys extend the configuration, both under `clip_init`: `text_features` (a torch file holding {"bg", "fg"}: the
+zero-shot text rows, for a machine without the reference checkout that `--reference_root` names) and `comer` (bool).
+"""
+import argparse
+import datetime
+import json
+import logging
+import math
+import os
+import random
+import re
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+from .train_step import TrainStep, make_optimizer
+
+LOG = logging.getLogger("weclip.train")
+LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, pseudo_seg_loss: %.4f, attn_loss: %.4f, pseudo_seg_mAcc: %.4f"   # :280
+SAVE_AFTER = {"voc": 26000, "coco": 40000}              # dist_clip_voc.py:288, dist_clip_coco.py:287
+MODEL_FILE, STATE_FILE = "WeCLIP_model_iter_%d.pth", "train_state_iter_%d.pth"
+_SCI = re.compile(r"^[+-]?(\d+\.?\d*|\.\d+)[eE][+-]?\d+$")
+
+
+# ---------------------------------------------------------------------------------------------- configuration
+class Config(dict):
+    """A dict with attribute access (`cfg.train.max_iters`), the part of OmegaConf the reference's scripts use."""
+
+    def __getattr__(self, key):
+        try:
+            return self[key]
+        except KeyError:
+            raise AttributeError(key) from None
+
+    def __setattr__(self, key, value):
+        self[key] = value
+
+
+def _wrap(v):
+    if isinstance(v, dict):
+        return Config((k, _wrap(x)) for k, x in v.items())
+    if isinstance(v, (list, tuple)):
+        return [_wrap(x) for x in v]
+    if isinstance(v, str) and _SCI.match(v.strip()):    # YAML 1.1 (PyYAML) reads `2e-4` / `1e-6` as strings: it wants a dot
+        return float(v)
+    return v
+
+
+def load_config(path, crop_size=None, work_dir=None):
+    """The reference's YAML -> Config.  Numbers spelt without a dot in the mantissa (`2e-4`) come out as floats; crop_size /
+    work_dir override `dataset.crop_size` / `work_dir.dir` as the reference's command line does (:302-306)."""
+    import yaml
+    with open(path) as f:
+        cfg = _wrap(yaml.safe_load(f))
+    if crop_size is not None:
+        cfg.dataset.crop_size = int(crop_size)
+    if work_dir is not None:
+        cfg.work_dir.dir = work_dir
+    return cfg
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m weclip_vit_comer_amd.train", description=__doc__.split("\n\n")[0])
+    p.add_argument("--config", type=str, required=True, help="the reference's YAML (configs/voc_attn_reg.yaml, coco_attn_reg.yaml)")
+    p.add_argument("--seg_detach", action="store_true", help="accepted and ignored, as in the reference")
+    p.add_argument("--work_dir", default=None, type=str)
+    p.add_argument("--radius", default=8, type=int)
+    p.add_argument("--crop_size", default=320, type=int)
+    p.add_argument("--dataset", choices=("voc", "coco"), default="voc")
+    p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
+    p.add_argument("--graph", action=argparse.BooleanOptionalAction, default=True, help="HIP-graph replay of the step")
+    p.add_argument("--threads", type=int, default=8, help="decode threads of the loaders")
+    p.add_argument("--prefetch", type=int, default=2)
+    p.add_argument("--max_iters", type=int, default=None, help="overrides train.max_iters")
+    p.add_argument("--save_after", type=int, default=None, help="checkpoints are written past this iteration (voc 26000, coco 40000)")
+    p.add_argument("--resume", type=str, default=None, help="a WeCLIP_model_iter_N.pth; its train_state_iter_N.pth is loaded with it")
+    return p
+
+
+def prepare_work_dir(cfg, timestamp=None, create=True):
+    """The tree of :308-318: <dir>/<ckpt_dir>/<timestamp>, <dir>/<pred_dir>, <dir>/<tb_logger_dir>/<timestamp>; returns the
+    path of <dir>/<timestamp>.log.  create=False (ranks other than 0) only resolves the names."""
+    timestamp = timestamp or "{0:%Y-%m-%d-%H-%M}".format(datetime.datetime.now())
+    wd = cfg.work_dir
+    wd.ckpt_dir = os.path.join(wd.dir, wd.ckpt_dir, timestamp)
+    wd.pred_dir = os.path.join(wd.dir, wd.pred_dir)
+    wd.tb_logger_dir = os.path.join(wd.dir, wd.tb_logger_dir, timestamp)
+    if create:
+        for d in (wd.ckpt_dir, wd.pred_dir, wd.tb_logger_dir):
+            os.makedirs(d, exist_ok=True)
+    return os.path.join(wd.dir, timestamp + ".log")
+
+
+def checkpoint_paths(ckpt_dir, n_iter):
+    """(model file in the reference's format, the training state beside it)."""
+    return os.path.join(ckpt_dir, MODEL_FILE % n_iter), os.path.join(ckpt_dir, STATE_FILE % n_iter)
+
+
+def state_path_of(model_path):
+    """WeCLIP_model_iter_N.pth -> its sibling train_state_iter_N.pth."""
+    d, name = os.path.split(model_path)
+    m = re.match(r"^WeCLIP_model_iter_(\d+)\.pth$", name)
+    if not m:
+        raise ValueError(f"--resume wants a {MODEL_FILE % 0}-style file name, got {name}")
+    return os.path.join(d, STATE_FILE % int(m.group(1)))
+
+
+def format_log_line(n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc):
+    return LOG_FORMAT % (n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc)
+
+
+def strict_json(v):
+    """Non-finite floats -> None, recursively: `json.dumps` would write them as the bare tokens NaN / Infinity, which strict
+    JSON readers refuse.  (A window's loss IS NaN when a batch's pseudo labels hold no foreground pixel, as in the reference.)"""
+    if isinstance(v, dict):
+        return {k: strict_json(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [strict_json(x) for x in v]
+    if isinstance(v, float) and not math.isfinite(v):
+        return None
+    return v
+
+
+def append_metrics(path, record):
+    with open(path, "a") as f:
+        f.write(json.dumps(strict_json(record), allow_nan=False) + "\n")
+
+
+def read_metrics(path):
+    with open(path) as f:
+        return [json.loads(line) for line in f if line.strip()]
+
+
+def setup_seed(seed):
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed_all(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+    torch.backends.cudnn.deterministic = True
+
+
+def setup_logger(filename=None):
+    """:44-56, on this module's logger: the file and the console."""
+    fmt = logging.Formatter("%(asctime)s - %(filename)s - %(levelname)s: %(message)s")
+    LOG.setLevel(logging.INFO)
+    for h in [logging.StreamHandler()] + ([logging.FileHandler(filename, mode="w")] if filename else []):
+        h.setFormatter(fmt)
+        LOG.addHandler(h)
+
+
+def cal_eta(time0, cur_iter, total_iter):
+    """:59-68."""
+    now = datetime.datetime.now().replace(microsecond=0)
+    delta = now - time0
+    eta = delta * ((total_iter - cur_iter) / float(cur_iter))
+    fin = now + eta
+    return str(delta), str(fin.replace(microsecond=0) - now)
+
+
+# ---------------------------------------------------------------------------------------------- the step
+class LoggedTrainStep(TrainStep):
+    """TrainStep whose losses() also counts, on the device, the pixels where the up-sampled logits' arg-max equals the
+    pseudo label (`counts` int64[2] = [matches, pixels], overwritten by every step).  The launch sits between the parent's
+    loss kernels and the backward, so in graph mode it is part of the captured step; the returned losses are the parent's."""
+
+    def __init__(self, model, *args, **kw):
+        super().__init__(model, *args, **kw)
+        self.counts = torch.zeros(2, device=next(model.parameters()).device, dtype=torch.int64)
+
+    def losses(self, seg, cam, attn_pred):
+        out = super().losses(seg, cam, attn_pred)
+        if seg.is_cuda:
+            from .validate import label_match_count
+            label_match_count(seg.detach().float().contiguous(), cam.long().contiguous(), self.counts)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- the driver
+class Trainer:
+    """cfg: load_config(); args: build_parser().parse_args().  model: a ready WeCLIP instead of the one built from
+    cfg.clip_init (embedding, tests).  rank_dump_dir: every rank writes `rank<r>.pth` (trainable parameters, iteration,
+    model.iter_num, the validation histograms) there at the end of fit() -- a cross-rank check, not part of the work_dir."""
+
+    seed = 1                                             # setup_seed(1), :322
+
+    def __init__(self, cfg, args, model=None, rank_dump_dir=None, timestamp=None):
+        from . import _lib as L
+        from .datasets import DeviceLoader
+        from .validate import Validator
+        L.require_gpu()
+        self.cfg, self.args, self.rank_dump_dir = cfg, args, rank_dump_dir
+        ddp = dist.is_available() and dist.is_initialized()
+        self.rank, self.world = (dist.get_rank(), dist.get_world_size()) if ddp else (0, 1)
+        self.kind = getattr(args, "dataset", "voc")
+        self.max_iters = int(args.max_iters if getattr(args, "max_iters", None) is not None else cfg.train.max_iters)
+        self.save_after = int(args.save_after if getattr(args, "save_after", None) is not None else SAVE_AFTER[self.kind])
+        self.log_path = prepare_work_dir(cfg, timestamp, create=self.rank == 0)
+        self.metrics_path = os.path.join(cfg.work_dir.dir, "metrics.jsonl")
+        self.val_metrics_path = os.path.join(cfg.work_dir.dir, "val_metrics.jsonl")
+        setup_seed(self.seed)
+
+        ds = cfg.dataset
+        if self.kind == "voc":
+            from .datasets.voc import VOC12ClsDataset as ClsDataset, VOC12SegDataset as SegDataset
+            val_stage = "train"                          # dist_clip_voc.py:162
+        else:
+            from .datasets.coco import CocoClsDataset as ClsDataset, CocoSegDataset as SegDataset
+            val_stage = "val"                            # dist_clip_coco.py:163
+        self.train_dataset = ClsDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.train.split, stage="train",
+                                        aug=True, resize_range=ds.resize_range, rescale_range=ds.rescale_range,
+                                        crop_size=ds.crop_size, img_fliplr=True, ignore_index=ds.ignore_index,
+                                        num_classes=ds.num_classes)
+        self.val_dataset = SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.val.split, stage=val_stage,
+                                      aug=False, ignore_index=ds.ignore_index, num_classes=ds.num_classes)
+        threads, prefetch = getattr(args, "threads", 8), getattr(args, "prefetch", 2)
+        self.train_loader = DeviceLoader(self.train_dataset, batch_size=cfg.train.samples_per_gpu, shuffle=True, drop_last=True,
+                                         seed=self.seed, rank=self.rank, world=self.world, threads=threads, prefetch=prefetch)
+        self.val_loader = DeviceLoader(self.val_dataset, batch_size=1, shuffle=False, rank=self.rank, world=self.world,
+                                       threads=threads, prefetch=prefetch)
+        # decided from the global sizes, so that under DP every rank takes the same branch (the smallest share is n // world)
+        if len(self.train_dataset) // self.world < int(cfg.train.samples_per_gpu):
+            raise RuntimeError("Trainer: the training split holds fewer images than one batch per rank")
+
+        self.model = model if model is not None else self.build_model()
+        self.model.train()
+        opt, sch = cfg.optimizer, cfg.scheduler
+        self.opt = make_optimizer(self.model, lr=float(opt.learning_rate), weight_decay=float(opt.weight_decay),
+                                  betas=tuple(float(b) for b in opt.betas), warmup_iter=int(sch.warmup_iter),
+                                  max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power))
+        self.step = LoggedTrainStep(self.model, self.opt, radius=getattr(args, "radius", 8), ignore_index=ds.ignore_index,
+                                    graph=bool(getattr(args, "graph", True)))
+        self.validator = Validator(self.model, ds.num_classes, self.rank, self.world)
+        dev = next(self.model.parameters()).device
+        self.acc = torch.zeros(3, device=dev, dtype=torch.float32)      # window sums of (loss, seg_loss, attn_loss)
+        self.window = 0                                                 # steps in the window (host)
+        self.n_iter = 0
+        self.time0 = datetime.datetime.now().replace(microsecond=0)
+        self._batches = None
+        self.writer = None
+        if self.rank == 0:
+            try:
+                from torch.utils.tensorboard import SummaryWriter
+                self.writer = SummaryWriter(cfg.work_dir.tb_logger_dir)
+            except ImportError:
+                pass
+        if getattr(args, "resume", None):
+            self.resume(args.resume)
+
+    def build_model(self):
+        cfg, args = self.cfg, self.args
+        if getattr(args, "reference_root", None):
+            from . import install_dropin
+            install_dropin(reference_root=args.reference_root)
+        if self.kind == "voc":
+            from .WeCLIP_model.model_attn_aff_voc import WeCLIP
+        else:
+            from .WeCLIP_model.model_attn_aff_coco import WeCLIP
+        ci = cfg.clip_init
+        text = None
+        if ci.get("text_features"):
+            rows = torch.load(ci.text_features, map_location="cuda")
+            text = (rows["bg"].float(), rows["fg"].float())
+        return WeCLIP(num_classes=cfg.dataset.num_classes, clip_model=ci.clip_pretrain_path, embedding_dim=ci.embedding_dim,
+                      in_channels=list(ci.in_channels), dataset_root_path=cfg.dataset.root_dir, device="cuda", text_features=text,
+                      comer=bool(ci.get("comer", False)))
+
+    # ---- one iteration --------------------------------------------------------------------------------------------
+    def _next_batch(self):
+        """Endless over epochs (:240-244): every pass over the DeviceLoader is one epoch and moves on to the next."""
+        while True:
+            if self._batches is None:
+                self._batches = iter(self.train_loader)
+            try:
+                return next(self._batches)
+            except StopIteration:
+                self._batches = None
+
+    def step_once(self):
+        """One training iteration -> the step's (loss, seg_loss, attn_loss) device scalars.  No host read."""
+        from .datasets import labels_from_onehot
+        _, inputs, _, _ = self._next_batch()
+        labels = labels_from_onehot(self.train_loader.last_cls_labels)      # the host copy: graph mode needs explicit labels
+        out = self.step(inputs, labels=labels)
+        self.acc.add_(torch.stack(out))
+        self.window += 1
+        self.n_iter += 1
+        return out
+
+    def log(self):
+        """The log line of :269-282 for the window since the last call: ONE device-to-host read (loss sums + counts).
+        pseudo_seg_mAcc is the LAST step's, as the reference's.  Needs at least one step since the last call."""
+        if self.window == 0:
+            raise RuntimeError("Trainer.log: no step since the last log line (there is no window to average)")
+        host = torch.cat([self.acc.double(), self.step.counts.double()]).cpu().tolist() if self.rank == 0 else None
+        self.acc.zero_()
+        steps, self.window = self.window, 0
+        if host is None:
+            return None
+        rec = {"iter": self.n_iter, "lr": self.opt.param_groups[0]["lr"], "seg_loss": host[1] / steps,
+               "attn_loss": host[2] / steps, "pseudo_seg_mAcc": host[3] / host[4]}
+        delta, eta = cal_eta(self.time0, max(self.n_iter, 1), self.max_iters)
+        LOG.info(format_log_line(rec["iter"], delta, eta, rec["lr"], rec["seg_loss"], rec["attn_loss"], rec["pseudo_seg_mAcc"]))
+        append_metrics(self.metrics_path, rec)
+        if self.writer is not None:
+            self.writer.add_scalars("train/loss", {"seg_loss": rec["seg_loss"], "attn_loss": rec["attn_loss"]}, global_step=self.n_iter)
+        return rec
+
+    def validate(self):
+        """Validator.run over the val split -> (seg_score, cam_score), logged as :291-294 on rank 0.  The model counts every
+        forward in `iter_num`, validation included (the reference's seg-trans switch at 15000 counts them too): afterwards the
+        counter stands where a single process validating ALL images leaves it, on every rank."""
+        before = self.model.iter_num
+        seg_score, cam_score = self.validator.run(self.val_loader)
+        self.model.iter_num = before + len(self.val_dataset)
+        if self.rank == 0:
+            LOG.info("cams score:")
+            LOG.info(cam_score)
+            LOG.info("segs score:")
+            LOG.info(seg_score)
+            brief = lambda s: None if s is None else {k: float(s[k]) for k in ("pAcc", "mAcc", "miou")}      # noqa: E731
+            append_metrics(self.val_metrics_path, {"iter": self.n_iter, "seg": brief(seg_score), "cam": brief(cam_score),
+                                                   "seg_hist_sum": int(self.validator.seg_hist_host.sum()),
+                                                   "cam_hist_sum": None if cam_score is None else int(self.validator.cam_hist_host.sum())})
+        return seg_score, cam_score
+
+    def save_model(self):
+        """Rank 0: WeCLIP_model_iter_N.pth = model.state_dict(), the reference's format (what test_msc_flip_* and
+        MscFlipEvaluator load)."""
+        if self.rank != 0:
+            return None
+        path = checkpoint_paths(self.cfg.work_dir.ckpt_dir, self.n_iter)[0]
+        torch.save(self.model.state_dict(), path)
+        return path
+
+    def save_state(self):
+        """Rank 0: train_state_iter_N.pth beside the model file: optimizer, iteration, model.iter_num and loader epoch as
+        they stand now (fit() writes it after the validation, whose forwards model.iter_num counts)."""
+        if self.rank != 0:
+            return None
+        path = checkpoint_paths(self.cfg.work_dir.ckpt_dir, self.n_iter)[1]
+        torch.save({"optimizer": self.opt.state_dict(), "global_step": self.opt.global_step, "iter": self.n_iter,
+                    "model_iter_num": self.model.iter_num, "loader_epoch": self.train_loader.epoch}, path)
+        return path
+
+    def save(self):
+        """Both files of the current iteration -> (model path, state path) on rank 0."""
+        return self.save_model(), self.save_state()
+
+    def resume(self, model_path):
+        """Parameters, optimizer tensors, iteration, model.iter_num and the loader epoch of a checkpoint pair: the LR schedule
+        and the seg-trans switch continue where they stopped.  The dropout and augmentation streams restart, and the loader
+        starts a fresh epoch, so the continuation is not bit-equal to the uninterrupted run."""
+        state = torch.load(state_path_of(model_path), map_location="cpu", weights_only=False)
+        self.model.load_state_dict(torch.load(model_path, map_location="cpu"), strict=True)
+        self.opt.load_state_dict(state["optimizer"])
+        self.opt.global_step = int(state["global_step"])
+        self.n_iter = int(state["iter"])
+        self.model.iter_num = int(state["model_iter_num"])
+        self.train_loader.set_epoch(int(state["loader_epoch"]))
+        self._batches = None
+        if self.rank == 0:
+            LOG.info("resumed from %s at iteration %d", model_path, self.n_iter)
+
+    def fit(self, until=None):
+        """The loop of :238-294 up to `until` (default: max_iters)."""
+        cfg = self.cfg.train
+        stop = self.max_iters if until is None else min(int(until), self.max_iters)
+        while self.n_iter < stop:
+            self.step_once()
+            if self.n_iter % cfg.log_iters == 0:
+                self.log()
+            if self.n_iter % cfg.eval_iters == 0:
+                if self.rank == 0:
+                    LOG.info("Validating...")
+                if self.n_iter > self.save_after:
+                    self.save_model()                    # before the validation, as :288-290
+                self.validate()
+                if self.n_iter > self.save_after:
+                    self.save_state()                    # after it: the state holds model.iter_num as it now stands
+        if self.n_iter >= self.max_iters:
+            self.close()
+        return True
+
+    def close(self):
+        if self._batches is not None:
+            self._batches.close()                        # ends the loader's decode threads
+            self._batches = None
+        if self.writer is not None:
+            self.writer.close()
+        if self.rank_dump_dir:
+            params = torch.cat([p.detach().flatten() for p in self.model.get_param_groups()[3]]).cpu()
+            torch.save({"rank": self.rank, "params": params, "iter": self.n_iter, "model_iter_num": self.model.iter_num,
+                        "seg_hist": self.validator.seg_hist.cpu(), "cam_hist": self.validator.cam_hist.cpu()},
+                       os.path.join(self.rank_dump_dir, f"rank{self.rank}.pth"))
+            self.rank_dump_dir = None
+
+
+def init_distributed():
+    """Under `python -m torch.distributed.run`: RCCL, one rank per GPU; WECLIP_DIST_BACKEND=gloo is the rehearsal switch of
+    bench.py (ranks share the GPUs that exist, gradients exchanged through the host).  Starts no processes."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    backend = os.environ.get("WECLIP_DIST_BACKEND", "nccl")
+    if backend != "nccl":
+        local = local % max(torch.cuda.device_count(), 1)
+    torch.cuda.set_device(local)
+    if world > 1:
+        if backend == "nccl":
+            dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group(backend=backend)
+    return world
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    cfg = load_config(args.config, crop_size=args.crop_size, work_dir=args.work_dir)
+    world = init_distributed()
+    try:
+        # WECLIP_TRAIN_RANK_DUMP=<dir>: Trainer(rank_dump_dir=...), the cross-rank check of the DP test
+        trainer = Trainer(cfg, args, rank_dump_dir=os.environ.get("WECLIP_TRAIN_RANK_DUMP") or None)
+        if trainer.rank == 0:
+            setup_logger(trainer.log_path)
+            LOG.info("\nargs: %s", args)
+            LOG.info("\nconfigs: %s", cfg)
+        trainer.fit()
+        trainer.close()
+        if world > 1:
+            dist.barrier()
+    finally:
+        if world > 1 and dist.is_initialized():
+            dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
