@@ -697,6 +697,27 @@ int wc_val_pair_hist(const float* seg, const long* cam, const long* gt, long* se
 int wc_label_match_count(const float* seg, const long* label, long* counts, int B, int C, int Hs, int Ws, int H, int W,
                          void* stream);
 
+/* ---- evaluation entry point: the per-image tail (csrc/evalfinish.hip) -------------------------- */
+/* wc_eval_finish: one evaluated image of test_msc_flip_voc.py:92-107 in one launch over the (Hl,Wl) label grid.
+ *   seg1 (C,Hs,Ws) f32 scale-1 logits; msc (C,Hs,Ws) f32 multi-scale average on the same grid, or NULL; cam (Hl,Wl) int64 or
+ *   NULL; gt (Hl,Wl) int64 or NULL.  p1 / pm = argmax_c bilinear(seg1 / msc)[c] (align_corners=False, scale = in / out, first
+ *   maximum wins: the value wc_resize_argmax writes, bit for bit).  Outputs, each NULL-able and written for EVERY pixel:
+ *   pred1_u8 / predm_u8 (Hl,Wl) uint8 = p1 / pm; cmap_rgb (Hl,Wl,3) uint8 HWC = the PASCAL VOC colour (utils/imutils.py:136-154
+ *   `colormap`, computed from the label) of pm, of p1 when msc is NULL.  Over the pixels with 0 <= gt < nc:
+ *   hist[gt*nc + p1] += 1, msc_hist[gt*nc + pm] += 1, cam_hist[gt*nc + cam] += 1, each (nc,nc) int64 and NULL-able (cam given
+ *   with gt needs cam_hist; predm_u8 / msc_hist need msc); a prediction or CAM value outside [0, nc) is skipped in its own
+ *   histogram and sets flag[0] (wc_confusion_hist's contract).  Integer atomics; the entry puts as many of the counted
+ *   histograms as fit 64 KiB into per-workgroup LDS cells and counts the rest with global atomics (same counts either way).
+ *   C <= 256 (the maps are uint8), nc <= 4096: WC_ERR_ARG otherwise, nothing launched.
+ * wc_label_finish: the same outputs for a ready int64 arg-max map (the CRF leg, :158-161).  pred (H,W) int64, gt (H,W) int64
+ *   or NULL; out_u8 (H,W) uint8 and cmap_rgb (H,W,3) uint8, each NULL-able; hist (nc,nc) int64, required with gt.  A pred
+ *   outside [0, 255] is written as 255 and sets flag[0]; a pred outside [0, nc) where 0 <= gt < nc is skipped and sets flag[0]. */
+int wc_eval_finish(const float* seg1, const float* msc, const long* cam, const long* gt, void* pred1_u8, void* predm_u8,
+                   void* cmap_rgb, long* hist, long* msc_hist, long* cam_hist, int* flag, int C, int Hs, int Ws, int Hl, int Wl,
+                   int nc, void* stream);
+int wc_label_finish(const long* pred, const long* gt, void* out_u8, void* cmap_rgb, long* hist, int* flag, int H, int W, int nc,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

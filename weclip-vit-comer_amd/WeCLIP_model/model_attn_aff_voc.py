@@ -137,10 +137,12 @@ class WeCLIP(nn.Module):
             maps.append(m)
         return xs, maps, B, Lq
 
-    def forward(self, img, img_names="2007_000032", mode="train", labels=None, plan=None):
+    def forward(self, img, img_names="2007_000032", mode="train", labels=None, plan=None, sizes=None):
         """-> (seg (B,nc,h,w), cam_labels (B,H,W) int64 [list of per-image maps in 'val' when the
         original sizes differ], attn_pred (B,hw,hw)).  `plan`: a ready clip_tool.PairPlan for `labels`
-        (TrainStep's graph mode keeps one per batch signature and refills it in place)."""
+        (TrainStep's graph mode keeps one per batch signature and refills it in place).  `sizes`: per image the (H, W) of
+        its 'val' CAM label map, for a caller that passes `labels` and knows the original size the reference reads off
+        the GT PNG (msc_flip_eval.py); default: the input's size with `labels`, the PNG's without."""
         B, _, H, W = img.shape
         h, w = H // 16, W // 16
         self.encoder.eval()
@@ -181,7 +183,7 @@ class WeCLIP(nn.Module):
 
                 with torch.no_grad():
                     cam_labels = self.cam_labels(img, xs[-1], maps, joined_attn_pred if seg_trans else None, img_names, labels, mode,
-                                                 seg_trans, h, w, plan=plan)
+                                                 seg_trans, h, w, plan=plan, sizes=sizes)
                 main.wait_stream(side)
                 return seg, cam_labels, attn_pred
             seg, attn_pred = HeadFunction.apply(self.head_engine, x16, B, Lq, h, w, drop, *self.head_engine.params())
@@ -197,7 +199,7 @@ class WeCLIP(nn.Module):
                 with torch.cuda.stream(side):
                     seg, attn_pred = self._module_head(img, xs, x16, comer_tokens, B, Lq, h, w)
                 with torch.no_grad():
-                    cam_labels = self.cam_labels(img, xs[-1], maps, None, img_names, labels, mode, seg_trans, h, w, plan=plan)
+                    cam_labels = self.cam_labels(img, xs[-1], maps, None, img_names, labels, mode, seg_trans, h, w, plan=plan, sizes=sizes)
                 main.wait_stream(side)
                 return seg, cam_labels, attn_pred
             seg, attn_pred = self._module_head(img, xs, x16, comer_tokens, B, Lq, h, w)
@@ -205,7 +207,7 @@ class WeCLIP(nn.Module):
             return seg, None, attn_pred
         with torch.no_grad():
             cam_labels = self.cam_labels(img, xs[-1], maps, attn_pred.detach(), img_names, labels, mode,
-                                         seg_trans, h, w, plan=plan)
+                                         seg_trans, h, w, plan=plan, sizes=sizes)
         return seg, cam_labels, attn_pred
 
     def side_streams(self):
@@ -243,7 +245,7 @@ class WeCLIP(nn.Module):
             attn_pred = torch.sigmoid(f.transpose(2, 1).bmm(f))
         return seg, attn_pred
 
-    def cam_labels(self, img, last_rows, maps, attn_pred, img_names, labels, mode, seg_trans, h, w, plan=None):
+    def cam_labels(self, img, last_rows, maps, attn_pred, img_names, labels, mode, seg_trans, h, w, plan=None, sizes=None):
         if self.bg_text_features is None or self.fg_text_features is None:
             raise RuntimeError("WeCLIP needs text_features=(bg, fg) (see __init__): pass them, or call "
                                "install_dropin(reference_root=<reference checkout>) before constructing WeCLIP so that "
@@ -252,11 +254,14 @@ class WeCLIP(nn.Module):
         if isinstance(img_names, str):
             img_names = [img_names]
         dev = img.device
+        given = sizes
         if plan is None:
             label_lists, sizes = self._labels_for(img_names, labels, (H, W))
             plan = CT.PairPlan(label_lists, self.fg_text_features.shape[0], self.bg_text_features.shape[0], dev)
         else:
             sizes = [(H, W)] * plan.B
+        if given is not None:
+            sizes = [tuple(int(v) for v in s) for s in given]
         text_hat = CT.normalised_text(self.fg_text_features, self.bg_text_features, dev)
         R, _, _, _ = CT.batch_refined_cams(self.encoder, last_rows, maps, attn_pred if seg_trans else None,
                                            plan, text_hat, h, w, self.cam_threshold, seg_trans,

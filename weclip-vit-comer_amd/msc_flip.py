@@ -68,8 +68,14 @@ class MscFlipEvaluator:
             self.crf_hist = torch.zeros(self.nc, self.nc, device=dev, dtype=torch.int64)
 
     @torch.no_grad()
-    def logits(self, inputs):
-        """inputs (1,3,H,W) -> (seg (nc,h,w): scale-1 un-flipped logits, msc (nc,h,w): multi-scale + flip average)."""
+    def logits(self, inputs, class_ids=None, want_cam=False, cam_size=None):
+        """inputs (1,3,H,W) -> (seg (nc,h,w): scale-1 un-flipped logits, msc (nc,h,w): multi-scale + flip average).
+        class_ids: the image's class ids; the model then gets `labels=[ids, ids]` for every pair (a VOC model built without
+        `dataset_root_path` has no other way to its CAM leg).  want_cam: the CAM label map of the scale-1 pair's first image
+        (test_msc_flip_voc.py:69-71; None for a model without a CAM leg in 'val') comes back as a third value; cam_size: its
+        (H, W) -- the label's, which the reference reads off the GT PNG -- instead of the resized input's.
+        With either, the VOC model's CAM / PAR chain is skipped at the non-unit scales, where the reference computes and
+        discards it (seg is bit-equal with and without: tests/test_msc_flip_eval_gpu.py)."""
         x = inputs[0].float().contiguous()
         _, H, W = x.shape
         if self.resize_long:                                  # F.interpolate(size=(_h, _w)): scale = in / out
@@ -80,20 +86,40 @@ class MscFlipEvaluator:
             h1, w1 = H, W
             pair = scale_flip_pair(x, (H, W), 1.0, 1.0)
         base = pair[0]                                        # the resized, un-flipped input all other scales start from
-        segs = _seg_of(self.model(pair, ["", ""], mode="val"))
-        segs = segs.float().contiguous()
+        extended = class_ids is not None or want_cam
+        kw = {} if class_ids is None else {"labels": [list(class_ids)] * 2}
+        sized = {} if cam_size is None else {"sizes": [tuple(cam_size)] * 2}
+        out = self.model(pair, ["", ""], mode="val", **kw, **sized)
+        segs = _seg_of(out).float().contiguous()
         seg1 = segs[0].contiguous()
         msc = torch.empty_like(seg1)
         w = 1.0 / (1 + sum(1 for s in self.scales if s != 1.0))
         flip_avg(segs, msc, w, accumulate=False)
-        for s in self.scales:
-            if s == 1.0:
-                continue
-            hs, ws = int(h1 * s), int(w1 * s)                 # F.interpolate(scale_factor=s): floor(size * s), step 1/s
-            pair_s = scale_flip_pair(base, (hs, ws), 1.0 / s, 1.0 / s)
-            segs_s = _seg_of(self.model(pair_s, ["", ""], mode="val"))
-            flip_avg(segs_s.float().contiguous(), msc, w, accumulate=True)
-        return seg1, msc
+        skip_cam = extended and bool(getattr(self.model, "val_runs_cam", False))
+        had = "val_runs_cam" in vars(self.model)
+        before = vars(self.model).get("val_runs_cam")
+        try:
+            if skip_cam:
+                self.model.val_runs_cam = False               # instance level: the class keeps its own
+            for s in self.scales:
+                if s == 1.0:
+                    continue
+                hs, ws = int(h1 * s), int(w1 * s)             # F.interpolate(scale_factor=s): floor(size * s), step 1/s
+                pair_s = scale_flip_pair(base, (hs, ws), 1.0 / s, 1.0 / s)
+                segs_s = _seg_of(self.model(pair_s, ["", ""], mode="val", **kw))
+                flip_avg(segs_s.float().contiguous(), msc, w, accumulate=True)
+        finally:
+            if skip_cam:
+                if had:
+                    self.model.val_runs_cam = before
+                else:
+                    del self.model.val_runs_cam
+        if not want_cam:
+            return seg1, msc
+        cam = None if isinstance(out, torch.Tensor) else out[1]
+        if cam is not None:
+            cam = cam[0].long().contiguous()
+        return seg1, msc, cam
 
     @torch.no_grad()
     def add(self, inputs, labels):

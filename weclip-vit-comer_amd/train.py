@@ -189,6 +189,29 @@ class LoggedTrainStep(TrainStep):
 
 
 # ---------------------------------------------------------------------------------------------- the driver
+def build_model(cfg, kind="voc", reference_root=None):
+    """The WeCLIP of `cfg.clip_init` for `kind` ("voc", "coco", or "seg": the supervised variant) with its text rows.  Shared with
+    the evaluation entry point (msc_flip_eval.py)."""
+    if reference_root:
+        from . import install_dropin
+        install_dropin(reference_root=reference_root)
+    if kind == "voc":
+        from .WeCLIP_model.model_attn_aff_voc import WeCLIP
+    elif kind == "coco":
+        from .WeCLIP_model.model_attn_aff_coco import WeCLIP
+    else:
+        from .WeCLIP_model.model_attn_aff_voc_seg import WeCLIP
+    ci = cfg.clip_init
+    text = None
+    if ci.get("text_features"):
+        rows = torch.load(ci.text_features, map_location="cuda")
+        text = (rows["bg"].float(), rows["fg"].float())
+    extra = {} if kind == "seg" else {"comer": bool(ci.get("comer", False))}
+    return WeCLIP(num_classes=cfg.dataset.num_classes, clip_model=ci.clip_pretrain_path, embedding_dim=ci.embedding_dim,
+                  in_channels=list(ci.in_channels), dataset_root_path=cfg.dataset.root_dir, device="cuda", text_features=text,
+                  **extra)
+
+
 class Trainer:
     """cfg: load_config(); args: build_parser().parse_args().  model: a ready WeCLIP instead of the one built from
     cfg.clip_init (embedding, tests).  rank_dump_dir: every rank writes `rank<r>.pth` (trainable parameters, iteration,
@@ -260,22 +283,7 @@ class Trainer:
             self.resume(args.resume)
 
     def build_model(self):
-        cfg, args = self.cfg, self.args
-        if getattr(args, "reference_root", None):
-            from . import install_dropin
-            install_dropin(reference_root=args.reference_root)
-        if self.kind == "voc":
-            from .WeCLIP_model.model_attn_aff_voc import WeCLIP
-        else:
-            from .WeCLIP_model.model_attn_aff_coco import WeCLIP
-        ci = cfg.clip_init
-        text = None
-        if ci.get("text_features"):
-            rows = torch.load(ci.text_features, map_location="cuda")
-            text = (rows["bg"].float(), rows["fg"].float())
-        return WeCLIP(num_classes=cfg.dataset.num_classes, clip_model=ci.clip_pretrain_path, embedding_dim=ci.embedding_dim,
-                      in_channels=list(ci.in_channels), dataset_root_path=cfg.dataset.root_dir, device="cuda", text_features=text,
-                      comer=bool(ci.get("comer", False)))
+        return build_model(self.cfg, self.kind, getattr(self.args, "reference_root", None))
 
     # ---- one iteration --------------------------------------------------------------------------------------------
     def _next_batch(self):
