@@ -628,6 +628,31 @@ int wc_dcrf_inference(const void* img, int img_is_u8, const float* unary, float*
 int wc_dcrf_message(const void* img, int img_is_u8, const float* Q, float* msg_pos, float* msg_bil, float* S, void* ws,
                     int C, int H, int W, float pos_xy_std, float bi_xy_std, float bi_rgb_std, void* stream);
 
+/* ---- dense energy loss (csrc/energy.hip) ------------------------------------------------------ */
+/* utils/losses.py:52-116 (`DenseEnergyLossFunction`, `DenseEnergyLoss`) with the `bilateralfilter_batch` call of :75 as the
+ * EXACT all-pairs sum (the extension's permutohedral lattice is not built; parity with it: unpinned).  Pixel i = y * W + x;
+ * images (N,3,H,W) f32 on the 0..255 scale, segs P (N,K,H,W) f32, rois (N,H,W) f32 in {0,1}, unlabel_u8 (N,H,W) bytes
+ * (non-zero = unlabelled).  k_n(i,j) = exp(-|p_i - p_j|^2 / (2 sigma_xy^2) - |I_n,i - I_n,j|^2 / (2 sigma_rgb^2)), j = i
+ * included; S = P * ROI; AS(n,k,i) = sum_j k_n(i,j) S(n,k,j); Gate = ROI - max_k P, then 1 where unlabelled, then 0 where
+ * negative; A = Gate * AS; loss = -(1/N) sum_{n,k,i} S A.
+ * Limits (WC_ERR_ARG, nothing launched): non-null pointers, 1 <= N <= 65535, 1 <= K <= 128, 1 <= H*W <= 640*640, sigmas
+ * finite and > 0.  No allocation, no host synchronisation, every launch on `stream`.
+ * Error model of an element of AS against fp64: |AS - AS64| <= eps * sum_j k |S_j| + 2^-24, eps = 2^-10 (the arithmetic of
+ * the dense CRF's bilateral message above).  Deterministic: no atomics, fixed-order sums, bit-identical from run to run.
+ * wc_energy_workspace_floats: *n_floats (HOST out-parameter) = N * (H*W*(8 + CP) + ceil(H*W / 128)), CP = 32*ceil(K/32): the
+ *                       f32 workspace `ws` of the two calls below (features, the pixel-major operand, loss partials).
+ * wc_bilateral_filter_batch: losses.py:75 alone: AS (N,K,H,W) of segs as given (no ROI, no Gate; segs may be signed).
+ * wc_dense_energy_fwd:  losses.py:55-84: A (N,K,H,W) = Gate * AS, gate (N,H,W), loss (1) f32.
+ * wc_dense_energy_bwd:  losses.py:87-91: grad_segs (N,K,H,W) = (-2/N) * grad_out[0] * A * ROI, grad_out (1) f32 in DEVICE
+ *                       memory.  The Gate is a constant here, as in the reference. */
+int wc_energy_workspace_floats(int N, int K, int H, int W, long* n_floats);
+int wc_bilateral_filter_batch(const float* images, const float* segs, float* AS, void* ws, int N, int K, int H, int W,
+                              float sigma_rgb, float sigma_xy, void* stream);
+int wc_dense_energy_fwd(const float* images, const float* segs, const float* rois, const void* unlabel_u8, float* A, float* gate,
+                        float* loss, void* ws, int N, int K, int H, int W, float sigma_rgb, float sigma_xy, void* stream);
+int wc_dense_energy_bwd(const float* A, const float* rois, const float* grad_out, float* grad_segs, int N, int K, int H, int W,
+                        void* stream);
+
 /* ---- CLIP text tower (csrc/text.hip; DESIGN.md "Text tower") -------------------------------------------------------- */
 /* wc_text_embed:      clip/model.py:393-395 (token_embedding(text) + positional_embedding) and :403 (`text.argmax(-1)`).
  *                     tokens (N, Lctx) int32; tok_emb (V, W) f32; pos (>= L, W) f32.  eot (N) int32 = index of the first

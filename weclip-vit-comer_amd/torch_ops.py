@@ -347,5 +347,60 @@ def _(text, token_embedding, positional_embedding, blocks, heads, ln_final_weigh
     return text_projection.new_empty((text.shape[0], text_projection.shape[1]), dtype=F32)
 
 
+@torch.library.custom_op(f"{_LIB}::bilateral_filter_batch", mutates_args=(), device_types="cuda")
+def bilateral_filter_batch(images: Tensor, segs: Tensor, sigma_rgb: float, sigma_xy: float) -> Tensor:
+    """The exact batched bilateral filter behind the dense energy loss (reference utils/losses.py:75): images (N,3,H,W) on the
+    0..255 scale, segs (N,K,H,W) -> AS (N,K,H,W) f32.  No autograd."""
+    from .utils.losses import bilateral_filter_batch as bf
+    return bf(images, segs, sigma_rgb, sigma_xy)
+
+
+@bilateral_filter_batch.register_fake
+def _(images, segs, sigma_rgb, sigma_xy):
+    return segs.new_empty(segs.shape, dtype=F32)
+
+
+@torch.library.custom_op(f"{_LIB}::dense_energy", mutates_args=(), device_types="cuda")
+def dense_energy(images: Tensor, segmentations: Tensor, rois: Tensor, unlabel_region: Tensor, sigma_rgb: float,
+                 sigma_xy: float) -> Tuple[Tensor, Tensor]:
+    """DenseEnergyLossFunction.forward (reference utils/losses.py:55-84) -> (loss (1,), A (N,K,H,W) = Gate * AS).  Differentiable
+    in `segmentations` through weclip::dense_energy_bwd (register_autograd); the gradient arriving at A is ignored, as the
+    reference's backward sees the loss alone."""
+    from .utils.losses import dense_energy_forward
+    loss, A, _ = dense_energy_forward(images, segmentations, sigma_rgb, sigma_xy, rois, unlabel_region)
+    return loss, A
+
+
+@dense_energy.register_fake
+def _(images, segmentations, rois, unlabel_region, sigma_rgb, sigma_xy):
+    return segmentations.new_empty((1,), dtype=F32), segmentations.new_empty(segmentations.shape, dtype=F32)
+
+
+@torch.library.custom_op(f"{_LIB}::dense_energy_bwd", mutates_args=(), device_types="cuda")
+def dense_energy_bwd(grad_loss: Tensor, A: Tensor, rois: Tensor) -> Tensor:
+    """Gradient of weclip::dense_energy with respect to the segmentations: -2 * grad_loss * A * ROI / N (reference
+    utils/losses.py:87-91; csrc/energy.hip energy_bwd_kernel)."""
+    from .utils.losses import dense_energy_backward
+    return dense_energy_backward(grad_loss, A, rois)
+
+
+@dense_energy_bwd.register_fake
+def _(grad_loss, A, rois):
+    return A.new_empty(A.shape, dtype=F32)
+
+
+def _energy_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1], inputs[2])
+
+
+def _energy_backward(ctx, grad_loss, grad_A):
+    A, rois = ctx.saved_tensors
+    return None, torch.ops.weclip.dense_energy_bwd(grad_loss, A, rois), None, None, None, None
+
+
+torch.library.register_autograd(f"{_LIB}::dense_energy", _energy_backward, setup_context=_energy_setup)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
-       "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text")
+       "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
+       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd")

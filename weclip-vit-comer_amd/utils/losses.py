@@ -1,5 +1,6 @@
-"""Live loss functions of the reference training step (utils/losses.py:11-22 get_aff_loss;
-scripts/dist_clip_voc.py:105-113 get_seg_loss).  Stock PyTorch-ROCm ops."""
+"""Loss functions of the reference (utils/losses.py:11-22 get_aff_loss; scripts/dist_clip_voc.py:105-113 get_seg_loss) in
+stock PyTorch-ROCm ops, their fused HIP forms, and the dense energy loss (utils/losses.py:35-116:
+get_energy_loss, DenseEnergyLossFunction, DenseEnergyLoss) on the GPU (csrc/energy.hip)."""
 import torch
 import torch.nn.functional as F
 
@@ -190,3 +191,135 @@ class _AffLossFn(torch.autograd.Function):
 def get_aff_loss_fused(attn_pred, cam_label, radius=8, ignore_index=255):
     """== get_aff_loss(attn_pred, cams_to_affinity_label(cam_label, get_mask_by_radius(h, w, radius)))[0]."""
     return _AffLossFn.apply(attn_pred, cam_label, radius, ignore_index)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Dense energy (regularised CRF) loss: reference utils/losses.py:35-116 with the `bilateralfilter_batch` call as the exact
+# all-pairs sum on the GPU (csrc/energy.hip, C ABI `wc_energy_*` / `wc_dense_energy_*`; DESIGN.md section 15).  The
+# reference's extension (a permutohedral lattice) is not shipped with it; parity with the lattice is unpinned.
+def _energy_workspace(N, K, H, W, device):
+    import ctypes
+    from .. import _lib as L
+    n = ctypes.c_long()
+    L.lib().wc_energy_workspace_floats(N, K, H, W, ctypes.byref(n))
+    return torch.empty(n.value, device=device, dtype=torch.float32)
+
+
+def _energy_shapes(images, segs, who):
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError(f"{who}: images must be (N, 3, H, W), got {tuple(images.shape)}")
+    if segs.dim() != 4 or segs.shape[0] != images.shape[0] or segs.shape[2:] != images.shape[2:]:
+        raise RuntimeError(f"{who}: segmentations {tuple(segs.shape)} do not match images {tuple(images.shape)}")
+    return segs.shape
+
+
+def bilateral_filter_batch(images, segs, sigma_rgb, sigma_xy):
+    """AS (N, K, H, W) f32 on the device: AS(n, k, i) = sum_j exp(-|p_i - p_j|^2 / (2 sigma_xy^2) - |I_n,i - I_n,j|^2 /
+    (2 sigma_rgb^2)) segs(n, k, j) over every pixel j of image n (j = i included): what the reference's
+    `bilateralfilter_batch(images, segs, AS, N, K, H, W, sigma_rgb, sigma_xy)` (losses.py:75) approximates.  images
+    (N, 3, H, W) on the 0..255 scale; segs may be signed.  No autograd."""
+    from .. import _lib as L
+    L.require_gpu()
+    N, K, H, W = _energy_shapes(images, segs, "bilateral_filter_batch")
+    img = images.detach().float().contiguous()
+    seg = segs.detach().float().contiguous()
+    AS = torch.empty_like(seg)
+    ws = _energy_workspace(N, K, H, W, seg.device)
+    L.lib().wc_bilateral_filter_batch(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segs"), L.ptr(AS), L.ptr(ws),
+                                      N, K, H, W, float(sigma_rgb), float(sigma_xy), L.stream())
+    return AS
+
+
+def dense_energy_forward(images, segs, sigma_rgb, sigma_xy, rois, unlabel_region):
+    """(loss (1,), A (N, K, H, W) = Gate * AS, Gate (N, H, W)) of DenseEnergyLossFunction.forward, all on the device."""
+    from .. import _lib as L
+    L.require_gpu()
+    N, K, H, W = _energy_shapes(images, segs, "DenseEnergyLossFunction")
+    if tuple(rois.shape) != (N, H, W) or tuple(unlabel_region.shape) != (N, H, W):
+        raise RuntimeError(f"DenseEnergyLossFunction: ROIs {tuple(rois.shape)} / unlabel_region {tuple(unlabel_region.shape)} "
+                           f"must be {(N, H, W)}")
+    img = images.detach().float().contiguous()
+    seg = segs.detach().float().contiguous()
+    roi = rois.detach().float().contiguous()                 # the caller's ROIs is left as it is (the reference unsqueezes it)
+    unl = (unlabel_region != 0).contiguous().view(torch.uint8)
+    A = torch.empty_like(seg)
+    gate = torch.empty_like(roi)
+    loss = torch.empty(1, device=seg.device, dtype=torch.float32)
+    ws = _energy_workspace(N, K, H, W, seg.device)
+    L.lib().wc_dense_energy_fwd(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segmentations"),
+                                L.ptr(roi, torch.float32, "ROIs"), L.ptr(unl, torch.uint8, "unlabel_region"), L.ptr(A), L.ptr(gate),
+                                L.ptr(loss), L.ptr(ws), N, K, H, W, float(sigma_rgb), float(sigma_xy), L.stream())
+    return loss, A, gate
+
+
+def dense_energy_backward(grad_output, A, rois):
+    """grad_segmentations = -2 * grad_output * A * ROI / N (losses.py:87-91): one elementwise kernel, grad_output read on the
+    device.  Computed and returned in f32 like the forward, which casts its inputs up; for half-precision segmentations
+    autograd casts the gradient back."""
+    from .. import _lib as L
+    L.require_gpu()
+    if A.dim() != 4 or tuple(rois.shape) != (A.shape[0],) + tuple(A.shape[2:]):
+        raise RuntimeError(f"dense_energy_backward: A {tuple(A.shape)} and ROIs {tuple(rois.shape)} do not match")
+    N, K, H, W = A.shape
+    g = grad_output.detach().float().reshape(-1)[:1].contiguous()
+    A = A.contiguous()
+    roi = rois.detach().float().contiguous()
+    out = torch.empty_like(A)
+    L.lib().wc_dense_energy_bwd(L.ptr(A, torch.float32, "A"), L.ptr(roi, torch.float32, "ROIs"), L.ptr(g, torch.float32, "grad"),
+                                L.ptr(out), N, K, H, W, L.stream())
+    return out
+
+
+class DenseEnergyLossFunction(torch.autograd.Function):
+    """loss (1,) = -(1/N) sum S * Gate * AS with S = segmentations * ROIs, AS the bilateral filter of S and
+    Gate = ROIs - max_k segmentations, 1 where unlabelled, 0 where negative (reference losses.py:52-91; argument order as
+    there).  backward gives -2 * grad * Gate * AS * ROIs / N to `segmentations` and nothing else: the Gate is held constant
+    and the factor 2 stands for the kernel's symmetry, as in the reference -- not the true derivative where the Gate varies."""
+
+    @staticmethod
+    def forward(ctx, images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region):
+        loss, A, _ = dense_energy_forward(images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region)
+        ctx.save_for_backward(A, ROIs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        A, rois = ctx.saved_tensors
+        return None, dense_energy_backward(grad_output, A, rois), None, None, None, None
+
+
+class DenseEnergyLoss(torch.nn.Module):
+    """reference losses.py:94-116: the loss at `scale_factor` of the input size, times `weight`.  Images, ROIs and the label
+    map are resampled nearest, the segmentations bilinear (align_corners=False); a label of 255 marks a pixel unlabelled;
+    sigma_xy shrinks with the image."""
+
+    def __init__(self, weight, sigma_rgb, sigma_xy, scale_factor):
+        super().__init__()
+        self.weight, self.scale_factor = weight, scale_factor
+        self.sigma_rgb, self.sigma_xy = sigma_rgb, sigma_xy
+
+    def _resample(self, x, mode="nearest"):
+        kw = dict(align_corners=False) if mode == "bilinear" else {}
+        return F.interpolate(x, scale_factor=self.scale_factor, mode=mode, **kw)
+
+    def forward(self, images, segmentations, ROIs, seg_label):
+        unlabelled = self._resample(seg_label).long().eq(255)[:, 0]
+        rois = self._resample(ROIs[:, None])[:, 0]
+        energy = DenseEnergyLossFunction.apply(self._resample(images), self._resample(segmentations, "bilinear"), self.sigma_rgb,
+                                               self.sigma_xy * self.scale_factor, rois, unlabelled)
+        return self.weight * energy
+
+    def extra_repr(self):
+        # nn.Module prints this between the brackets: the order and names are the reference's
+        fields = ("sigma_rgb", "sigma_xy", "weight", "scale_factor")
+        return ", ".join(f"{k}={getattr(self, k)}" for k in fields)
+
+
+def get_energy_loss(img, logit, label, img_box, loss_layer, mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375]):
+    """reference losses.py:35-50: soft-max, crop mask from img_box rows (y0, y1, x0, x1), de-normalised image, loss_layer."""
+    pred_prob = F.softmax(logit, dim=1)
+    crop_mask = torch.zeros_like(pred_prob[:, 0])
+    for idx, coord in enumerate(img_box):
+        crop_mask[idx, int(coord[0]):int(coord[1]), int(coord[2]):int(coord[3])] = 1
+    _img = torch.stack([img[:, c] * std[c] + mean[c] for c in range(3)], dim=1)
+    return loss_layer(_img, pred_prob, crop_mask, label.type(torch.uint8).unsqueeze(1))
