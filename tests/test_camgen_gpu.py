@@ -59,6 +59,27 @@ def test_clip_preprocess_batch_equals_single_images():
         assert np.array_equal(both[b].cpu().numpy().view(np.uint32), ref.view(np.uint32))
 
 
+def test_clip_preprocess_at_the_8x_table_limit():
+    """128 x 160 -> 16 x 20 is exactly 8x, the largest ratio the host accepts (its tap bound is 33 = PREP_KMAX): the widest windows
+    the shared coefficient routine (csrc/resample.h) sees from a valid call, 32 taps of the 33 the table holds.  The uint8 image
+    equals the restatement of Pillow's BICUBIC."""
+    import ctypes
+    from weclip_vit_comer_amd import _lib as L
+    from weclip_vit_comer_amd.clip.generate_cams import CLIP_MEAN, CLIP_STD
+    img = np.random.default_rng(8).integers(0, 256, (128, 160, 3), dtype=np.uint8)
+    src = torch.from_numpy(img).cuda()
+    n = ctypes.c_long(0)
+    L.lib().wc_clip_preprocess_workspace_bytes(1, 128, 160, 16, 20, ctypes.byref(n))
+    ws = torch.empty(n.value, device="cuda", dtype=torch.uint8)
+    dst = torch.empty(1, 3, 16, 20, device="cuda", dtype=torch.float32)
+    u8 = torch.empty(1, 16, 20, 3, device="cuda", dtype=torch.uint8)
+    L.lib().wc_clip_preprocess(L.ptr(src, torch.uint8, "images"), L.ptr(dst), None, L.ptr(u8), L.ptr(ws), ws.numel(), 1, 128, 160, 16, 20,
+                               (ctypes.c_float * 3)(*CLIP_MEAN), (ctypes.c_float * 3)(*CLIP_STD), L.stream())
+    ref = PR.bicubic_resize_u8(img, 16, 20)
+    got = u8[0].cpu().numpy()
+    assert np.array_equal(got, ref), np.count_nonzero(got != ref)
+
+
 def test_output_kernel_within_one_fp16_ulp_of_the_reference(golden):
     from weclip_vit_comer_amd.clip.generate_cams import resize_cam_f32, scale_cam_f16
     g = golden("cam_scale_resize.npz")

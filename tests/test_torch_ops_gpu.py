@@ -90,6 +90,19 @@ def test_device_input_pipeline_matches_oracle_at_bench_size():
     assert torch.isnan(bad[:, :, 4:71, 4:96]).all() and not torch.isnan(bad[:, :, 75:, :]).any() and not torch.isnan(bad[:, :, :, 100:]).any()
 
 
+def test_device_input_pipeline_at_the_4x_table_limit():
+    """The largest down-scaling ratio the host accepts (64 x 80 -> 16 x 20, exactly 4x) gives the widest windows the shared
+    coefficient routine (csrc/resample.h) sees from a valid call: 8 taps of the 9 the table holds, none may be poisoned.  Flip on,
+    pad (3, 2), crop 24: finite and equal on every value to the oracle's restatement."""
+    from weclip_vit_comer_amd.data import DeviceAugment
+    img = torch.randint(0, 256, (64, 80, 3), generator=torch.Generator().manual_seed(21), dtype=torch.uint8)
+    aug = DeviceAugment(crop_size=24, rescale_range=(0.25, 2.0), seed=1)
+    out = aug(img[None].cuda(), aug.pack([(0.25, 1, 16, 20, 3, 2, 0, 0)])).cpu()[0]
+    ref = O.augment_normalize(img, 0.25, 1, 3, 2, 0, 0, 24)
+    assert tuple(out.shape) == (3, 24, 24) and torch.isfinite(out).all()
+    assert torch.equal(out, ref), (out - ref).abs().max().item()
+
+
 @pytest.mark.parametrize("case", ["dx_only", "dw_only", "both"])
 def test_trainable_linear_partial_gradients(case):
     """weclip::linear through register_autograd with a frozen weight (dx only), a frozen input (dW / db only) and both:

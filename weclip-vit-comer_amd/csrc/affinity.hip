@@ -15,6 +15,7 @@
 //                       box fill -- on the device, one workgroup per (image, class) pair.
 //   cam_upsample_kernel: per-map min-max, bilinear (half-pixel) resize to H x W, bg = 1 - max_k.
 #include "common.h"
+#include "resample.h"
 
 #define MAXK 4   // classes per pass in the mat-vec kernels
 
@@ -539,12 +540,10 @@ __global__ __launch_bounds__(256) void cam_upsample_kernel(const float* __restri
                                                             int h, int w, int K, int C, int H, int W, float sy, float sx) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
     if (x >= W || y >= H) return;
-    float fy = fmaxf(sy * (y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sx * (x + 0.5f) - 0.5f, 0.f);
-    int y0 = (int)fy, x0 = (int)fx;
-    if (y0 > h - 1) y0 = h - 1;
-    if (x0 > w - 1) x0 = w - 1;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
-    const float ly = fy - y0, lx = fx - x0, hy = 1.f - ly, hx = 1.f - lx;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    wc_bil_src(y, h, sy, y0, y1, ly);
+    wc_bil_src(x, w, sx, x0, x1, lx);
     const long HW = (long)H * W;
     const int n = nk[b];
     float best = -INFINITY;
@@ -553,7 +552,7 @@ __global__ __launch_bounds__(256) void cam_upsample_kernel(const float* __restri
         const float mn = stats[((long)b * K + k) * 2], den = 1e-7f + stats[((long)b * K + k) * 2 + 1];
         const float v00 = (Rb[((long)y0 * w + x0) * K + k] - mn) / den, v01 = (Rb[((long)y0 * w + x1) * K + k] - mn) / den;
         const float v10 = (Rb[((long)y1 * w + x0) * K + k] - mn) / den, v11 = (Rb[((long)y1 * w + x1) * K + k] - mn) / den;
-        const float v = hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
+        const float v = wc_lerp4(v00, v01, v10, v11, ly, lx);
         cams[((long)b * C + 1 + k) * HW + (long)y * W + x] = v;
         best = fmaxf(best, v);
     }

@@ -11,19 +11,16 @@
 // PIL's BILINEAR (Pillow, ImagingResample 8 bits per channel) is NOT plain half-pixel bilinear: it is a separable
 // triangle filter whose support grows with the down-scaling ratio (support = max(in / out, 1), up to
 // 2 * ceil(support) + 1 taps), evaluated with coefficients normalised in double precision and rounded to 22-bit fixed
-// point, a horizontal pass whose result is rounded to uint8, then a vertical pass over those uint8 values.  The two
-// kernels below follow that arithmetic step by step (same double-precision operation order, same integer rounding), so
+// point, a horizontal pass whose result is rounded to uint8, then a vertical pass over those uint8 values.  resample.h
+// follows that arithmetic step by step (same double-precision operation order, same integer rounding), so
 // the output equals PIL's on every pixel, up- and down-scaling (tests/golden/augment_ref.npz, made by the reference's
 // own transforms with real PIL).
 //   aug_coeff_kernel: per image and axis, for the `crop` output coordinates only: first tap, tap count and the
 //                     fixed-point coefficients (or "outside the rescaled image": zero padding);
 //   augment_normalize_kernel: one thread per output pixel, ny x nx taps (3 x 3 when up-scaling, 5 x 5 at scale 0.5).
 #include "common.h"
+#include "resample.h"
 #include "augment_shape.h"
-
-#define AUG_KMAX 9          // 2 * ceil(support) + 1 with support <= 4, i.e. down-scaling by at most 4
-#define AUG_ENT 12          // ints per table entry: first tap, count, AUG_KMAX coefficients, pad (48 B)
-#define AUG_PREC 22         // Pillow: PRECISION_BITS = 32 - 8 - 2
 
 struct AugParams {      // one per image, 8 ints / floats = 32 B
     float scale;        // s of random_scaling
@@ -56,44 +53,12 @@ __global__ __launch_bounds__(256) void aug_coeff_kernel(const AugParams* __restr
         return;
     }
     if (axis && p.flip) r = out_size - 1 - r;
-    // Pillow precompute_coeffs(inSize, in0 = 0, in1 = inSize, outSize, BILINEAR) for output coordinate r
-    const double scale = (double)((float)in_size - 0.f) / out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fscale;
-    const double center = 0.0 + (r + 0.5) * scale;
-    const double ss = 1.0 / fscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    int n = xmax - xmin;
-    if (n > AUG_KMAX) {                                                    // down-scaling beyond 4x: the table cannot hold Pillow's
-        e[0] = 0;                                                          // filter -> the pixel is POISONED (NaN), never a
-        e[1] = -1;                                                         // silently different filter (checked precondition)
-        return;
+    // down-scaling beyond 4x: the table cannot hold Pillow's filter -> the pixel is POISONED (NaN), never a silently different
+    // filter (checked precondition).  The weights of the capped window stay behind e[1] = -1; they mean nothing and are never read.
+    if (pil_coeffs<PilTriangle, AUG_KMAX>(r, in_size, out_size, e) > AUG_KMAX) {
+        e[0] = 0;
+        e[1] = -1;
     }
-    double k[AUG_KMAX], ww = 0.0;
-#pragma unroll
-    for (int x = 0; x < AUG_KMAX; ++x) {
-        double a = ((double)(x + xmin) - center + 0.5) * ss;
-        a = a < 0.0 ? -a : a;
-        const double w = (x < n && a < 1.0) ? 1.0 - a : 0.0;
-        k[x] = w;
-        ww += w;
-    }
-    e[0] = xmin;
-    e[1] = n;
-#pragma unroll
-    for (int x = 0; x < AUG_KMAX; ++x) {
-        const double v = ww != 0.0 ? k[x] / ww : k[x];
-        e[2 + x] = (int)(0.5 + v * (double)(1 << AUG_PREC));               // normalize_coeffs_8bpc (all coefficients >= 0)
-    }
-    e[2 + AUG_KMAX] = 0;
-}
-
-__device__ __forceinline__ int aug_clip8(int v) {
-    v >>= AUG_PREC;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 template <bool RAGGED>
@@ -113,32 +78,15 @@ __global__ __launch_bounds__(256) void augment_normalize_kernel(const unsigned c
     }
     const int* ey = tab + (((long)b * 2 + 0) * crop + y) * AUG_ENT;       // one entry per wave
     const int* ex = tab + (((long)b * 2 + 1) * crop + x) * AUG_ENT;
-    const int ymin = ey[0], ny = ey[1], xmin = ex[0], nx = ex[1];
     float v0 = 0.f, v1 = 0.f, v2 = 0.f;                                    // canvas padding (mean_rgb = [0, 0, 0])
-    if (ny == 0 || nx == 0) {
-        // outside the rescaled image on either axis: canvas padding, whatever the other axis' table says
-    } else if (ny < 0 || nx < 0) {                                         // precondition in/out <= 4 violated (aug_coeff_kernel)
+    int c0, c1, c2;
+    const int got = pil_gather_rgb8(ey, ex, src, Ws, c0, c1, c2);
+    if (got < 0) {                                                         // precondition in/out <= 4 violated (aug_coeff_kernel)
         v0 = v1 = v2 = __builtin_nanf("");
-    } else {
-        const unsigned char* S = src + ((long)ymin * Ws + xmin) * 3;
-        int a0 = 1 << (AUG_PREC - 1), a1 = a0, a2 = a0;
-        for (int j = 0; j < ny; ++j) {
-            const unsigned char* row = S + (long)j * Ws * 3;
-            int h0 = 1 << (AUG_PREC - 1), h1 = h0, h2 = h0;                // horizontal pass of source row ymin + j
-            for (int i = 0; i < nx; ++i) {
-                const int kx = ex[2 + i];
-                h0 += kx * row[3 * i];
-                h1 += kx * row[3 * i + 1];
-                h2 += kx * row[3 * i + 2];
-            }
-            const int ky = ey[2 + j];                                      // vertical pass over the uint8-rounded rows
-            a0 += ky * aug_clip8(h0);
-            a1 += ky * aug_clip8(h1);
-            a2 += ky * aug_clip8(h2);
-        }
-        v0 = (float)aug_clip8(a0);
-        v1 = (float)aug_clip8(a1);
-        v2 = (float)aug_clip8(a2);
+    } else if (got) {
+        v0 = (float)c0;
+        v1 = (float)c1;
+        v2 = (float)c2;
     }
     const long plane = (long)crop * crop;
     float* D = dst + (long)b * 3 * plane + (long)y * crop + x;

@@ -15,15 +15,13 @@
 //                        (pad -> flip -> Pillow NEAREST), or -1 in the padding
 //   segaug_hist_kernel   per (image, candidate, 32-row slab): class histogram of the label as the crop would see it
 //   segaug_select_kernel per image: integer acceptance rule over the candidates -> chosen box, index, img_box
-//   segaug_coeff_kernel  Pillow BILINEAR tables of the chosen window (the arithmetic of augment.hip's aug_coeff_kernel)
+//   segaug_coeff_kernel  Pillow BILINEAR tables of the chosen window (resample.h, the tables of augment.hip's aug_coeff_kernel)
 //   segaug_gather_kernel one thread per output pixel: image taps -> photometric chain on the uint8 triple -> normalise;
 //                        label through the index tables
 #include "common.h"
+#include "resample.h"
 #include "augment_shape.h"
 
-#define SEG_KMAX 9          // as augment.hip: 2 * ceil(support) + 1 taps, down-scaling by at most 4
-#define SEG_ENT 12
-#define SEG_PREC 22
 #define SEG_MAX_CAND 16
 #define SEG_SLAB 32         // rows of the crop window per histogram block
 #define SEG_RUN 16          // consecutive pixels of a row per thread
@@ -306,7 +304,7 @@ __global__ __launch_bounds__(256) void segaug_coeff_kernel(const SegAugParams* _
     const AugShape sh = aug_shape<RAGGED>(b, Hs, Ws, offsets, sizes, src_bytes);
     const int in_size = axis ? sh.W : sh.H, out_size = axis ? p.rw : p.rh;
     int r = o + sel[b * 4 + axis] - (axis ? p.pad_x : p.pad_y);           // coordinate in the rescaled image
-    int* e = tab + (((long)b * 2 + axis) * crop + o) * SEG_ENT;
+    int* e = tab + (((long)b * 2 + axis) * crop + o) * AUG_ENT;
     if (p.rh < 1 || p.rw < 1 || p.rh > CM || p.rw > CM || !sh.ok) {        // record outside the checked preconditions: poison
         e[0] = 0;
         e[1] = -1;
@@ -318,44 +316,11 @@ __global__ __launch_bounds__(256) void segaug_coeff_kernel(const SegAugParams* _
         return;
     }
     if (axis && p.flip) r = out_size - 1 - r;
-    // Pillow precompute_coeffs(inSize, in0 = 0, in1 = inSize, outSize, BILINEAR) for output coordinate r
-    const double scale = (double)((float)in_size - 0.f) / out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * fscale;
-    const double center = 0.0 + (r + 0.5) * scale;
-    const double ss = 1.0 / fscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    int n = xmax - xmin;
-    if (n > SEG_KMAX) {                                                    // down-scaling beyond 4x: POISONED (NaN), as augment.hip
+    // down-scaling beyond 4x: POISONED (NaN), as augment.hip; the weights left behind e[1] = -1 mean nothing and are never read
+    if (pil_coeffs<PilTriangle, AUG_KMAX>(r, in_size, out_size, e) > AUG_KMAX) {
         e[0] = 0;
         e[1] = -1;
-        return;
     }
-    double k[SEG_KMAX], ww = 0.0;
-#pragma unroll
-    for (int x = 0; x < SEG_KMAX; ++x) {
-        double a = ((double)(x + xmin) - center + 0.5) * ss;
-        a = a < 0.0 ? -a : a;
-        const double w = (x < n && a < 1.0) ? 1.0 - a : 0.0;
-        k[x] = w;
-        ww += w;
-    }
-    e[0] = xmin;
-    e[1] = n;
-#pragma unroll
-    for (int x = 0; x < SEG_KMAX; ++x) {
-        const double v = ww != 0.0 ? k[x] / ww : k[x];
-        e[2 + x] = (int)(0.5 + v * (double)(1 << SEG_PREC));               // normalize_coeffs_8bpc
-    }
-    e[2 + SEG_KMAX] = 0;
-}
-
-__device__ __forceinline__ int seg_clip8(int v) {
-    v >>= SEG_PREC;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
 // grid (cdiv(crop, 64), cdiv(crop, 4), B): one thread per output pixel
@@ -386,31 +351,15 @@ __global__ __launch_bounds__(256) void segaug_gather_kernel(const u8* __restrict
     const long plane = (long)crop * crop;
     dst_lab[(long)b * plane + (long)y * crop + x] = (iy < 0 || ix < 0) ? ignore : lv;
 
-    const int* ey = tab + (((long)b * 2 + 0) * crop + y) * SEG_ENT;
-    const int* ex = tab + (((long)b * 2 + 1) * crop + x) * SEG_ENT;
-    const int ymin = ey[0], ny = ey[1], xmin = ex[0], nx = ex[1];
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f;                                    // canvas padding (mean_rgb = [0, 0, 0]), not distorted:
-    if (ny == 0 || nx == 0) {                                              // the reference pads after PhotoMetricDistortion
-    } else if (ny < 0 || nx < 0) {
+    const int* ey = tab + (((long)b * 2 + 0) * crop + y) * AUG_ENT;
+    const int* ex = tab + (((long)b * 2 + 1) * crop + x) * AUG_ENT;
+    // canvas padding (mean_rgb = [0, 0, 0]) is not distorted: the reference pads after PhotoMetricDistortion
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+    int c0, c1, c2;
+    const int got = pil_gather_rgb8(ey, ex, src, Ws, c0, c1, c2);
+    if (got < 0) {
         v0 = v1 = v2 = __builtin_nanf("");
-    } else {
-        const u8* S = src + ((long)ymin * Ws + xmin) * 3;
-        int a0 = 1 << (SEG_PREC - 1), a1 = a0, a2 = a0;
-        for (int j = 0; j < ny; ++j) {
-            const u8* row = S + (long)j * Ws * 3;
-            int h0 = 1 << (SEG_PREC - 1), h1 = h0, h2 = h0;
-            for (int i = 0; i < nx; ++i) {
-                const int kx = ex[2 + i];
-                h0 += kx * row[3 * i];
-                h1 += kx * row[3 * i + 1];
-                h2 += kx * row[3 * i + 2];
-            }
-            const int ky = ey[2 + j];
-            a0 += ky * seg_clip8(h0);
-            a1 += ky * seg_clip8(h1);
-            a2 += ky * seg_clip8(h2);
-        }
-        int c0 = seg_clip8(a0), c1 = seg_clip8(a1), c2 = seg_clip8(a2);
+    } else if (got) {
         if (p.photo & 15) seg_photometric(p, c0, c1, c2);
         v0 = (float)c0;
         v1 = (float)c1;
@@ -434,7 +383,7 @@ static int seg_check_shape(const char* who, int B, int Hs, int Ws, int crop, int
 extern "C" int wc_seg_augment_workspace_ints(int B, int crop, int canvas_max, int n_cand, long* n_ints) {
     WC_CHECK_ARG(n_ints, "wc_seg_augment_workspace_ints: bad argument");
     if (int rc = seg_check_shape("wc_seg_augment_workspace_ints", B, 1, 1, crop, canvas_max, n_cand, 0)) return rc;
-    *n_ints = (long)B * 2 * canvas_max + (long)B * n_cand * 256 + (long)B * 2 * crop * SEG_ENT;
+    *n_ints = (long)B * 2 * canvas_max + (long)B * n_cand * 256 + (long)B * 2 * crop * AUG_ENT;
     return WC_OK;
 }
 

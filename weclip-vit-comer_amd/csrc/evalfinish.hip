@@ -7,27 +7,11 @@
 //                         a grid, so a pixel's source indices and weights are computed once), the uint8 prediction maps, the
 //                         colour image and the three histograms (gt, seg1 pred), (gt, msc pred), (gt, CAM label)     (:92-107)
 //   label_finish_kernel : the same outputs for a ready int64 arg-max map (the CRF leg)                               (:158-161)
-// Bilinear index arithmetic = ATen's area_pixel_compute_source_index with align_corners=False and a size-derived scale,
-// restated from evalops.hip / trainlog.hip (ev_src / ev_bilerp, resize_argmax_kernel) operation for operation: with
-// -ffp-contract=off the interpolated values, and so each arg-max, are the bits resize_argmax_kernel computes
-// (tests/test_eval_finish_gpu.py pins it).  Histogram and flag contract = confusion_hist_kernel's.
+// Bilinear arithmetic (so each arg-max is resize_argmax_kernel's) and the histogram skeleton: resample.h.  Flag contract =
+// confusion_hist_kernel's.
 // The colour of label v is the PASCAL VOC bit-interleaved map: bit j of v (j = 0..7) goes to bit 7 - j/3 of channel j % 3.
 #include "common.h"
-
-__device__ __forceinline__ void ef_src(int d, int in, float scale, int& i0, int& i1, float& l1) {
-    const float s = fmaxf(scale * (d + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - i0;
-}
-
-__device__ __forceinline__ float ef_bilerp(const float* __restrict__ S, int Ws, int y0, int y1, int x0, int x1, float ly,
-                                           float lx) {
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    return hy * (hx * S[(long)y0 * Ws + x0] + lx * S[(long)y0 * Ws + x1]) +
-           ly * (hx * S[(long)y1 * Ws + x0] + lx * S[(long)y1 * Ws + x1]);
-}
+#include "resample.h"
 
 // (r, g, b) of label v packed as r | g << 8 | b << 16 (utils/imutils.py:142-151)
 __device__ __forceinline__ unsigned int ef_colour(unsigned int v) {
@@ -40,12 +24,6 @@ __device__ __forceinline__ unsigned int ef_colour(unsigned int v) {
         v >>= 3;
     }
     return r | (g << 8) | (b << 16);
-}
-
-// One histogram's add: LDS cell (32-bit, flushed once per workgroup) or straight global atomic
-__device__ __forceinline__ void ef_count(unsigned int* sh, unsigned long long* hist, int cell) {
-    if (sh) atomicAdd(&sh[cell], 1u);
-    else atomicAdd(&hist[cell], 1ull);
 }
 
 // 4 labels -> the uint8 map and the RGB image at pixels [i, i + n) of a row-major grid.  Full groups whose first pixel is
@@ -98,10 +76,7 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const float* __restric
         lds[k] = (lds_mask >> k) & 1 ? sh + lds_cells : nullptr;
         if ((lds_mask >> k) & 1) lds_cells += cells;
     }
-    if (lds_cells) {
-        for (int i = threadIdx.x; i < lds_cells; i += 256) sh[i] = 0;
-        __syncthreads();
-    }
+    if (lds_cells) wc_hist_zero(sh, lds_cells);
     const int G = (Wl + 3) >> 2;
     const long groups = (long)Hl * G, plane = (long)Hs * Ws;
     for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
@@ -109,9 +84,9 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const float* __restric
         const int n = Wl - xb < 4 ? Wl - xb : 4;
         int y0, y1, x0[4], x1[4];
         float ly, lx[4];
-        ef_src(y, Hs, sy, y0, y1, ly);
+        wc_bil_src(y, Hs, sy, y0, y1, ly);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ef_src(xb + (k < n ? k : 0), Ws, sx, x0[k], x1[k], lx[k]);
+        for (int k = 0; k < 4; ++k) wc_bil_src(xb + (k < n ? k : 0), Ws, sx, x0[k], x1[k], lx[k]);
         float best1[4], bestm[4];
         unsigned int arg1[4] = {0, 0, 0, 0}, argm[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -120,14 +95,14 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const float* __restric
             const float* S1 = seg1 + c * plane;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float v = ef_bilerp(S1, Ws, y0, y1, x0[k], x1[k], ly, lx[k]);
+                const float v = wc_bilerp(S1, Ws, y0, y1, x0[k], x1[k], ly, lx[k]);
                 if (v > best1[k]) { best1[k] = v; arg1[k] = c; }
             }
             if (msc) {
                 const float* Sm = msc + c * plane;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float v = ef_bilerp(Sm, Ws, y0, y1, x0[k], x1[k], ly, lx[k]);
+                    const float v = wc_bilerp(Sm, Ws, y0, y1, x0[k], x1[k], ly, lx[k]);
                     if (v > bestm[k]) { bestm[k] = v; argm[k] = c; }
                 }
             }
@@ -141,27 +116,24 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const float* __restric
             if (t < 0 || t >= nc) continue;
             if (hist) {
                 if ((int)arg1[k] >= nc) *flag = 1;
-                else ef_count(lds[0], hist, (int)t * nc + (int)arg1[k]);
+                else wc_hist_count(lds[0], hist, (int)t * nc + (int)arg1[k]);
             }
             if (msc && msc_hist) {
                 if ((int)argm[k] >= nc) *flag = 1;
-                else ef_count(lds[1], msc_hist, (int)t * nc + (int)argm[k]);
+                else wc_hist_count(lds[1], msc_hist, (int)t * nc + (int)argm[k]);
             }
             if (cam && cam_hist) {
                 const long cv = cam[i + k];
                 if (cv < 0 || cv >= nc) *flag = 1;
-                else ef_count(lds[2], cam_hist, (int)t * nc + (int)cv);
+                else wc_hist_count(lds[2], cam_hist, (int)t * nc + (int)cv);
             }
         }
     }
     if (lds_cells) {
         __syncthreads();
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (!lds[k]) continue;
-            for (int i = threadIdx.x; i < cells; i += 256)
-                if (lds[k][i]) atomicAdd(&dst[k][i], (unsigned long long)lds[k][i]);
-        }
+        for (int k = 0; k < 3; ++k)
+            if (lds[k]) wc_hist_flush_cells(lds[k], dst[k], cells);
     }
 }
 
@@ -173,10 +145,7 @@ __global__ __launch_bounds__(256) void label_finish_kernel(const long* __restric
                                                             int nc, int use_lds) {
     extern __shared__ unsigned int sh[];
     const int cells = nc * nc;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < cells; i += 256) sh[i] = 0;
-        __syncthreads();
-    }
+    if (use_lds) wc_hist_zero(sh, cells);
     const int G = (W + 3) >> 2;
     const long groups = (long)H * G;
     for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long)gridDim.x * 256) {
@@ -192,26 +161,17 @@ __global__ __launch_bounds__(256) void label_finish_kernel(const long* __restric
             const long t = gt[i + k];
             if (t < 0 || t >= nc) continue;
             if (p < 0 || p >= nc) *flag = 1;
-            else ef_count(use_lds ? sh : nullptr, hist, (int)t * nc + (int)p);
+            else wc_hist_count(use_lds ? sh : nullptr, hist, (int)t * nc + (int)p);
         }
         ef_store(lab, n, i, out_u8, cmap_rgb);
     }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < cells; i += 256)
-            if (sh[i]) atomicAdd(&hist[i], (unsigned long long)sh[i]);
-    }
+    if (use_lds) wc_hist_flush(sh, hist, cells);
 }
 
 // ---------------------------------------------------------------------------------------------
 // groups_per_thread: 1 for eval_finish_kernel (a group costs 8 * C dependent-latency loads per logit tensor: the launch wants every
 // CU busy), 4 for label_finish_kernel (a group is 4 loads: fewer, longer-lived workgroups make the LDS histogram worth its flush)
-static unsigned ef_blocks(int H, int W, int groups_per_thread) {
-    const long groups = (long)H * ((W + 3) / 4), per_block = 256L * groups_per_thread;
-    long blocks = (groups + per_block - 1) / per_block;
-    if (blocks > 1024) blocks = 1024;                      // (a workgroup then counts n / 1024 pixels: 32-bit cells hold 2^42 pixels)
-    return (unsigned)blocks;
-}
+static unsigned ef_blocks(int H, int W, int groups_per_thread) { return wc_hist_blocks((long)H * ((W + 3) / 4), groups_per_thread); }
 
 extern "C" int wc_eval_finish(const float* seg1, const float* msc, const long* cam, const long* gt, void* pred1_u8, void* predm_u8,
                               void* cmap_rgb, long* hist, long* msc_hist, long* cam_hist, int* flag, int C, int Hs, int Ws, int Hl,

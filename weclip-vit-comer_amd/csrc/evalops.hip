@@ -6,25 +6,10 @@
 //   flip_avg_kernel        : msc (+)= w * (resize(seg[0]) + flip(resize(seg[1]))) / 2               (:67-68, 84-86, 88)
 //   resize_argmax_kernel   : argmax_c F.interpolate(seg, size=labels)[c]   without the (nc, H, W) tensor (:90-94)
 //   confusion_hist_kernel  : hist[t * nc + p] += 1 over pixels with 0 <= t < nc                     (evaluate.py:10-16)
-// Bilinear index arithmetic = ATen's area_pixel_compute_source_index with align_corners=False: src =
-// max(scale * (dst + 0.5) - 0.5, 0) where `scale` is in/out for size= calls and 1/scale_factor for scale_factor=
-// calls (F.interpolate keeps the user's factor when recompute_scale_factor is unset) -- the caller passes it.
+// Bilinear arithmetic: resample.h.  `scale` is in/out for size= calls and 1/scale_factor for scale_factor= calls
+// (F.interpolate keeps the user's factor when recompute_scale_factor is unset) -- the caller passes it.
 #include "common.h"
-
-__device__ __forceinline__ void ev_src(int d, int in, float scale, int& i0, int& i1, float& l1) {
-    const float s = fmaxf(scale * (d + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - i0;
-}
-
-__device__ __forceinline__ float ev_bilerp(const float* __restrict__ S, int Ws, int y0, int y1, int x0, int x1, float ly,
-                                           float lx) {
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    return hy * (hx * S[(long)y0 * Ws + x0] + lx * S[(long)y0 * Ws + x1]) +
-           ly * (hx * S[(long)y1 * Ws + x0] + lx * S[(long)y1 * Ws + x1]);
-}
+#include "resample.h"
 
 // dst (2, C, Hd, Wd): [0] = bilinear(src (C, Hs, Ws)), [1] = [0] flipped along x.  identity != 0: plain copy + flip.
 __global__ __launch_bounds__(256) void scale_flip_pair_kernel(const float* __restrict__ src, float* __restrict__ dst, int C,
@@ -39,9 +24,9 @@ __global__ __launch_bounds__(256) void scale_flip_pair_kernel(const float* __res
     } else {
         int y0, y1, x0, x1;
         float ly, lx;
-        ev_src(y, Hs, sy, y0, y1, ly);
-        ev_src(x, Ws, sx, x0, x1, lx);
-        v = ev_bilerp(S, Ws, y0, y1, x0, x1, ly, lx);
+        wc_bil_src(y, Hs, sy, y0, y1, ly);
+        wc_bil_src(x, Ws, sx, x0, x1, lx);
+        v = wc_bilerp(S, Ws, y0, y1, x0, x1, ly, lx);
     }
     const long plane = (long)Hd * Wd;
     dst[(long)c * plane + (long)y * Wd + x] = v;
@@ -64,11 +49,11 @@ __global__ __launch_bounds__(256) void flip_avg_kernel(const float* __restrict__
     } else {
         int y0, y1, x0, x1, xf0, xf1;
         float ly, lx, lxf;
-        ev_src(y, Hs, sy, y0, y1, ly);
-        ev_src(x, Ws, sx, x0, x1, lx);
-        ev_src(Wd - 1 - x, Ws, sx, xf0, xf1, lxf);
-        a = ev_bilerp(S0, Ws, y0, y1, x0, x1, ly, lx);
-        b = ev_bilerp(S1, Ws, y0, y1, xf0, xf1, ly, lxf);
+        wc_bil_src(y, Hs, sy, y0, y1, ly);
+        wc_bil_src(x, Ws, sx, x0, x1, lx);
+        wc_bil_src(Wd - 1 - x, Ws, sx, xf0, xf1, lxf);
+        a = wc_bilerp(S0, Ws, y0, y1, x0, x1, ly, lx);
+        b = wc_bilerp(S1, Ws, y0, y1, xf0, xf1, ly, lxf);
     }
     const long o = ((long)c * Hd + y) * Wd + x;
     const float v = wgt * ((a + b) / 2.f);
@@ -82,15 +67,9 @@ __global__ __launch_bounds__(256) void resize_argmax_kernel(const float* __restr
     if (x >= Wd || y >= Hd) return;
     int y0, y1, x0, x1;
     float ly, lx;
-    ev_src(y, Hs, sy, y0, y1, ly);
-    ev_src(x, Ws, sx, x0, x1, lx);
-    float best = -INFINITY;
-    int arg = 0;
-    for (int c = 0; c < C; ++c) {
-        const float v = ev_bilerp(seg + (long)c * Hs * Ws, Ws, y0, y1, x0, x1, ly, lx);
-        if (v > best) { best = v; arg = c; }
-    }
-    pred[(long)y * Wd + x] = arg;
+    wc_bil_src(y, Hs, sy, y0, y1, ly);
+    wc_bil_src(x, Ws, sx, x0, x1, lx);
+    pred[(long)y * Wd + x] = wc_resize_argmax_at(seg, C, Hs, Ws, y0, y1, x0, x1, ly, lx);
 }
 
 // hist[t * nc + p] += #pixels with true label t in [0, nc) and prediction p.  Integer atomics: the result does not
@@ -101,22 +80,14 @@ __global__ __launch_bounds__(256) void confusion_hist_kernel(const long* __restr
                                                               long n, int nc, int use_lds) {
     extern __shared__ unsigned int sh[];
     const int cells = nc * nc;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < cells; i += 256) sh[i] = 0;
-        __syncthreads();
-    }
+    if (use_lds) wc_hist_zero(sh, cells);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const long t = lt[i], p = lp[i];
         if (t < 0 || t >= nc) continue;
         if (p < 0 || p >= nc) { *flag = 1; continue; }
-        if (use_lds) atomicAdd(&sh[t * nc + p], 1u);
-        else atomicAdd(&hist[t * nc + p], 1ull);
+        wc_hist_count(use_lds ? sh : nullptr, hist, (int)t * nc + (int)p);
     }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < cells; i += 256)
-            if (sh[i]) atomicAdd(&hist[i], (unsigned long long)sh[i]);
-    }
+    if (use_lds) wc_hist_flush(sh, hist, cells);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -154,9 +125,7 @@ extern "C" int wc_confusion_hist(const long* label_true, const long* label_pred,
     if (n == 0) return WC_OK;
     const size_t lds = (size_t)nc * nc * sizeof(unsigned int);
     const int use_lds = lds <= 64 * 1024;
-    long blocks = (n + 256 * 16 - 1) / (256 * 16);         // ~16 pixels per thread, so the LDS histogram is worth its flush
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(confusion_hist_kernel, dim3((unsigned)blocks), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, label_true,
+    hipLaunchKernelGGL(confusion_hist_kernel, dim3(wc_hist_blocks(n, 16)), dim3(256), use_lds ? lds : 0, (hipStream_t)stream, label_true,
                        label_pred, (unsigned long long*)hist, flag, n, nc, use_lds);
     WC_LAUNCH_CHECK("confusion_hist_kernel");
     return WC_OK;

@@ -10,16 +10,9 @@
 //   seg_loss_bwd_y_kernel   : the same gradient formed inside the Y pass (no (B, nc, H, W) tensor), + seg_bwd_x_kernel
 //   seg_loss_fused_kernel   : TRAINING: loss and gradient in one pixel pass (nc <= 24), + seg_count / seg_bwd_x2 kernels
 #include "common.h"
+#include "resample.h"
 
 #define SEG_MAX_C 96
-
-__device__ __forceinline__ void bil_index(int d, int in, float scale, int& i0, int& i1, float& l1) {
-    float s = fmaxf(scale * (d + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - i0;
-}
 
 template <bool BWD>
 __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__ seg, const long* __restrict__ label,
@@ -34,8 +27,8 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
         const long lab = label[((long)b * H + y) * W + x];
         int y0, y1, x0, x1;
         float ly, lx;
-        bil_index(y, h, sy, y0, y1, ly);
-        bil_index(x, w, sx, x0, x1, lx);
+        wc_bil_src(y, h, sy, y0, y1, ly);
+        wc_bil_src(x, w, sx, x0, x1, lx);
         const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
         const float* S = seg + (long)b * nc * h * w;
         const long o00 = (long)y0 * w + x0, o01 = (long)y0 * w + x1, o10 = (long)y1 * w + x0, o11 = (long)y1 * w + x1;
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_y_kernel(const float* __rest
     if (x >= W || ys >= h) return;
     int x0, x1;
     float lx;
-    bil_index(x, w, sx, x0, x1, lx);
+    wc_bil_src(x, w, sx, x0, x1, lx);
     const float iy = 1.0f / sy;
     int y_lo = (int)floorf((ys - 1.5f) * iy) - 1, y_hi = (int)ceilf((ys + 1.5f) * iy) + 1;
     if (y_lo < 0) y_lo = 0;
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(256) void seg_loss_bwd_y_kernel(const float* __rest
         }
         int y0, y1;
         float ly;
-        bil_index(y, h, sy, y0, y1, ly);
+        wc_bil_src(y, h, sy, y0, y1, ly);
         const float wy = (y0 == ys ? 1.f - ly : 0.f) + (y1 == ys ? ly : 0.f);       // wave-uniform
         long lab = labs[0];
 #pragma unroll
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(256) void seg_bwd_x_kernel(const float* __restrict_
     for (int x = x_lo; x <= x_hi; ++x) {
         int x0, x1;
         float lx;
-        bil_index(x, Ws, sx, x0, x1, lx);
+        wc_bil_src(x, Ws, sx, x0, x1, lx);
         const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
         acc = fmaf(wx, T[x], acc);
     }
@@ -342,7 +335,7 @@ __global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __rest
     if (x < W && ys < h) {
         int x0, x1;
         float lx;
-        bil_index(x, w, sx, x0, x1, lx);
+        wc_bil_src(x, w, sx, x0, x1, lx);
         const int y1s = ys + (ys < h - 1 ? 1 : 0);
         const float* S = seg + (long)b * nc * h * w;
         float av[NCT], dv[NCT], accT[NCT], accB[NCT];
@@ -370,7 +363,7 @@ __global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __rest
             }
             int y0, y1;
             float ly;
-            bil_index(y, h, sy, y0, y1, ly);
+            wc_bil_src(y, h, sy, y0, y1, ly);
             long lab = labs[0];
 #pragma unroll
             for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;
@@ -451,7 +444,7 @@ __global__ __launch_bounds__(256) void seg_bwd_x2_kernel(const float* __restrict
         for (int x = x_lo; x <= x_hi; ++x) {
             int x0, x1;
             float lx;
-            bil_index(x, Ws, sx, x0, x1, lx);
+            wc_bil_src(x, Ws, sx, x0, x1, lx);
             const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
             acc = fmaf(wx, v[x + (x >> 4)], acc);
         }
@@ -509,7 +502,7 @@ __global__ __launch_bounds__(256) void ce_loss_fused_kernel(const float* __restr
     if (x < W && ys < h) {
         int x0, x1;
         float lx;
-        bil_index(x, w, sx, x0, x1, lx);
+        wc_bil_src(x, w, sx, x0, x1, lx);
         const int y1s = ys + (ys < h - 1 ? 1 : 0);
         const float* S = seg + (long)b * nc * h * w;
         const long r0 = (long)ys * w, r1 = (long)y1s * w;
@@ -536,7 +529,7 @@ __global__ __launch_bounds__(256) void ce_loss_fused_kernel(const float* __restr
             }
             int y0, y1;
             float ly;
-            bil_index(y, h, sy, y0, y1, ly);
+            wc_bil_src(y, h, sy, y0, y1, ly);
             long lab = labs[0];
 #pragma unroll
             for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;

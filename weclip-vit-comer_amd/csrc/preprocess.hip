@@ -5,8 +5,8 @@
 //   generate_cams_voc12.py:84-93   img_ms_and_flip: (h, w) = scale * original size rounded up to the patch size, [image, flip]
 //   pytorch_grad_cam/utils/image.py:51-61  scale_cam_image([cam], (ori_w, ori_h)): min-max, cv2.resize (bilinear), float16
 // Kernels:
-//   clipprep_coeff_kernel   Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BICUBIC filter, both axes, in double
-//                           precision: per output coordinate {first tap, tap count, 22-bit fixed-point weights}
+//   clipprep_coeff_kernel   Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BICUBIC filter, both axes (resample.h):
+//                           per output coordinate {first tap, tap count, 22-bit fixed-point weights}
 //   clipprep_hpass_kernel   horizontal pass: uint8 HWC (B,H0,W0,3) -> uint8 (B,H0,w,3); integer arithmetic only
 //   clipprep_vpass_kernel   vertical pass -> uint8 (B,h,w,3) (optional), then x / 255, - mean, / std in fp32 -> CHW, and the
 //                           horizontally flipped copy (optional)
@@ -14,57 +14,21 @@
 //                           to the pair's own (ori_h, ori_w), fp16 (round to nearest even)
 // The tap loads of a thread are issued together: indices are clamped into the row, taps beyond the window carry weight 0.
 #include "common.h"
+#include "resample.h"
 
-#define PREP_PREC 22
-#define PREP_KMAX 33        // 2 * ceil(2 * 8) + 1 taps: down-scaling by at most 8
-#define PREP_ENT 36         // {first, count, PREP_KMAX weights, pad}
+#define PREP_KMAX 33                    // 2 * ceil(2 * 8) + 1 taps: down-scaling by at most 8
+#define PREP_ENT PIL_ENT(PREP_KMAX)     // 36
 #define CAM_MAX_TOKENS 4096 // refined CAM of one pair held in LDS (a 1024 x 1024 input at patch size 16)
 
 typedef unsigned char u8;
-
-// Pillow's bicubic_filter (a = -0.5)
-__device__ __forceinline__ double prep_bicubic(double x) {
-    const double a = -0.5;
-    x = x < 0.0 ? -x : x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
 
 // grid (cdiv(max(h, w), 256), 2).  tab[(axis * OM + o) * PREP_ENT ...], OM = max(h, w); axis 0 = vertical (H0 -> h).
 __global__ __launch_bounds__(256) void clipprep_coeff_kernel(int* __restrict__ tab, int H0, int W0, int h, int w, int OM) {
     const int o = blockIdx.x * 256 + threadIdx.x, axis = blockIdx.y;
     const int in_size = axis ? W0 : H0, out_size = axis ? w : h;
     if (o >= out_size) return;
-    int* e = tab + ((long)axis * OM + o) * PREP_ENT;
-    // precompute_coeffs(inSize, in0 = 0, in1 = inSize, outSize, BICUBIC) for output coordinate o
-    const double scale = (double)((float)in_size - 0.f) / out_size;
-    const double fscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * fscale;
-    const double center = 0.0 + (o + 0.5) * scale;
-    const double ss = 1.0 / fscale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > in_size) xmax = in_size;
-    int n = xmax - xmin;
-    if (n > PREP_KMAX) n = PREP_KMAX;                   // unreachable: the host refuses down-scaling beyond 8
-    double ww = 0.0;
-    for (int x = 0; x < n; ++x) ww += prep_bicubic(((double)(x + xmin) - center + 0.5) * ss);
-    e[0] = xmin;
-    e[1] = n;
-    for (int x = 0; x < PREP_KMAX; ++x) {
-        double v = x < n ? prep_bicubic(((double)(x + xmin) - center + 0.5) * ss) : 0.0;
-        if (ww != 0.0) v = v / ww;
-        // normalize_coeffs_8bpc: round half away from zero
-        e[2 + x] = v < 0.0 ? (int)(-0.5 + v * (double)(1 << PREP_PREC)) : (int)(0.5 + v * (double)(1 << PREP_PREC));
-    }
-    e[2 + PREP_KMAX] = 0;
-}
-
-__device__ __forceinline__ int prep_clip8(int v) {
-    v >>= PREP_PREC;                                    // arithmetic shift: a negative sum clips to 0
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
+    // a window beyond PREP_KMAX taps is clamped to the table; unreachable: the host refuses down-scaling beyond 8
+    pil_coeffs<PilBicubic, PREP_KMAX>(o, in_size, out_size, tab + ((long)axis * OM + o) * PREP_ENT);
 }
 
 // grid (cdiv(w, 64), cdiv(H0, 4), B): one thread per pixel of the intermediate
@@ -76,7 +40,7 @@ __global__ __launch_bounds__(256) void clipprep_hpass_kernel(const u8* __restric
     const int* e = tab + ((long)OM + x) * PREP_ENT;
     const int xmin = e[0];
     const u8* row = src + ((long)b * H0 + y) * W0 * 3;
-    int a0 = 1 << (PREP_PREC - 1), a1 = a0, a2 = a0;
+    int a0 = 1 << (PIL_PREC - 1), a1 = a0, a2 = a0;
     const int nk = KT ? KT : ksize;
 #pragma unroll
     for (int i = 0; i < nk; ++i) {
@@ -86,9 +50,9 @@ __global__ __launch_bounds__(256) void clipprep_hpass_kernel(const u8* __restric
         a2 += k * row[sx + 2];
     }
     u8* D = mid + (((long)b * H0 + y) * w + x) * 3;
-    D[0] = (u8)prep_clip8(a0);
-    D[1] = (u8)prep_clip8(a1);
-    D[2] = (u8)prep_clip8(a2);
+    D[0] = (u8)pil_clip8(a0);
+    D[1] = (u8)pil_clip8(a1);
+    D[2] = (u8)pil_clip8(a2);
 }
 
 // grid (cdiv(w, 64), cdiv(h, 4), B): one thread per output pixel
@@ -102,7 +66,7 @@ __global__ __launch_bounds__(256) void clipprep_vpass_kernel(const u8* __restric
     const int* e = tab + (long)y * PREP_ENT;
     const int ymin = e[0];
     const u8* col = mid + ((long)b * H0 * w + x) * 3;
-    int a0 = 1 << (PREP_PREC - 1), a1 = a0, a2 = a0;
+    int a0 = 1 << (PIL_PREC - 1), a1 = a0, a2 = a0;
     const int nk = KT ? KT : ksize;
 #pragma unroll
     for (int j = 0; j < nk; ++j) {
@@ -112,7 +76,7 @@ __global__ __launch_bounds__(256) void clipprep_vpass_kernel(const u8* __restric
         a1 += k * p[1];
         a2 += k * p[2];
     }
-    const int c0 = prep_clip8(a0), c1 = prep_clip8(a1), c2 = prep_clip8(a2);
+    const int c0 = pil_clip8(a0), c1 = pil_clip8(a1), c2 = pil_clip8(a2);
     if (out_u8) {
         u8* U = out_u8 + (((long)b * h + y) * w + x) * 3;
         U[0] = (u8)c0;
@@ -192,8 +156,7 @@ extern "C" int wc_clip_preprocess(const void* src_u8, float* dst, float* dst_fli
 
 // ---- output stage ------------------------------------------------------------------------------------------------
 // grid (cdiv(max_pixels, 256), P).  sizes (P,2) int32 {ori_h, ori_w}; offsets (P) int64: first element of pair p in `out`.
-// Bilinear rule: src = max((dst + 0.5) * in / out - 0.5, 0), second tap clamped to the last row / column -- OpenCV's
-// INTER_LINEAR for float images and F.interpolate(mode="bilinear", align_corners=False), in fp32.
+// Bilinear rule: resample.h -- OpenCV's INTER_LINEAR for float images and F.interpolate(mode="bilinear", align_corners=False), in fp32.
 __global__ __launch_bounds__(256) void cam_scale_resize_kernel(const float* __restrict__ cam, const int* __restrict__ sizes,
                                                                const long long* __restrict__ offsets, __half* __restrict__ out, long out_elems,
                                                                int gh, int gw) {
@@ -217,15 +180,14 @@ __global__ __launch_bounds__(256) void cam_scale_resize_kernel(const float* __re
     if (i >= (long)oh * ow) return;
     const int y = (int)(i / ow), x = (int)(i - (long)y * ow);
     const float sy = (float)gh / (float)oh, sx = (float)gw / (float)ow;
-    const float fy = fmaxf(sy * ((float)y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sx * ((float)x + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)fy, gh - 1), x0 = min((int)fx, gw - 1);
-    const int y1 = min(y0 + 1, gh - 1), x1 = min(x0 + 1, gw - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    wc_bil_src(y, gh, sy, y0, y1, ly);
+    wc_bil_src(x, gw, sx, x0, x1, lx);
     const float a = (tile[y0 * gw + x0] - lo) / den, b = (tile[y0 * gw + x1] - lo) / den;
     const float c = (tile[y1 * gw + x0] - lo) / den, d = (tile[y1 * gw + x1] - lo) / den;
-    const float v = hy * (hx * a + lx * b) + ly * (hx * c + lx * d);
-    const long o = offsets[p] + i;
-    if (o >= 0 && o < out_elems) out[o] = __float2half_rn(v);             // a table that disagrees with `out` never writes outside it
+    const long o = offsets[p] + i;                                         // a table that disagrees with `out` never writes outside it
+    if (o >= 0 && o < out_elems) out[o] = __float2half_rn(wc_lerp4(a, b, c, d, ly, lx));
 }
 
 // normalise = 0: the plain resize of GradCAM.__call__(target_size=...) (cv2.resize of the map as it is)
@@ -239,13 +201,13 @@ __global__ __launch_bounds__(256) void cam_resize_kernel(const float* __restrict
     const float* C = cam + (long)p * gh * gw;
     const int y = (int)(i / ow), x = (int)(i - (long)y * ow);
     const float sy = (float)gh / (float)oh, sx = (float)gw / (float)ow;
-    const float fy = fmaxf(sy * ((float)y + 0.5f) - 0.5f, 0.f), fx = fmaxf(sx * ((float)x + 0.5f) - 0.5f, 0.f);
-    const int y0 = min((int)fy, gh - 1), x0 = min((int)fx, gw - 1);
-    const int y1 = min(y0 + 1, gh - 1), x1 = min(x0 + 1, gw - 1);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    int y0, y1, x0, x1;
+    float ly, lx;
+    wc_bil_src(y, gh, sy, y0, y1, ly);
+    wc_bil_src(x, gw, sx, x0, x1, lx);
     const float a = C[y0 * gw + x0], b = C[y0 * gw + x1], c = C[y1 * gw + x0], d = C[y1 * gw + x1];
     const long o = offsets[p] + i;
-    if (o >= 0 && o < out_elems) out[o] = hy * (hx * a + lx * b) + ly * (hx * c + lx * d);
+    if (o >= 0 && o < out_elems) out[o] = wc_lerp4(a, b, c, d, ly, lx);
 }
 
 static int cam_check(const char* who, const void* cam, const void* sizes, const void* offsets, const void* out, long out_elems, int P,

@@ -3,17 +3,14 @@
 //     pytorch_grad_cam/utils/image.py:57)                      -> align_corners = 0
 //   F.interpolate(imgs, bilinear, align_corners=True)          (WeCLIP_model/PAR.py:67)
 //   F.interpolate(segs, bilinear, align_corners=False)         (scripts/dist_clip_voc.py:250)
-// Index arithmetic follows ATen's area_pixel_compute_source_index (half-pixel centres,
-// negative source clamped to 0), which equals OpenCV's INTER_LINEAR for float data.
+// Index arithmetic and lerp: resample.h.
 #include "common.h"
+#include "resample.h"
 
 __device__ __forceinline__ void src_index(int d, int in, float scale, int align, int& i0, int& i1,
                                           float& l1) {
-    float s = align ? scale * d : fmaxf(scale * (d + 0.5f) - 0.5f, 0.f);
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - i0;
+    if (align) wc_bil_src_aligned(d, in, scale, i0, i1, l1);
+    else wc_bil_src(d, in, scale, i0, i1, l1);
 }
 
 __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__ src,
@@ -27,10 +24,7 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const float* __restrict__
     src_index(y, Hs, sy, align, y0, y1, ly);
     src_index(x, Ws, sx, align, x0, x1, lx);
     const float* S = src + (long)blockIdx.z * Hs * Ws;
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    const float v = hy * (hx * S[(long)y0 * Ws + x0] + lx * S[(long)y0 * Ws + x1]) +
-                    ly * (hx * S[(long)y1 * Ws + x0] + lx * S[(long)y1 * Ws + x1]);
-    dst[((long)blockIdx.z * Hd + y) * Wd + x] = v;
+    dst[((long)blockIdx.z * Hd + y) * Wd + x] = wc_bilerp(S, Ws, y0, y1, x0, x1, ly, lx);
 }
 
 // Backward of the bilinear up-sampling, separable and deterministic (ATen's backward scatters with

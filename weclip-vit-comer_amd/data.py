@@ -67,6 +67,20 @@ MEAN = (123.675, 116.28, 103.53)       # datasets/transforms.py:8
 STD = (58.395, 57.12, 57.375)
 
 
+def _check_rescale(who, b, H, W, rh, rw):
+    """Precondition of the Pillow tables (csrc/resample.h) for image b: (H, W) -> (rh, rw).  Raises, never poisons."""
+    if rh < 1 or rw < 1 or H > 4 * rh or W > 4 * rw:
+        raise RuntimeError(f"{who}: image {b} ({H}x{W} -> {rh}x{rw}): rescaled size must be >= 1 and "
+                           "down-scaling at most 4x")
+
+
+def _workspace(ws, n_ints, device):
+    """`ws` if it holds n_ints int32 on `device`, else a new buffer that does."""
+    if ws is None or ws.numel() < n_ints or ws.device != device:
+        ws = torch.empty(n_ints, device=device, dtype=torch.int32)
+    return ws
+
+
 class DeviceAugment:
     """The reference's train-time augmentation (datasets/voc.py:108-143: random_scaling -> random_fliplr -> random_crop
     -> normalize_img -> CHW) with the random draws on the host and the pixel work in HIP kernels (csrc/augment.hip):
@@ -113,6 +127,15 @@ class DeviceAugment:
         """Host-side random parameters of one batch -> int32 tensor (B, 8) in the kernel's record layout."""
         return self.pack([self.draw_one(H, W) for _ in range(B)])
 
+    def _buffers(self, B, device):
+        """The output of one call, with the coefficient workspace grown to the batch."""
+        import ctypes
+        from . import _lib as L
+        n = ctypes.c_long(0)
+        L.lib().wc_augment_workspace_ints(B, self.crop, ctypes.byref(n))
+        self._ws = _workspace(self._ws, n.value, device)
+        return torch.empty(B, 3, self.crop, self.crop, device=device, dtype=torch.float32)
+
     def __call__(self, images_u8, params=None):
         """images_u8 (B,H,W,3) uint8 CUDA; params: a draw() result (default: a fresh draw).  -> (B,3,crop,crop) f32."""
         import ctypes
@@ -128,11 +151,7 @@ class DeviceAugment:
             if int(rhw.min()) < 1 or H > 4 * int(rhw[:, 0].min()) or W > 4 * int(rhw[:, 1].min()):
                 raise RuntimeError("DeviceAugment: rescaled size must be >= 1 and down-scaling at most 4x")
         p = params.pin_memory().to(images_u8.device, non_blocking=True) if not params.is_cuda else params
-        out = torch.empty(B, 3, self.crop, self.crop, device=images_u8.device, dtype=torch.float32)
-        n = ctypes.c_long(0)
-        L.lib().wc_augment_workspace_ints(B, self.crop, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != images_u8.device:
-            self._ws = torch.empty(n.value, device=images_u8.device, dtype=torch.int32)
+        out = self._buffers(B, images_u8.device)
         L.lib().wc_augment_normalize(L.ptr(images_u8.contiguous(), torch.uint8, "images"), L.ptr(p, torch.int32, "params"),
                                      L.ptr(out), L.ptr(self._ws, torch.int32), B, H, W, self.crop,
                                      (ctypes.c_float * 3)(*self.mean), (ctypes.c_float * 3)(*self.std), L.stream())
@@ -141,10 +160,7 @@ class DeviceAugment:
     def check_ragged(self, params, sizes):
         """Host-side precondition of the kernels for host-resident records and a list of (H, W): raises, never poisons."""
         for b, (H, W) in enumerate(sizes):
-            rh, rw = int(params[b, 2]), int(params[b, 3])
-            if rh < 1 or rw < 1 or H > 4 * rh or W > 4 * rw:
-                raise RuntimeError(f"DeviceAugment: image {b} ({H}x{W} -> {rh}x{rw}): rescaled size must be >= 1 and "
-                                   "down-scaling at most 4x")
+            _check_rescale("DeviceAugment", b, H, W, int(params[b, 2]), int(params[b, 3]))
 
     def ragged(self, src_u8, offsets, sizes, params):
         """A batch of images of different sizes (csrc/augment.hip, wc_augment_normalize_ragged): src_u8 flat uint8 CUDA, the
@@ -156,11 +172,7 @@ class DeviceAugment:
         B = int(offsets.shape[0])
         if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or tuple(sizes.shape) != (B, 2) or tuple(params.shape) != (B, 8):
             raise RuntimeError("DeviceAugment.ragged expects a flat uint8 source, (B) offsets, (B,2) sizes, (B,8) params")
-        out = torch.empty(B, 3, self.crop, self.crop, device=src_u8.device, dtype=torch.float32)
-        n = ctypes.c_long(0)
-        L.lib().wc_augment_workspace_ints(B, self.crop, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != src_u8.device:
-            self._ws = torch.empty(n.value, device=src_u8.device, dtype=torch.int32)
+        out = self._buffers(B, src_u8.device)
         L.lib().wc_augment_normalize_ragged(L.ptr(src_u8, torch.uint8, "src"), src_u8.numel(), L.ptr(offsets, torch.int64, "offsets"),
                                             L.ptr(sizes, torch.int32, "sizes"), L.ptr(params, torch.int32, "params"), L.ptr(out),
                                             L.ptr(self._ws, torch.int32), B, self.crop, (ctypes.c_float * 3)(*self.mean),
@@ -312,6 +324,17 @@ class DeviceSegAugment:
         hi = self.range[1] if self.range else 1.0
         return max(self.crop, int(hi * H), int(hi * W))
 
+    def _buffers(self, B, canvas_max, dev):
+        """(image, label, img_box, sel) of one call, with the workspace grown to the batch."""
+        import ctypes
+        from . import _lib as L
+        n = ctypes.c_long(0)
+        L.lib().wc_seg_augment_workspace_ints(B, self.crop, canvas_max, self.n_cand, ctypes.byref(n))
+        self._ws = _workspace(self._ws, n.value, dev)
+        return (torch.empty(B, 3, self.crop, self.crop, device=dev, dtype=torch.float32),
+                torch.empty(B, self.crop, self.crop, device=dev, dtype=torch.int64),
+                torch.empty(B, 4, device=dev, dtype=torch.int32), torch.empty(B, 4, device=dev, dtype=torch.int32))
+
     def __call__(self, images_u8, labels_u8, params=None):
         """images_u8 (B,H,W,3) / labels_u8 (B,H,W) uint8 CUDA; params: a draw() / pack() result, host or device resident
         (default: a fresh draw).  -> (image (B,3,crop,crop) f32, label (B,crop,crop) int64, img_box (B,4) int32).
@@ -339,14 +362,7 @@ class DeviceSegAugment:
         dev = images_u8.device
         rec = rec if rec.is_cuda else rec.pin_memory().to(dev, non_blocking=True)
         cand = cand if cand.is_cuda else cand.pin_memory().to(dev, non_blocking=True)
-        out = torch.empty(B, 3, self.crop, self.crop, device=dev, dtype=torch.float32)
-        lab = torch.empty(B, self.crop, self.crop, device=dev, dtype=torch.int64)
-        sel = torch.empty(B, 4, device=dev, dtype=torch.int32)
-        box = torch.empty(B, 4, device=dev, dtype=torch.int32)
-        n = ctypes.c_long(0)
-        L.lib().wc_seg_augment_workspace_ints(B, self.crop, cm, self.n_cand, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != dev:
-            self._ws = torch.empty(n.value, device=dev, dtype=torch.int32)
+        out, lab, box, sel = self._buffers(B, cm, dev)
         L.lib().wc_seg_augment(L.ptr(images_u8.contiguous(), torch.uint8, "images"), L.ptr(labels_u8.contiguous(), torch.uint8, "labels"),
                                L.ptr(rec, torch.int32, "params"), L.ptr(cand, torch.int32, "candidates"), L.ptr(out),
                                L.ptr(lab, torch.int64), L.ptr(sel), L.ptr(box), L.ptr(self._ws, torch.int32), B, H, W, self.crop,
@@ -360,9 +376,7 @@ class DeviceSegAugment:
         cm = self.crop
         for b, (H, W) in enumerate(sizes):
             rh, rw = int(rec[b, 2]), int(rec[b, 3])
-            if rh < 1 or rw < 1 or H > 4 * rh or W > 4 * rw:
-                raise RuntimeError(f"DeviceSegAugment: image {b} ({H}x{W} -> {rh}x{rw}): rescaled size must be >= 1 and "
-                                   "down-scaling at most 4x")
+            _check_rescale("DeviceSegAugment", b, H, W, rh, rw)
             lim = torch.tensor([max(rh, self.crop) - self.crop, max(rw, self.crop) - self.crop], dtype=cand.dtype)
             if int(cand[b].min()) < 0 or bool((cand[b] > lim).any()):
                 raise RuntimeError("DeviceSegAugment: candidate box outside the padded canvas")
@@ -382,14 +396,7 @@ class DeviceSegAugment:
             raise RuntimeError("DeviceSegAugment.ragged expects flat uint8 buffers, the labels one third of the images")
         if tuple(sizes.shape) != (B, 2) or tuple(rec.shape) != (B, 16) or tuple(cand.shape) != (B, self.n_cand, 2):
             raise RuntimeError("DeviceSegAugment.ragged: (B,2) sizes, (B,16) records, (B,n_cand,2) candidates")
-        out = torch.empty(B, 3, self.crop, self.crop, device=dev, dtype=torch.float32)
-        lab = torch.empty(B, self.crop, self.crop, device=dev, dtype=torch.int64)
-        sel = torch.empty(B, 4, device=dev, dtype=torch.int32)
-        box = torch.empty(B, 4, device=dev, dtype=torch.int32)
-        n = ctypes.c_long(0)
-        L.lib().wc_seg_augment_workspace_ints(B, self.crop, int(canvas_max), self.n_cand, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != dev:
-            self._ws = torch.empty(n.value, device=dev, dtype=torch.int32)
+        out, lab, box, sel = self._buffers(B, int(canvas_max), dev)
         L.lib().wc_seg_augment_ragged(L.ptr(src_u8, torch.uint8, "images"), L.ptr(lab_u8, torch.uint8, "labels"), src_u8.numel(),
                                       L.ptr(offsets, torch.int64, "offsets"), L.ptr(sizes, torch.int32, "sizes"),
                                       L.ptr(rec, torch.int32, "params"), L.ptr(cand, torch.int32, "candidates"), L.ptr(out),
