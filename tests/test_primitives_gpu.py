@@ -188,6 +188,69 @@ def test_gemm_few_rows(ops, M, N, K):
     assert _rel(out.cpu().double(), x.double() @ w32.double().t()) < 5e-6
 
 
+@pytest.mark.parametrize("family,M,N,K", [("pp", 20480 + 16, 512, 128), ("skinny", 16, 256, 128),
+                                          ("tile2", 300, 200, 128), ("tile4", 300, 200, 192)])
+def test_gemm_every_epilogue_kind_of_every_family(ops, family, M, N, K):
+    """wc_gemm_f16 picks its kernel from one table per family, indexed by the epilogue kind (0 plain, 1 side input, 2 erf GELU,
+    3 erf GELU' with side input).  The smallest shape of each family -- 256x256 (81 x 2 tiles, ragged last row tile), few rows,
+    128x128 with two stages (K / 64 < 3) and with the 4-stage ring -- runs every kind through the narrow (fp32) and the wide
+    (fp16-only) epilogue against fp64, and the timers must have recorded exactly the instantiation the table names."""
+    from weclip_vit_comer_amd import _lib as L
+    plan = L.lib().cdll.wc_gemm_plan(M, N, K, 1, 1)
+    assert (plan in (1, 2)) if family == "pp" else plan == 0
+    name = {"pp": lambda ek: "gemm_f16_pp_kernel<%d, %d>" % (ek, 10 if ek < 2 else 8),
+            "skinny": lambda ek: "gemm_skinny_kernel<%d>" % ek,
+            "tile2": lambda ek: "gemm_f16_kernel<%d, 2>" % ek,
+            "tile4": lambda ek: "gemm_f16_kernel<%d, 4>" % ek}[family]
+    g = torch.Generator().manual_seed(M + N + K)
+    a = torch.randn(M, K, generator=g).half().cuda()
+    w = (torch.randn(N, K, generator=g) * 0.05).half().cuda()
+    bias = torch.randn(N, generator=g).cuda()
+    saved = torch.randn(M, N, generator=g).half().cuda()
+    u = torch.randn(M, N, generator=g).cuda()
+    ref = a.double() @ w.double().t()
+    refb = ref + bias.double()
+    ud = u.double()
+    sg = torch.sigmoid(1.702 * ud)
+    want = {0: refb, 6: torch.nn.functional.gelu(refb), 5: ref * (saved.double() > 0), 4: ref * (sg * (1 + 1.702 * ud * (1 - sg))),
+            7: ref * (0.5 * (1 + torch.erf(ud / 2 ** 0.5)) + ud * torch.exp(-0.5 * ud * ud) / (2 * torch.pi) ** 0.5)}
+    side = {0: dict(bias=bias), 6: dict(bias=bias), 5: dict(auxh=saved, ldaux=N), 4: dict(aux=u, rpg=1, ldaux=N),
+            7: dict(aux=u, rpg=1, ldaux=N)}
+    ek_of = {0: 0, 5: 1, 4: 1, 6: 2, 7: 3}
+
+    def run(act, **outs):
+        ops.KernelTimer.enable(1)
+        try:
+            ops.gemm(a, w, M, N, K, act=act, **side[act], **outs)
+            names = set(ops.KernelTimer.summary())
+        finally:
+            ops.KernelTimer.enable(0)
+        # (a 256x256 launch that sends its ragged last rows to a second launch records that kernel as well)
+        expect = {name(ek_of[act])} | ({"gemm_skinny_kernel<%d>" % ek_of[act]} if plan == 2 else set())
+        print(family, "act", act, sorted(outs), "->", sorted(names))
+        assert names == expect, (names, expect)
+
+    o0 = torch.zeros(M, N, device="cuda")
+    run(0, out32=o0)
+    assert _rel(o0.double(), want[0]) < 2e-6
+    for act in (5, 4, 7):
+        o = torch.zeros(M, N, device="cuda")
+        run(act, out32=o)
+        e = _rel(o.double(), want[act])
+        print(family, "act", act, "fp32 rel", e)
+        assert e < 2e-6, (act, e)
+    pre, h = torch.zeros(M, N, device="cuda"), torch.zeros(M, N, device="cuda", dtype=torch.float16)
+    run(6, pre32=pre, out16=h)
+    assert torch.equal(pre, o0)            # the erf builds sum in the same order as the plain ones
+    assert _rel(h.double(), want[6]) < 1e-3
+    for act in (5, 4, 7):                  # fp16 output alone: the wide epilogue, which has its own side-input code
+        h = torch.zeros(M, N, device="cuda", dtype=torch.float16)
+        run(act, out16=h)
+        e = _rel(h.double(), want[act])
+        print(family, "act", act, "fp16 rel", e)
+        assert e < 1e-3, (act, e)
+
+
 def test_gemm_grouped_two_level_batch(ops):
     """wc_gemm_f16_grouped: batch index z = group * zdiv + member.  (a) groups x members with per-group weights / biases
     and outputs written side by side (the adapters' first Linear: blocks x images); (b) groups only, A taken as column

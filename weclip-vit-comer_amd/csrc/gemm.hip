@@ -71,6 +71,21 @@ extern "C" int wc_gemm_log_report(char* buf, int cap) {
 
 #include "gemm_common.h"
 
+// XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (private L2s), so linear
+// ids l, l+8, l+16.. share an L2.  Give each XCD whole M-tile rows: its consecutive workgroups walk
+// the N tiles of one M tile and re-use the A tile from that XCD's L2 instead of 8 L2s fetching it.
+// (Only for tall grids: with fewer than 16 M tiles the remap would park the work on a few XCDs.)
+__device__ __forceinline__ void gemm_tile_of(int lin, int gx, int gy, int& tx, int& ty) {
+    if (gy >= 16) {
+        const int slot = lin >> 3;
+        ty = (slot / gx) * 8 + (lin & 7);
+        tx = slot - (slot / gx) * gx;
+    } else {
+        ty = lin / gx;
+        tx = lin - ty * gx;
+    }
+}
+
 // Main kernel.  Operand tiles go global -> LDS directly (global_load_lds_dwordx4, no VGPR staging and no
 // ds_write: the LDS store path, ~79 B/clk/CU for ds_write_b128, was the bottleneck of the register-staged
 // version).  An LDS-DMA wave-instruction writes 64 lanes x 16 B = 1 KiB linearly (8 unpadded 128-B tile
@@ -86,22 +101,9 @@ __global__ __launch_bounds__(256, NST == 2 ? 2 : 1) void gemm_f16_kernel(GemmArg
     constexpr int TILE = BM * BK * 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
-    // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs (private L2s), so linear
-    // ids l, l+8, l+16.. share an L2.  Give each XCD whole M-tile rows: its consecutive workgroups walk
-    // the N tiles of one M tile and re-use the A tile from that XCD's L2 instead of 8 L2s fetching it.
-    // (Only for tall grids: with fewer than 16 M tiles the remap would park the work on a few XCDs.)
-    const int gx = g.gx, gy = g.gy;
-    const int lin = blockIdx.x;
     int tx, ty;
-    if (gy >= 16) {
-        const int slot = lin >> 3;
-        ty = (slot / gx) * 8 + (lin & 7);
-        tx = slot - (slot / gx) * gx;
-    } else {
-        ty = lin / gx;
-        tx = lin - ty * gx;
-    }
-    if (ty >= gy) return;
+    gemm_tile_of(blockIdx.x, g.gx, g.gy, tx, ty);
+    if (ty >= g.gy) return;
     const int m0 = ty * BM, n0 = tx * BN;
     const long zb = blockIdx.z;
     const long z2 = (int)blockIdx.z / g.zdiv, z1 = zb - z2 * g.zdiv;
@@ -318,34 +320,20 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmArgs g) {
 // the LDS-DMA of half-tile p+6 between its MFMAs; a slot is re-staged at least two phases after its last read.
 // The two row groups run one barrier apart: while the waves of one group multiply (and issue DMA), the other
 // group's waves (their SIMD neighbours) read fragments, so LDS reads, DMA and MFMA overlap.
-//
-// M16 (round 3): the same schedule on v_mfma_f32_16x16x32_f16 -- per phase 16 MFMAs of 16 cycles instead of 8 of 32, the same
-// fragment bytes (a 16-B fragment is now 16 rows x 8 of the 32 k of an MFMA: lane l reads row l & 15, 16-B chunk l >> 4; the
-// XOR swizzle is conflict-free for that pattern as well) and the same 128 accumulator registers.  The matrix pipe takes the
-// same cycles either way; what differs is the clock the chip holds under the load (MI355X_MICROARCH.md, DVFS item 7).
 #define PP_SLOT 16384
 // RING = half-tile slots in LDS: 8 (128 KiB, three half-tiles in flight across the barriers) or 10 (all 160 KiB, FIVE in flight;
 // the default).  A fifth of the staged lines miss the XCD's L2 and come from the Infinity Cache, and a half-tile is complete
 // only when its slowest line is; two more half-tiles in flight give 1-3 % (8192^3: 907 -> 881 us, QKV 78.9 -> 76.4 us,
 // bit-identical outputs) -- the depth of the ring is a small part of the transport side's 41 GB/s per CU, not its cause.
-template <int EK, bool M16, int RING = 8>
+template <int EK, int RING = 8>
 __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // RING half-tile slots [128 rows][64 halfs], XOR-swizzled
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
-    const int gx = g.gx, gy = g.gy;
-    const int lin = blockIdx.x;
     int tx, ty;
-    if (gy >= 16) {          // XCD-aware order, as in the 128x128 kernel
-        const int slot = lin >> 3;
-        ty = (slot / gx) * 8 + (lin & 7);
-        tx = slot - (slot / gx) * gx;
-    } else {
-        ty = lin / gx;
-        tx = lin - ty * gx;
-    }
-    if (ty >= gy) return;
+    gemm_tile_of(blockIdx.x, g.gx, g.gy, tx, ty);      // XCD-aware order, as in the 128x128 kernel
+    if (ty >= g.gy) return;
     const int m0 = ty * 256, n0 = tx * 256;
 
     // per-thread DMA sources of the four half-tile kinds (two 16-B chunks each)
@@ -396,45 +384,31 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(GemmArgs g) {
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       \
     }
     // fragment read addresses (bytes inside a slot): A rows wr*64 + mi*32 + l31, B rows wc*32 + l31
-    // M16: fragment x of a 32-row block is (row tile tr = x >> 1, k half x & 1): rows tr*16 + (lane & 15), chunk (x & 1)*4 + (lane >> 4)
-    const int hh = lane >> 5, l31 = lane & 31, q16 = lane >> 4, l15 = lane & 15;
+    const int hh = lane >> 5, l31 = lane & 31;
     int aaddr[2][4], baddr[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi) {
-            const int ra = M16 ? wr * 64 + mi * 32 + (ks >> 1) * 16 + l15 : wr * 64 + mi * 32 + l31;
-            const int ch = M16 ? (ks & 1) * 4 + q16 : 2 * ks + hh;
+            const int ra = wr * 64 + mi * 32 + l31;
+            const int ch = 2 * ks + hh;
             aaddr[mi][ks] = ra * 128 + ((ch ^ ((ra >> 1) & 7)) << 4);
         }
-        const int rb = M16 ? wc * 32 + (ks >> 1) * 16 + l15 : wc * 32 + l31;
-        const int ch = M16 ? (ks & 1) * 4 + q16 : 2 * ks + hh;
+        const int rb = wc * 32 + l31;
+        const int ch = 2 * ks + hh;
         baddr[ks] = rb * 128 + ((ch ^ ((rb >> 1) & 7)) << 4);
     }
-    f32x16 acc[M16 ? 1 : 2][2][2];      // [row half a][mi][column half b]
-    f32x4 acc4[M16 ? 2 : 1][2][2][4];   // M16: [a][mi][b][tr*2 + tc]
-    if constexpr (M16) {
+    f32x16 acc[2][2][2];      // [row half a][mi][column half b]
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc4[a][i][j][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    } else {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[a][i][j][r] = 0.f;
-    }
-    float bv[M16 ? 4 : 2], sc[M16 ? 4 : 2];
-    if constexpr (M16) gemm_colvals16(g, n0, wc, lane, bv, sc);
-    else gemm_colvals(g, n0, wc, lane, 0, bv, sc);
+                for (int r = 0; r < 16; ++r) acc[a][i][j][r] = 0.f;
+    float bv[2], sc[2];
+    gemm_colvals(g, n0, wc, lane, 0, bv, sc);
 
     // prologue: half-tiles 0..5 (0..7 with the 10-slot ring; nt >= 2 is guaranteed by the launcher), the first two landed
     PP_STAGE(0, 0, 0); PP_STAGE(0, 1, 1); PP_STAGE(0, 2, 2); PP_STAGE(0, 3, 3); PP_STAGE(1, 0, 4); PP_STAGE(1, 1, 5);
@@ -456,26 +430,12 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(GemmArgs g) {
 #define PP_READ_B(fb_, slot_)                                                                                 \
     _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                          \
         fb_[ks] = *reinterpret_cast<const f16x8*>(smem + (slot_) * PP_SLOT + baddr[ks]);
-    // M16: MFMA (k2, mi, tr, tc) multiplies fragment fa[mi][tr*2 + k2] with fb[tc*2 + k2] into acc4[a][mi][b][tr*2 + tc]; the
-    // quarter q_ (0..3) of a phase is k half k2 = q_ >> 1, mi = q_ & 1: four MFMAs on four different accumulators
-#define PP_MMA16_Q(a_, fb_, b_, q_)                                                                           \
-    _Pragma("unroll") for (int tt = 0; tt < 4; ++tt)                                                          \
-        acc4[a_][(q_) & 1][b_][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(                                  \
-            fa[(q_) & 1][(tt >> 1) * 2 + ((q_) >> 1)], fb_[(tt & 1) * 2 + ((q_) >> 1)], acc4[a_][(q_) & 1][b_][tt], 0, 0, 0);
-#define PP_PIN16(a_, b_)                                                                                      \
-    asm volatile("" : "+v"(acc4[a_][0][b_][0]), "+v"(acc4[a_][0][b_][1]), "+v"(acc4[a_][0][b_][2]), "+v"(acc4[a_][0][b_][3]),  \
-                      "+v"(acc4[a_][1][b_][0]), "+v"(acc4[a_][1][b_][1]), "+v"(acc4[a_][1][b_][2]), "+v"(acc4[a_][1][b_][3]));
 #define PP_MMA(a_, fb_, b_)                                                                                   \
-    if constexpr (M16) {                                                                                      \
-        PP_MMA16_Q(a_, fb_, b_, 0) PP_MMA16_Q(a_, fb_, b_, 1) PP_MMA16_Q(a_, fb_, b_, 2) PP_MMA16_Q(a_, fb_, b_, 3) \
-        PP_PIN16(a_, b_)                                                                                      \
-    } else {                                                                                                  \
-        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                    \
-            acc[a_][0][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][ks], fb_[ks], acc[a_][0][b_], 0, 0, 0); \
-            acc[a_][1][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[1][ks], fb_[ks], acc[a_][1][b_], 0, 0, 0); \
-        }                                                                                                     \
-        asm volatile("" : "+v"(acc[a_][0][b_]), "+v"(acc[a_][1][b_]));   /* keeps the MFMAs inside their phase */ \
-    }
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                        \
+        acc[a_][0][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][ks], fb_[ks], acc[a_][0][b_], 0, 0, 0); \
+        acc[a_][1][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[1][ks], fb_[ks], acc[a_][1][b_], 0, 0, 0); \
+    }                                                                                                         \
+    asm volatile("" : "+v"(acc[a_][0][b_]), "+v"(acc[a_][1][b_]));   /* keeps the MFMAs inside their phase */
     // one phase of the guarded form (last K-tiles): [fragment reads] -> DMA of half-tile phi+6 -> counted wait ->
     // barrier -> 8 MFMAs -> barrier
 #define PP_PHASE(phi_, READS_, tj_, qj_, slotj_, MMA_)                                                        \
@@ -525,22 +485,13 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(GemmArgs g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         __builtin_amdgcn_s_setprio(1);                                                                        \
-        if constexpr (M16) {                                                                                  \
-            PP_MMA16_Q(a_, fb_, b_, 0)                                                                        \
-            PP_STAGE_H(tj_, qj_, slotj_, 0)                                                                   \
-            PP_MMA16_Q(a_, fb_, b_, 1) PP_MMA16_Q(a_, fb_, b_, 2)                                             \
-            PP_STAGE_H(tj_, qj_, slotj_, 1)                                                                   \
-            PP_MMA16_Q(a_, fb_, b_, 3)                                                                        \
-            PP_PIN16(a_, b_)                                                                                  \
-        } else {                                                                                              \
-            _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                \
-                acc[a_][0][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][ks], fb_[ks], acc[a_][0][b_], 0, 0, 0); \
-                acc[a_][1][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[1][ks], fb_[ks], acc[a_][1][b_], 0, 0, 0); \
-                if (ks == 0) PP_STAGE_H(tj_, qj_, slotj_, 0)                                                  \
-                if (ks == 2) PP_STAGE_H(tj_, qj_, slotj_, 1)                                                  \
-            }                                                                                                 \
-            asm volatile("" : "+v"(acc[a_][0][b_]), "+v"(acc[a_][1][b_]));                                    \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                    \
+            acc[a_][0][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[0][ks], fb_[ks], acc[a_][0][b_], 0, 0, 0); \
+            acc[a_][1][b_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[1][ks], fb_[ks], acc[a_][1][b_], 0, 0, 0); \
+            if (ks == 0) PP_STAGE_H(tj_, qj_, slotj_, 0)                                                      \
+            if (ks == 2) PP_STAGE_H(tj_, qj_, slotj_, 1)                                                      \
         }                                                                                                     \
+        asm volatile("" : "+v"(acc[a_][0][b_]), "+v"(acc[a_][1][b_]));                                        \
         __builtin_amdgcn_s_setprio(0);                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                    \
         __builtin_amdgcn_s_barrier();                                                                         \
@@ -633,21 +584,14 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(GemmArgs g) {
 #undef PP_PHASE_S
 #undef PP_PHASE
 #undef PP_MMA
-#undef PP_MMA16_Q
-#undef PP_PIN16
 #undef PP_READ_A
 #undef PP_READ_B
 #undef PP_WAIT
 #undef PP_STAGE
     if (wr == 0) __builtin_amdgcn_s_barrier();       // re-align the two row groups
     __syncthreads();                                 // every wave is done with the operand slots: epilogue scratch
-    if constexpr (M16) {      // (the epilogue reads the 16x16 tiles as register r = (tr*2 + tc)*4 + i of a 32x32 block)
-        gemm_epilogue<EK, 2, true>(g, acc4[0], m0 + wr * 128, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
-        gemm_epilogue<EK, 2, true>(g, acc4[1], m0 + wr * 128 + 64, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
-    } else {
-        gemm_epilogue<EK, 2, false>(g, acc[0], m0 + wr * 128, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
-        gemm_epilogue<EK, 2, false>(g, acc[1], m0 + wr * 128 + 64, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
-    }
+    gemm_epilogue<EK>(g, acc[0], m0 + wr * 128, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
+    gemm_epilogue<EK>(g, acc[1], m0 + wr * 128 + 64, n0, 0, wc, lane, 0, smem + wave * 8192, bv, sc, 0);
 }
 
 // Which kernel a shape takes: 0 = 128x128 kernel, 1 = 256x256 ping-pong kernel, 2 = ping-pong kernel on the
@@ -663,16 +607,103 @@ static int gemm_plan(int M, int N, int K, int nseg, int batch, bool row_mapped_a
     const long gx = wc_cdiv(N, 256), gy = wc_cdiv(M, 256);
     if (!pp_mode || batch != 1 || (long)K * nseg < 2 * BK || gx * gy < pp_min_tiles) return 0;
     if ((long)M * lda * 2 >= (1L << 32) || (long)N * ldw * 2 >= (1L << 32)) return 0;      // the tall kernels carry 32-bit byte offsets
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-            n_cu = 256;
-    }
+    const int n_cu = gemm_cu_count();
     const bool can_split = M % 256 != 0 && !row_mapped_aux;
     const bool split = can_split && wc_cdiv(gx * (gy - 1), n_cu) < wc_cdiv(gx * gy, n_cu);
     return split ? 2 : 1;
+}
+
+extern "C" int wc_gemm_plan(int M, int N, int K, int nseg, int batch) {
+    return gemm_plan(M, N, K, nseg, batch, false);
+}
+
+// The builds of each kernel family, indexed by the epilogue kind EK = (act 6 / 7 ? 2 : 0) | (act 4 / 5 / 7 ? 1 : 0) of
+// gemm_epilogue: instantiation, dynamic LDS, and the name the timers record -- the instantiation as rocprofv3 prints it,
+// because bench.py joins PMC traffic to the timers by name.
+struct GemmKernel { void (*fn)(GemmArgs); int threads; int lds; const char* name; };
+#define GEMM_KERNEL(threads_, lds_, ...) {__VA_ARGS__, threads_, lds_, #__VA_ARGS__}
+// 256x256: the 10-slot ring; the erf-GELU epilogues fit the register budget only beside the 8-slot ring
+static const GemmKernel gemm_pp_kernels[4] = {
+    GEMM_KERNEL(512, 10 * PP_SLOT, gemm_f16_pp_kernel<0, 10>), GEMM_KERNEL(512, 10 * PP_SLOT, gemm_f16_pp_kernel<1, 10>),
+    GEMM_KERNEL(512, 8 * PP_SLOT, gemm_f16_pp_kernel<2, 8>), GEMM_KERNEL(512, 8 * PP_SLOT, gemm_f16_pp_kernel<3, 8>)};
+static const GemmKernel gemm_skinny_kernels[4] = {
+    GEMM_KERNEL(256, 0, gemm_skinny_kernel<0>), GEMM_KERNEL(256, 0, gemm_skinny_kernel<1>),
+    GEMM_KERNEL(256, 0, gemm_skinny_kernel<2>), GEMM_KERNEL(256, 0, gemm_skinny_kernel<3>)};
+// 128x128: [0] two stages (64 KiB, two workgroups per CU), [1] the 4-stage ring (128 KiB)
+static const GemmKernel gemm_tile_kernels[2][4] = {
+    {GEMM_KERNEL(256, 2 * 2 * BM * BK * 2, gemm_f16_kernel<0, 2>), GEMM_KERNEL(256, 2 * 2 * BM * BK * 2, gemm_f16_kernel<1, 2>),
+     GEMM_KERNEL(256, 2 * 2 * BM * BK * 2, gemm_f16_kernel<2, 2>), GEMM_KERNEL(256, 2 * 2 * BM * BK * 2, gemm_f16_kernel<3, 2>)},
+    {GEMM_KERNEL(256, 4 * 2 * BM * BK * 2, gemm_f16_kernel<0, 4>), GEMM_KERNEL(256, 4 * 2 * BM * BK * 2, gemm_f16_kernel<1, 4>),
+     GEMM_KERNEL(256, 4 * 2 * BM * BK * 2, gemm_f16_kernel<2, 4>), GEMM_KERNEL(256, 4 * 2 * BM * BK * 2, gemm_f16_kernel<3, 4>)}};
+#undef GEMM_KERNEL
+
+// dynamic LDS above the default per-kernel limit of 64 KiB has to be allowed once per kernel
+static bool gemm_reserve_lds(const GemmKernel* k, int n) {
+    for (int i = 0; i < n; ++i)
+        if (k[i].lds > 65536 &&
+            hipFuncSetAttribute((const void*)k[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, k[i].lds) != hipSuccess)
+            return false;
+    return true;
+}
+
+static int gemm_launch(const GemmKernel& k, const char* family, dim3 grid, const GemmArgs& g, double flop, void* stream) {
+    const int pr = wc_prof_begin(stream);
+    hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), k.lds, (hipStream_t)stream, g);
+    wc_prof_end(pr, k.name, flop, stream);
+    WC_LAUNCH_CHECK(family);
+    return WC_OK;
+}
+
+// Routes one checked product (g complete but for the tile grid) to its kernel(s).
+static int gemm_dispatch(GemmArgs g, int batch, void* stream) {
+    int M = g.M;
+    const int N = g.N, K = g.K, act = g.act;
+    const int ek = ((act == 6 || act == 7) ? 2 : 0) | ((act == 4 || act == 5 || act == 7) ? 1 : 0);
+    const int plan = gemm_plan(M, N, K, g.nseg, batch, false, g.lda, g.ldw);
+    if (plan) {   // tall GEMM: 256x256 ping-pong kernel
+        g.gx = wc_cdiv(N, 256);
+        g.gy = wc_cdiv(M, 256);
+        static bool lds_attr_set = false;
+        if (!lds_attr_set) {
+            WC_CHECK_ARG(gemm_reserve_lds(gemm_pp_kernels, 4), "wc_gemm_f16: cannot reserve 160 KiB of LDS");
+            lds_attr_set = true;
+        }
+        // A ragged last row of tiles (M % 256 rows) costs every CU a whole extra round when it tips the tile
+        // count over a multiple of the CU count (ViT-B fc1 at 16 x 1025 tokens: 65 x 12 tiles = 3.05 rounds):
+        // those rows then go to the 128x128 kernel in a second, small launch.
+        const int m_main = M / 256 * 256, m_rem = M - m_main;
+        const bool split = plan == 2;
+        if (split) {
+            g.M = m_main;
+            g.gy -= 1;
+        }
+        const dim3 gridp((unsigned)(g.gx * (g.gy >= 16 ? (g.gy + 7) / 8 * 8 : g.gy)), 1, 1);
+        const int rc = gemm_launch(gemm_pp_kernels[ek], "gemm_f16_pp_kernel", gridp, g, 2.0 * g.M * N * K, stream);
+        if (rc != WC_OK || !split) return rc;
+        for (int i = 0; i < g.nseg; ++i) g.A[i] += (long)m_main * g.lda;
+        if (g.resid) g.resid += (long)m_main * g.ldr;
+        if (g.C32) g.C32 += (long)m_main * g.ldc;
+        if (g.C16) g.C16 += (long)m_main * g.ldc;
+        if (g.C16lo) g.C16lo += (long)m_main * g.ldc;
+        if (g.P32) g.P32 += (long)m_main * g.ldc;
+        if (g.aux && !g.rowmap) g.aux += (long)m_main * g.ldaux;
+        if (g.rowmap) g.row0 = m_main;          // row-mapped aux rows: keep the pointer, shift the row index
+        if (g.auxh) g.auxh += (long)m_main * g.ldaux;
+        g.M = M = m_rem;
+    }
+    if (M <= 32 && batch == 1 && N >= 256)      // a few rows against many weight rows
+        return gemm_launch(gemm_skinny_kernels[ek], "gemm_skinny_kernel", dim3(wc_cdiv(N, 64)), g, 2.0 * M * N * K, stream);
+    g.gx = wc_cdiv(N, BN);
+    g.gy = wc_cdiv(M, BM);
+    const dim3 grid((unsigned)(g.gx * ((g.gy + 7) / 8 * 8)), 1, batch);
+    static bool lds_attr_set128 = false;
+    if (!lds_attr_set128) {
+        WC_CHECK_ARG(gemm_reserve_lds(gemm_tile_kernels[1], 4), "wc_gemm_f16: cannot reserve 128 KiB of LDS");
+        lds_attr_set128 = true;
+    }
+    // at most one workgroup per CU: the 4-stage ring (128 KiB); else two 2-stage workgroups per CU
+    const bool ring = (long)g.gx * g.gy * batch <= gemm_cu_count() && K / BK * g.nseg >= 3;
+    return gemm_launch(gemm_tile_kernels[ring][ek], "gemm_f16_kernel", grid, g, 2.0 * g.M * N * K * batch, stream);
 }
 
 extern "C" int wc_gemm_f16_grouped(const void* A0, const void* A1, const void* A2, const void* W0, const void* W1,
@@ -681,54 +712,8 @@ extern "C" int wc_gemm_f16_grouped(const void* A0, const void* A1, const void* A
                                    void* C16, void* C16lo, long ldc, int act, int round16, float scale, int scale_cols,
                                    float* P32, const float* aux, const int* rowmap, int rpg, long ldaux, const void* auxh,
                                    const float* cscale, long sCS, int zdiv, long sA2, long sW2, long sC2, long sB2,
-                                   long sX2, void* stream);
-
-extern "C" int wc_gemm_plan(int M, int N, int K, int nseg, int batch) {
-    return gemm_plan(M, N, K, nseg, batch, false);
-}
-
-extern "C" int wc_gemm_f16(const void* A0, const void* A1, const void* A2, const void* W0,
-                           const void* W1, const void* W2, int nseg, int M, int N, int K, long lda,
-                           long ldw, int batch, long sA, long sW, long sC, const float* bias,
-                           const float* resid, long ldr, long sR, float* C32, void* C16, void* C16lo, long ldc, int act,
-                           int round16, float scale, int scale_cols, float* P32, const float* aux,
-                           const int* rowmap, int rpg, long ldaux, const void* auxh, const float* cscale,
-                           long sCS, void* stream) {
-    return wc_gemm_f16_grouped(A0, A1, A2, W0, W1, W2, nseg, M, N, K, lda, ldw, batch, sA, sW, sC, bias, resid, ldr, sR,
-                               C32, C16, C16lo, ldc, act, round16, scale, scale_cols, P32, aux, rowmap, rpg, ldaux, auxh,
-                               cscale, sCS, batch, 0, 0, 0, 0, 0, stream);
-}
-
-static int gemm_f16_grouped_impl(const void* A0, const void* A1, const void* A2, const void* W0,
-                                   const void* W1, const void* W2, int nseg, int M, int N, int K, long lda,
-                                   long ldw, int batch, long sA, long sW, long sC, const float* bias,
-                                   const float* resid, long ldr, long sR, float* C32, void* C16, void* C16lo, long ldc,
-                                   int act, int round16, float scale, int scale_cols, float* P32, const float* aux,
-                                   const int* rowmap, int rpg, long ldaux, const void* auxh, const float* cscale,
-                                   long sCS, int zdiv, long sA2, long sW2, long sC2, long sB2, long sX2, void* stream);
-
-extern "C" int wc_gemm_f16_grouped(const void* A0, const void* A1, const void* A2, const void* W0,
-                                   const void* W1, const void* W2, int nseg, int M, int N, int K, long lda,
-                                   long ldw, int batch, long sA, long sW, long sC, const float* bias,
-                                   const float* resid, long ldr, long sR, float* C32, void* C16, void* C16lo, long ldc,
-                                   int act, int round16, float scale, int scale_cols, float* P32, const float* aux,
-                                   const int* rowmap, int rpg, long ldaux, const void* auxh, const float* cscale,
-                                   long sCS, int zdiv, long sA2, long sW2, long sC2, long sB2, long sX2, void* stream) {
+                                   long sX2, void* stream) {
     const int sl = shape_log_begin(stream);
-    const int rc = gemm_f16_grouped_impl(A0, A1, A2, W0, W1, W2, nseg, M, N, K, lda, ldw, batch, sA, sW, sC, bias, resid, ldr, sR, C32, C16,
-                                         C16lo, ldc, act, round16, scale, scale_cols, P32, aux, rowmap, rpg, ldaux, auxh, cscale, sCS, zdiv,
-                                         sA2, sW2, sC2, sB2, sX2, stream);
-    if (sl >= 0) shape_log_end(sl, C32 ? (C16 ? "f16+f32" : "f32") : "f16", M, N, K, nseg, batch, gemm_plan(M, N, K, nseg, batch, false, lda, ldw), act, stream);
-    return rc;
-}
-
-static int gemm_f16_grouped_impl(const void* A0, const void* A1, const void* A2, const void* W0,
-                                   const void* W1, const void* W2, int nseg, int M, int N, int K, long lda,
-                                   long ldw, int batch, long sA, long sW, long sC, const float* bias,
-                                   const float* resid, long ldr, long sR, float* C32, void* C16, void* C16lo, long ldc,
-                                   int act, int round16, float scale, int scale_cols, float* P32, const float* aux,
-                                   const int* rowmap, int rpg, long ldaux, const void* auxh, const float* cscale,
-                                   long sCS, int zdiv, long sA2, long sW2, long sC2, long sB2, long sX2, void* stream) {
     WC_CHECK_ARG(zdiv >= 1 && sA2 % 8 == 0 && sW2 % 8 == 0, "wc_gemm_f16_grouped: zdiv >= 1, sA2 / sW2 %% 8 == 0");
     WC_CHECK_ARG(nseg >= 1 && nseg <= 3, "wc_gemm_f16: nseg must be 1..3");
     WC_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % BK == 0, "wc_gemm_f16: need M,N>0 and K %% 64 == 0 (got M=%d N=%d K=%d)", M, N, K);
@@ -742,16 +727,14 @@ static int gemm_f16_grouped_impl(const void* A0, const void* A1, const void* A2,
     WC_CHECK_ARG(act >= 0 && act <= 7, "wc_gemm_f16: act must be 0..7");
     WC_CHECK_ARG(act != 5 || (auxh && ldaux >= N), "wc_gemm_f16: act 5 needs auxh, ldaux");
     WC_CHECK_ARG((act != 4 && act != 7) || (aux && rpg > 0 && ldaux >= N), "wc_gemm_f16: act 4 / 7 need aux, rpg, ldaux");
-    const bool use_aux = act == 4 || act == 5 || act == 7;      // the epilogue variant that reads a side input
-    const bool erf = act == 6 || act == 7;                      // the erf-GELU builds (gemm_epilogue EK 2 / 3)
-    GemmArgs g;
+    GemmArgs g = {};
     g.A[0] = (const __half*)A0; g.A[1] = (const __half*)A1; g.A[2] = (const __half*)A2;
     g.W[0] = (const __half*)W0; g.W[1] = (const __half*)W1; g.W[2] = (const __half*)W2;
     g.nseg = nseg; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw;
     g.sA = sA; g.sW = sW; g.sC = sC; g.sR = sR; g.bias = bias; g.resid = resid; g.ldr = ldr;
     g.C32 = C32; g.C16 = (__half*)C16; g.C16lo = (__half*)C16lo; g.ldc = ldc;
     g.act = act; g.round16 = round16; g.scale = scale; g.scale_cols = scale_cols;
-    g.P32 = P32; g.aux = aux; g.rowmap = rowmap; g.row0 = 0; g.rpg = rpg > 0 ? rpg : 1; g.ldaux = ldaux;
+    g.P32 = P32; g.aux = aux; g.rowmap = rowmap; g.rpg = rpg > 0 ? rpg : 1; g.ldaux = ldaux;
     g.auxh = (const __half*)auxh; g.cscale = cscale; g.sCS = sCS;
     g.zdiv = zdiv; g.sA2 = sA2; g.sW2 = sW2; g.sC2 = sC2; g.sB2 = sB2; g.sX2 = sX2;
     // wide epilogue needs every 4-column group of a row 16-B (fp32) / 8-B (fp16) addressable
@@ -760,113 +743,21 @@ static int gemm_f16_grouped_impl(const void* A0, const void* A1, const void* A2,
              ((act != 4 && act != 7) || (ldaux % 4 == 0 && (uintptr_t)aux % 16 == 0)))
                 ? 1 : 0;
     g.auxvec = (act == 5 && ldaux % 4 == 0 && sX2 % 4 == 0 && (uintptr_t)auxh % 8 == 0) ? 1 : 0;
-    g.gx = wc_cdiv(N, BN);
-    const int plan = gemm_plan(M, N, K, nseg, batch, false, lda, ldw);
-    if (plan) {   // tall GEMM: 256x256 ping-pong kernel
-        g.gx = wc_cdiv(N, 256);
-        g.gy = wc_cdiv(M, 256);
-        dim3 gridp((unsigned)(g.gx * (g.gy >= 16 ? (g.gy + 7) / 8 * 8 : g.gy)), 1, 1);
-        static bool lds_attr_set = false;
-        if (!lds_attr_set) {      // 160 / 128 KiB of dynamic LDS are above the default per-kernel limit
-            WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_f16_pp_kernel<0, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PP_SLOT) == hipSuccess &&
-                         hipFuncSetAttribute((const void*)gemm_f16_pp_kernel<1, false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, 10 * PP_SLOT) == hipSuccess &&
-                         hipFuncSetAttribute((const void*)gemm_f16_pp_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * PP_SLOT) == hipSuccess &&
-                         hipFuncSetAttribute((const void*)gemm_f16_pp_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * PP_SLOT) == hipSuccess,
-                         "wc_gemm_f16: cannot reserve 160 KiB of LDS");
-            lds_attr_set = true;
-        }
-        // A ragged last row of tiles (M % 256 rows) costs every CU a whole extra round when it tips the tile
-        // count over a multiple of the CU count (ViT-B fc1 at 16 x 1025 tokens: 65 x 12 tiles = 3.05 rounds):
-        // those rows then go to the 128x128 kernel in a second, small launch.
-        const int m_main = M / 256 * 256, m_rem = M - m_main;
-        const bool split = plan == 2;
-        if (split) {
-            g.M = m_main;
-            g.gy -= 1;
-            gridp.x = (unsigned)(g.gx * (g.gy >= 16 ? (g.gy + 7) / 8 * 8 : g.gy));
-        }
-        const int pr = wc_prof_begin(stream);
-        if (erf) {      // the erf-GELU epilogues: 8-slot ring builds of their own (register budget)
-            if (use_aux)
-                hipLaunchKernelGGL((gemm_f16_pp_kernel<3, false>), gridp, dim3(512), 8 * PP_SLOT, (hipStream_t)stream, g);
-            else
-                hipLaunchKernelGGL((gemm_f16_pp_kernel<2, false>), gridp, dim3(512), 8 * PP_SLOT, (hipStream_t)stream, g);
-            wc_prof_end(pr, use_aux ? "gemm_f16_pp_kernel<3, false, 8>" : "gemm_f16_pp_kernel<2, false, 8>", 2.0 * g.M * N * K, stream);
-        } else {
-            if (use_aux)
-                hipLaunchKernelGGL((gemm_f16_pp_kernel<1, false, 10>), gridp, dim3(512), 10 * PP_SLOT, (hipStream_t)stream, g);
-            else
-                hipLaunchKernelGGL((gemm_f16_pp_kernel<0, false, 10>), gridp, dim3(512), 10 * PP_SLOT, (hipStream_t)stream, g);
-            wc_prof_end(pr, use_aux ? "gemm_f16_pp_kernel<1, false, 10>" : "gemm_f16_pp_kernel<0, false, 10>", 2.0 * g.M * N * K, stream);
-        }
-        WC_LAUNCH_CHECK("gemm_f16_pp_kernel");
-        if (!split) return WC_OK;
-        for (int i = 0; i < nseg; ++i) g.A[i] += (long)m_main * lda;
-        if (g.resid) g.resid += (long)m_main * ldr;
-        if (g.C32) g.C32 += (long)m_main * ldc;
-        if (g.C16) g.C16 += (long)m_main * ldc;
-        if (g.C16lo) g.C16lo += (long)m_main * ldc;
-        if (g.P32) g.P32 += (long)m_main * ldc;
-        if (g.aux && !g.rowmap) g.aux += (long)m_main * ldaux;
-        if (g.rowmap) g.row0 = m_main;          // row-mapped aux rows: keep the pointer, shift the row index
-        if (g.auxh) g.auxh += (long)m_main * ldaux;
-        g.M = M = m_rem;
-        g.gx = wc_cdiv(N, BN);
-    }
-    const int skinny_env = 1;
-    if (skinny_env && M <= 32 && batch == 1 && N >= 256) {      // a few rows against many weight rows
-        const int prs = wc_prof_begin(stream);
-        if (erf && use_aux)
-            hipLaunchKernelGGL(gemm_skinny_kernel<3>, dim3(wc_cdiv(N, 64)), dim3(256), 0, (hipStream_t)stream, g);
-        else if (erf)
-            hipLaunchKernelGGL(gemm_skinny_kernel<2>, dim3(wc_cdiv(N, 64)), dim3(256), 0, (hipStream_t)stream, g);
-        else if (use_aux)
-            hipLaunchKernelGGL(gemm_skinny_kernel<true>, dim3(wc_cdiv(N, 64)), dim3(256), 0, (hipStream_t)stream, g);
-        else
-            hipLaunchKernelGGL(gemm_skinny_kernel<false>, dim3(wc_cdiv(N, 64)), dim3(256), 0, (hipStream_t)stream, g);
-        wc_prof_end(prs, erf ? "gemm_skinny_kernel<erf>" : use_aux ? "gemm_skinny_kernel<1>" : "gemm_skinny_kernel<0>", 2.0 * M * N * K, stream);
-        WC_LAUNCH_CHECK("gemm_skinny_kernel");
-        return WC_OK;
-    }
-    g.gy = wc_cdiv(M, BM);
-    dim3 grid((unsigned)(g.gx * ((g.gy + 7) / 8 * 8)), 1, batch);
-    // at most one workgroup per CU: the 4-stage ring (128 KiB); else two 2-stage workgroups per CU
-    static int n_cu128 = 0;
-    if (!n_cu128) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n_cu128, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu128 <= 0)
-            n_cu128 = 256;
-        WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_f16_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * BM * BK * 2) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)gemm_f16_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * BM * BK * 2) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)gemm_f16_kernel<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * BM * BK * 2) == hipSuccess &&
-                     hipFuncSetAttribute((const void*)gemm_f16_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * BM * BK * 2) == hipSuccess,
-                     "wc_gemm_f16: cannot reserve 128 KiB of LDS");
-    }
-    const int ring_env = 1;
-    const bool ring = ring_env && (long)g.gx * g.gy * batch <= n_cu128 && K / BK * nseg >= 3;
-    const size_t lds = (ring ? 4 : 2) * 2 * BM * BK * 2;
-    const int pr = wc_prof_begin(stream);
-    if (erf) {
-        if (use_aux) {
-            if (ring) hipLaunchKernelGGL((gemm_f16_kernel<3, 4>), grid, dim3(256), lds, (hipStream_t)stream, g);
-            else hipLaunchKernelGGL((gemm_f16_kernel<3, 2>), grid, dim3(256), lds, (hipStream_t)stream, g);
-        } else {
-            if (ring) hipLaunchKernelGGL((gemm_f16_kernel<2, 4>), grid, dim3(256), lds, (hipStream_t)stream, g);
-            else hipLaunchKernelGGL((gemm_f16_kernel<2, 2>), grid, dim3(256), lds, (hipStream_t)stream, g);
-        }
-    } else if (use_aux) {
-        if (ring) hipLaunchKernelGGL((gemm_f16_kernel<true, 4>), grid, dim3(256), lds, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL((gemm_f16_kernel<true, 2>), grid, dim3(256), lds, (hipStream_t)stream, g);
-    } else {
-        if (ring) hipLaunchKernelGGL((gemm_f16_kernel<false, 4>), grid, dim3(256), lds, (hipStream_t)stream, g);
-        else hipLaunchKernelGGL((gemm_f16_kernel<false, 2>), grid, dim3(256), lds, (hipStream_t)stream, g);
-    }
-    wc_prof_end(pr, erf ? (ring ? "gemm_f16_kernel<erf, 4>" : "gemm_f16_kernel<erf, 2>")
-                    : use_aux ? (ring ? "gemm_f16_kernel<1, 4>" : "gemm_f16_kernel<1, 2>")
-                              : (ring ? "gemm_f16_kernel<0, 4>" : "gemm_f16_kernel<0, 2>"), 2.0 * g.M * N * K * batch, stream);
-    WC_LAUNCH_CHECK("gemm_f16_kernel");
-    return WC_OK;
+    const int rc = gemm_dispatch(g, batch, stream);
+    if (sl >= 0) shape_log_end(sl, C32 ? (C16 ? "f16+f32" : "f32") : "f16", M, N, K, nseg, batch, gemm_plan(M, N, K, nseg, batch, false, lda, ldw), act, stream);
+    return rc;
+}
+
+extern "C" int wc_gemm_f16(const void* A0, const void* A1, const void* A2, const void* W0,
+                           const void* W1, const void* W2, int nseg, int M, int N, int K, long lda,
+                           long ldw, int batch, long sA, long sW, long sC, const float* bias,
+                           const float* resid, long ldr, long sR, float* C32, void* C16, void* C16lo, long ldc, int act,
+                           int round16, float scale, int scale_cols, float* P32, const float* aux,
+                           const int* rowmap, int rpg, long ldaux, const void* auxh, const float* cscale,
+                           long sCS, void* stream) {
+    return wc_gemm_f16_grouped(A0, A1, A2, W0, W1, W2, nseg, M, N, K, lda, ldw, batch, sA, sW, sC, bias, resid, ldr, sR,
+                               C32, C16, C16lo, ldc, act, round16, scale, scale_cols, P32, aux, rowmap, rpg, ldaux, auxh,
+                               cscale, sCS, batch, 0, 0, 0, 0, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

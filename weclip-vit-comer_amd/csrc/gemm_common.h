@@ -6,6 +6,18 @@
 int shape_log_begin(void* stream);
 void shape_log_end(int idx, const char* kind, int M, int N, int K, int nseg, int batch, int plan, int act, void* stream);
 
+// CU count of the current device, or 256 where it cannot be read (host side; looked up once per source file)
+static inline int gemm_cu_count() {
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
+            n_cu = 256;
+    }
+    return n_cu;
+}
+
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -13,7 +25,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define BM 128
 #define BN 128
 #define BK 64
-#define LDS_ROW 144   // bytes per padded tile row (64 halfs = 128 B + 16 B pad)
 
 struct GemmArgs {
     const __half* A[3];
@@ -84,45 +95,21 @@ __device__ __forceinline__ void gemm_colvals(const GemmArgs& g, int n0, int wc, 
     }
 }
 
-// The same for the 16x16 MFMA layout (L16 below): a lane owns FOUR columns of the 64-wide block, 16 apart.
-__device__ __forceinline__ void gemm_colvals16(const GemmArgs& g, int n0, int wc, int lane, float (&bv)[4], float (&sc)[4]) {
-#pragma unroll
-    for (int ci = 0; ci < 4; ++ci) {
-        const int col = n0 + wc * 64 + ci * 16 + (lane & 15);
-        const int colc = col < g.N ? col : g.N - 1;
-        bv[ci] = g.bias ? g.bias[colc] : 0.f;
-        sc[ci] = (col < g.scale_cols) ? g.scale : 1.0f;
-        if (g.cscale) sc[ci] *= g.cscale[colc];
-    }
-}
-
-// NI = column tiles (of 32) of the wave's block: 2 (64 x 64) or 1 (64 x 32: the third column tile of the 256x192 kernel).
-// L16: the accumulators come from v_mfma_f32_16x16x32_f16.  A 32x32 block is then FOUR 16x16 tiles (tr, tc) packed into the
-// same 16 registers, r = (tr*2 + tc)*4 + i, holding row tr*16 + (lane>>4)*4 + i, column tc*16 + (lane&15); registers 8c'..8c'+7
-// still cover the rows [16c', 16c'+16) of the block, so the chunking of the wide path is unchanged, and a lane's per-column
-// constants are bv / sc[ni*2 + tc] (gemm_colvals16).
-template <int NI>
-__device__ __forceinline__ float epi_acc(const f32x16 (&acc)[2][NI], int mi, int ni, int r) { return acc[mi][ni][r]; }
-template <int NI>
-__device__ __forceinline__ float epi_acc(const f32x4 (&acc)[2][NI][4], int mi, int ni, int r) { return acc[mi][ni][r >> 2][r & 3]; }
-
 // EK = epilogue kind of the build: 0 plain (act 0..3), 1 side input (act 4 QuickGELU', act 5 ReLU'), 2 erf GELU (act 6),
 // 3 erf GELU' with side input (act 7).  The erf forms live in builds of their own: carried by every build they cost the
 // 128x128 kernel its second workgroup per CU (244 -> 260 registers: 65 -> 95 us on the decoder shapes, round 3).
-template <int EK, int NI = 2, bool L16 = false, class ACC>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m0, int n0, int wr, int wc,
-                                              int lane, long zb, char* scratch, const float (&bv)[L16 ? 2 * NI : 2],
-                                              const float (&sc)[L16 ? 2 * NI : 2], long cb, long xb = 0) {
+template <int EK>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, const f32x16 (&acc)[2][2], int m0, int n0, int wr, int wc,
+                                              int lane, long zb, char* scratch, const float (&bv)[2],
+                                              const float (&sc)[2], long cb, long xb = 0) {
     constexpr bool AUX = (EK & 1) != 0, ERF = EK >= 2;
     const int act = g.act;
-    // layout of accumulator register r (0..15) of block (mi, ni): row inside the 32-row block, column inside the 64-wide block,
-    // index of the lane's per-column constants
+    // layout of accumulator register r (0..15) of block (mi, ni): row inside the 32-row block, column inside the 64-wide block
     // (row = lane part + compile-time part: kept apart so that row * ldc stays one lane-dependent base + scalar multiples of ldc)
-    const int rowl = L16 ? ((lane >> 4) << 2) : 4 * (lane >> 5);
-#define EPI_ROWC(r_) (L16 ? ((((r_) >> 3) << 4) + ((r_) & 3)) : (((r_) & 3) + 8 * (((r_) >> 2) & 3)))
+    const int rowl = 4 * (lane >> 5);
+#define EPI_ROWC(r_) (((r_) & 3) + 8 * (((r_) >> 2) & 3))
 #define EPI_ROW(r_) (rowl + EPI_ROWC(r_))
-#define EPI_COL(ni_, r_) (L16 ? ((ni_) * 32 + ((((r_) >> 2) & 1) << 4) + (lane & 15)) : ((ni_) * 32 + (lane & 31)))
-#define EPI_CI(ni_, r_) (L16 ? ((ni_) * 2 + (((r_) >> 2) & 1)) : (ni_))
+#define EPI_COL(ni_) ((ni_) * 32 + (lane & 31))
     const bool has_res = g.resid != nullptr;
     const bool r16 = g.round16 != 0;
     if (g.vec && !g.P32 && g.C16 && !g.C32) {   // fp32 outputs are already 128-B coalesced per half-wave: measured slower there
@@ -148,7 +135,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int grow = m0 + wr * 64 + c * 16 + it * 4 + (lane >> 4);
-                okr[it] = grow < g.M && gcol < g.N && (NI == 2 || c4 < 32);
+                okr[it] = grow < g.M && gcol < g.N;
                 arow[it] = grow < g.M ? grow : g.M - 1;
             }
             if (g.rowmap) {
@@ -179,28 +166,28 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
         for (int c = 0; c < 4; ++c) {            // rows [16c, 16c+16) of the wave's 64x64 sub-tile
             const int mi = c >> 1, rq0 = (c & 1) * 8;
             float* tile = tile0 + (c & 1) * 1024;
-            float v[NI * 8];
+            float v[16];
             if constexpr (AUX) {
                 if ((ERF ? act == 7 : act == 4) && c + 1 < 4) aux_load(c + 1, ua[(c + 1) & 1]);
             }
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
+            for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-                for (int rr = 0; rr < 8; ++rr) v[ni * 8 + rr] = epi_acc<NI>(acc, mi, ni, rq0 + rr) + bv[EPI_CI(ni, rr)];
+                for (int rr = 0; rr < 8; ++rr) v[ni * 8 + rr] = acc[mi][ni][rq0 + rr] + bv[ni];
             if (r16) {
 #pragma unroll
-                for (int e = 0; e < NI * 8; ++e) v[e] = __half2float(__float2half(v[e]));
+                for (int e = 0; e < 16; ++e) v[e] = __half2float(__float2half(v[e]));
             }
             if (has_sc) {
 #pragma unroll
-                for (int e = 0; e < NI * 8; ++e) v[e] *= sc[EPI_CI(e >> 3, e & 7)];
+                for (int e = 0; e < 16; ++e) v[e] *= sc[e >> 3];
             }
-            if constexpr (!AUX) { WC_EPI_ACT(v, NI * 8) }
+            if constexpr (!AUX) { WC_EPI_ACT(v, 16) }
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
+            for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
                 for (int rr = 0; rr < 8; ++rr)
-                    tile[EPI_ROW(rr) * 64 + EPI_COL(ni, rr)] = v[ni * 8 + rr];      // (rr < 8: rows 0..15 of the chunk)
+                    tile[EPI_ROW(rr) * 64 + EPI_COL(ni)] = v[ni * 8 + rr];      // (rr < 8: rows 0..15 of the chunk)
             // same wave reads what it wrote: LDS ops of a wave complete in order, no barrier needed
             float f[4][4];
             bool ok[4];
@@ -211,7 +198,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
                 const int grow = m0 + wr * 64 + c * 16 + rl;
                 const float4 t4 = *reinterpret_cast<const float4*>(tile + rl * 64 + c4);
                 f[it][0] = t4.x; f[it][1] = t4.y; f[it][2] = t4.z; f[it][3] = t4.w;
-                ok[it] = grow < g.M && gcol < g.N && (NI == 2 || c4 < 32);      // NI == 1: the lanes of columns 32..63 idle
+                ok[it] = grow < g.M && gcol < g.N;
                 o[it] = (long)(grow < g.M ? grow : g.M - 1) * g.ldc + (gcol < g.N ? gcol : 0);
             }
             if constexpr (AUX) {
@@ -281,16 +268,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
     }
     // all 64 residual values of the wave's sub-tile are requested up front: one memory latency, not four
     // (the output may alias the residual, so the compiler cannot hoist these loads over the stores itself)
-    float rva[AUX ? 1 : 2][AUX ? 1 : NI][16];
+    float rva[AUX ? 1 : 2][AUX ? 1 : 2][16];
     if (!AUX && has_res) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
+            for (int ni = 0; ni < 2; ++ni) {
                 const int rbase = m0 + wr * 64 + mi * 32 + rowl;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int col = n0 + wc * 64 + EPI_COL(ni, r);
+                    const int col = n0 + wc * 64 + EPI_COL(ni);
                     const int colc = col < g.N ? col : g.N - 1;
                     int row = rbase + EPI_ROWC(r);
                     if (row > g.M - 1) row = g.M - 1;
@@ -301,17 +288,18 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-            // a lane's columns of this block: one (32x32 layout) or two, 16 apart (L16)
+        for (int ni = 0; ni < 2; ++ni) {
+            // the lane's column of this block.  (Two-entry arrays with equal entries: as scalars or one-entry arrays they compile
+            //  to other code in 14 of the 22 kernels that carry this epilogue -- packed adds and multiplies, 1-4 registers up or
+            //  down, another scratch size in one --, a change that would have to be measured on the step before it is made.)
             int colv[2], colcv[2];
             bool colokv[2];
 #pragma unroll
             for (int tc = 0; tc < 2; ++tc) {
-                colv[tc] = n0 + wc * 64 + EPI_COL(ni, tc * 4);
+                colv[tc] = n0 + wc * 64 + EPI_COL(ni);
                 colokv[tc] = colv[tc] < g.N;
                 colcv[tc] = colokv[tc] ? colv[tc] : g.N - 1;
             }
-#define EPI_TC(r_) (L16 ? (((r_) >> 2) & 1) : 0)
             const int rbase = m0 + wr * 64 + mi * 32 + rowl;
             float uv[16], v[16], pre[16];
             float (&rv)[16] = rva[AUX ? 0 : mi][AUX ? 0 : ni];
@@ -321,7 +309,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
                     for (int r = 0; r < 16; ++r) {
                         int row = rbase + EPI_ROWC(r);
                         if (row > g.M - 1) row = g.M - 1;
-                        rv[r] = g.resid[zb * g.sR + (long)row * g.ldr + colcv[EPI_TC(r)]];
+                        rv[r] = g.resid[zb * g.sR + (long)row * g.ldr + colcv[0]];
                     }
                 }
             }
@@ -330,7 +318,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
                 for (int r = 0; r < 16; ++r) {
                     int row = rbase + EPI_ROWC(r);
                     if (row > g.M - 1) row = g.M - 1;
-                    const int colc = colcv[EPI_TC(r)];
+                    const int colc = colcv[0];
                     if (!ERF && act == 4) {
                         const long arow = g.rowmap ? (long)g.rowmap[(row + g.row0) / g.rpg] * g.rpg + (row + g.row0) % g.rpg : row;
                         const float u = g.aux[arow * g.ldaux + colc];
@@ -346,13 +334,13 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
                 }
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = epi_acc<NI>(acc, mi, ni, r) + bv[EPI_CI(ni, r)];
+            for (int r = 0; r < 16; ++r) v[r] = acc[mi][ni][r] + bv[ni];
             if (r16) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] = __half2float(__float2half(v[r]));
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { v[r] *= sc[EPI_CI(ni, r)]; pre[r] = v[r]; }
+            for (int r = 0; r < 16; ++r) { v[r] *= sc[ni]; pre[r] = v[r]; }
             if constexpr (AUX) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] *= uv[r];
@@ -363,10 +351,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
 #pragma unroll
                 for (int r = 0; r < 16; ++r) v[r] += rv[r];
             }
-            // element r lives at o0 + drow(r) * ldc + (its column - the lane's first column)
+            // element r lives at o0 + drow(r) * ldc
             const long o0 = cb + (long)rbase * g.ldc + colv[0];
-#define EPI_OFF(r_) ((long)EPI_ROWC(r_) * g.ldc + (EPI_TC(r_) ? 16 : 0))
-#define EPI_OK(r_) (colokv[EPI_TC(r_)] && rbase + EPI_ROWC(r_) < g.M)
+#define EPI_OFF(r_) ((long)EPI_ROWC(r_) * g.ldc)
+#define EPI_OK(r_) (colokv[0] && rbase + EPI_ROWC(r_) < g.M)
             if (g.P32) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
@@ -393,10 +381,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, int m
         }
 #undef EPI_OFF
 #undef EPI_OK
-#undef EPI_TC
 #undef EPI_ROW
 #undef EPI_ROWC
 #undef EPI_COL
-#undef EPI_CI
 }
 

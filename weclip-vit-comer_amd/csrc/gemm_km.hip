@@ -284,19 +284,10 @@ __global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_
         }
     }
     const float bv[2] = {0.f, 0.f}, sc[2] = {1.f, 1.f};
-    gemm_epilogue<false>(g.e, acc, n0, k0, wr, wc, lane, z, smem + w4 * 8192, bv, sc, (long)z * g.e.sC + (long)grp * g.gP);
+    gemm_epilogue<0>(g.e, acc, n0, k0, wr, wc, lane, z, smem + w4 * 8192, bv, sc, (long)z * g.e.sC + (long)grp * g.gP);
 }
 
 // part: (nslices, N, K + bias) fp32 with nslices = ceil(M / mslice); zeros: device buffer of >= 16 zero bytes.
-extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N,
-                                      int K, int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, int groups,
-                                      long gA, long gX, void* stream);
-
-extern "C" int wc_gemm_km_f16(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N, int K,
-                              int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, void* stream) {
-    return wc_gemm_km_f16_grouped(dY, lda, X, ldx, zeros, M, N, K, x_rpg, x_gs, x_off, mslice, bias, part, 1, 0, 0, stream);
-}
-
 // groups > 1: `groups` weight gradients of one shape in one launch (blockIdx.y): group i reads dY + i*gA and X + i*gX
 // (elements) and writes part + i * nslices * N * (K + bias).
 extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N,
@@ -314,21 +305,16 @@ extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, l
     }
     const int ns = wc_cdiv(M, mslice);
     WC_CHECK_ARG(ns <= 65535, "wc_gemm_km_f16: too many slices");
-    KmArgs g;
+    KmArgs g = {};
     g.A = (const __half*)dY; g.X = (const __half*)X; g.zeros = (const __half*)zeros;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldx = ldx;
     g.x_rpg = x_rpg; g.x_gs = x_gs; g.x_off = x_off; g.mslice = mslice; g.bias = bias ? 1 : 0;
     const int K1 = K + g.bias;
     g.bias_edge = (g.bias && K % 128 == 0) ? 1 : 0;
     g.gx = g.bias_edge ? K / 128 : wc_cdiv(K1, 128);
-    GemmArgs& e = g.e;
-    e.A[0] = e.A[1] = e.A[2] = nullptr; e.W[0] = e.W[1] = e.W[2] = nullptr;
-    e.nseg = 1; e.M = N; e.N = K1; e.K = 0; e.lda = e.ldw = 0; e.sA = e.sW = 0;
-    e.sC = (long)N * K1; e.sR = 0; e.bias = nullptr; e.resid = nullptr; e.ldr = 0;
-    e.C32 = part; e.C16 = nullptr; e.C16lo = nullptr; e.ldc = K1; e.act = 0; e.round16 = 0; e.scale = 1.f; e.scale_cols = 0;
-    e.P32 = nullptr; e.aux = nullptr; e.rowmap = nullptr; e.row0 = 0; e.rpg = 1; e.ldaux = 0; e.auxh = nullptr; e.cscale = nullptr;
-    e.sCS = 0; e.gx = g.gx; e.gy = wc_cdiv(N, 128); e.vec = 0; e.auxvec = 0;
-    e.zdiv = 1; e.sA2 = e.sW2 = e.sC2 = e.sB2 = e.sX2 = 0;
+    GemmArgs& e = g.e;      // a plain fp32 store of the partials: everything else stays zero / null
+    e.nseg = 1; e.M = N; e.N = K1; e.sC = (long)N * K1; e.C32 = part; e.ldc = K1;
+    e.scale = 1.f; e.rpg = 1; e.zdiv = 1; e.gx = g.gx; e.gy = wc_cdiv(N, 128);
     g.gA = gA; g.gX = gX; g.gP = (long)ns * N * K1;
     g.tiles = g.gx * wc_cdiv(N, 128); g.ns = ns; g.units = groups * ns;
     g.xcd = g.units % 8 == 0 ? 1 : 0;
@@ -336,17 +322,14 @@ extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, l
     dim3 grid((unsigned)(g.tiles * g.units));
     const int pr = wc_prof_begin(stream);
     const int sl = shape_log_begin(stream);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            n_cu <= 0)
-            n_cu = 256;
+    static bool lds_attr_set = false;
+    if (!lds_attr_set) {
         WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_km_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256) == hipSuccess &&
                          hipFuncSetAttribute((const void*)gemm_km_kernel<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 64 * 256) == hipSuccess,
                      "wc_gemm_km_f16: cannot reserve 128 KiB of LDS");
+        lds_attr_set = true;
     }
-    if ((long)g.tiles * g.units <= n_cu && mslice >= 128)      // at most one workgroup per CU: eight waves, 64-token stages
+    if ((long)g.tiles * g.units <= gemm_cu_count() && mslice >= 128)      // at most one workgroup per CU: eight waves, 64-token stages
         hipLaunchKernelGGL((gemm_km_kernel<4, 2>), grid, dim3(512), 4 * 128 * 256, (hipStream_t)stream, g);
     else
         hipLaunchKernelGGL((gemm_km_kernel<5, 1>), grid, dim3(256), 5 * 64 * 256, (hipStream_t)stream, g);
@@ -354,6 +337,11 @@ extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, l
     wc_prof_end(pr, "gemm_km_kernel", 2.0 * M * N * K1 * groups, stream);
     WC_LAUNCH_CHECK("gemm_km_kernel");
     return WC_OK;
+}
+
+extern "C" int wc_gemm_km_f16(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N, int K,
+                              int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, void* stream) {
+    return wc_gemm_km_f16_grouped(dY, lda, X, ldx, zeros, M, N, K, x_rpg, x_gs, x_off, mslice, bias, part, 1, 0, 0, stream);
 }
 
 // out[i] = alpha * sum_s part[s*n + i]   (split-K reduction: slices are a batched GEMM over K ranges)

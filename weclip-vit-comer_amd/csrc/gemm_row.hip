@@ -9,22 +9,29 @@
 // 256x256 tile kernel ran it at a third of the HBM rate (1.3 rounds of one workgroup per CU that load, multiply and store
 // one after the other; weights re-staged through LDS for every tile; 64-byte output segments).  Here
 //   * the WEIGHTS ARE STATIONARY IN REGISTERS: a wave owns 64 output columns and keeps their whole K extent as MFMA B
-//     fragments (128 registers at K = 256), loaded once per workgroup; workgroups are persistent (two per CU, each walks
-//     its 32-row tiles), so the only operand traffic is A, read exactly once;
-//   * A tiles (32 rows x K) arrive by LDS-DMA into a two-slot ring, the next tile's DMA issued before this tile's MFMAs;
-//     XOR-swizzled 16-byte chunks (chunk c of row r at c ^ (r & 15)) keep the ds_read_b128 fragment reads conflict-free;
-//   * the epilogue works on WHOLE ROWS: the accumulators are dropped into a [32][256] fp32 tile in LDS, then a wave takes a
-//     row at a time -- lane l owns columns 4l..4l+3 -- so that every side input (residual, saved pre-activation) is one
-//     1-KiB coalesced load and every output one 1-KiB (fp32) / 512-B (fp16) coalesced store;
+//     fragments of v_mfma_f32_16x16x32_f16 (128 registers at K = 256), loaded once per workgroup; workgroups are persistent
+//     (two per CU, each walks its 16-row tiles), so the only operand traffic is A, read exactly once;
+//   * A tiles (16 rows x K) arrive by LDS-DMA into a THREE-slot ring: the DMA of tile i + 2 is issued at the top of
+//     iteration i, so two tiles are in flight behind the one being multiplied; XOR-swizzled 16-byte chunks (chunk c of row r
+//     at c ^ (r & 15)) keep the ds_read_b128 fragment reads conflict-free;
+//   * the launch's ONE side input (residual, saved pre-activation or saved fp16 output) arrives by LDS-DMA as well, as a dense
+//     [16][N] image in a two-slot ring, one tile ahead: the row phase costs no registers for it and no load sits between its
+//     stores;
+//   * the epilogue works on WHOLE ROWS: the accumulators are dropped into a [16][256] fp32 tile in LDS, then each wave takes
+//     its four rows together -- lane l owns columns 4l..4l+3 -- so that every output is one 1-KiB (fp32) / 512-B (fp16)
+//     coalesced store per row;
 //   * and because a workgroup holds complete rows, the LayerNorm(s) that consume the output (up to two different affine
 //     parameter sets) are computed right there and leave as the fp16 operand of the next GEMM: no LayerNorm launch, no
 //     second read of the 88 MB activation.
 // Two workgroups of four waves per CU overlap each other's load / multiply / store phases.
 //
-// vmcnt discipline: LDS-DMA, loads and stores share one in-order counter.  Each iteration issues the next tile's DMA first
-// and contains ONE explicit `s_waitcnt vmcnt(0)` -- after the row phase's first side loads, before its first store -- which
-// therefore also covers that DMA; the barrier at the top of the next iteration then makes every wave's pieces visible.  No
-// counted waits (a spilled register or a skipped store cannot break the accounting).
+// vmcnt discipline: LDS-DMA, loads and stores share one counter, and LDS-DMA / loads complete in issue order among
+// themselves.  Each iteration has ONE vmcnt wait, between the MFMAs and the row phase's first store.  In the steady state
+// it is COUNTED: it leaves in flight exactly the DMA batch issued at the top of the iteration (A of tile i + 2, side input of
+// tile i + 1: NDMA + nsd instructions per wave), which implies that the previous batch -- this tile's side input, the next
+// tile's A -- has landed; the last two iterations wait for vmcnt(0).  The barrier at the top of the next iteration makes
+// every wave's pieces visible.  The count assumes that nothing else enters the queue: LDS access inside the loop is inline
+// asm (no compiler-placed waits), and the build refuses a register spill in this file (NO_SCRATCH in build.py).
 #include "gemm_common.h"
 #include <stdlib.h>
 
@@ -382,34 +389,9 @@ __global__ __launch_bounds__(256, 2) void gemm_row_kernel(RowArgs g) {
 #undef ROW_DMA_S
 }
 
-static int g_row_cus = 0;
-
 // C ABI: see include/weclip_hip.h
 extern "C" int wc_gemm_row_supported(int M, int N, int K) {
     return (M > 0 && N > 0 && N <= 256 && N % 4 == 0 && (K == 128 || K == 256)) ? 1 : 0;
-}
-
-static int gemm_row_impl(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
-                         const float* cscale, int act, const float* aux, const void* auxh, long ldaux, const float* resid,
-                         long ldr, float* C32, void* C16, float* P32, long ldc, long ldc16, const float* ln_g0, const float* ln_b0,
-                         void* ln_o0, const float* ln_g1, const float* ln_b1, void* ln_o1, float eps, int groups, long gA, long gW,
-                         long gB, long gC, long gX, void* stream);
-
-extern "C" int wc_gemm_row_f16(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
-                               const float* cscale, int act, const float* aux, const void* auxh, long ldaux, const float* resid,
-                               long ldr, float* C32, void* C16, float* P32, long ldc, long ldc16, const float* ln_g0, const float* ln_b0,
-                               void* ln_o0, const float* ln_g1, const float* ln_b1, void* ln_o1, float eps, void* stream) {
-    return gemm_row_impl(A, lda, W, ldw, M, N, K, bias, cscale, act, aux, auxh, ldaux, resid, ldr, C32, C16, P32, ldc, ldc16, ln_g0,
-                         ln_b0, ln_o0, ln_g1, ln_b1, ln_o1, eps, 1, 0, 0, 0, 0, 0, stream);
-}
-
-extern "C" int wc_gemm_row_f16_grouped(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
-                                       int act, const void* auxh, long ldaux, float* C32, void* C16, long ldc, long ldc16, int groups,
-                                       long gA, long gW, long gB, long gC, long gX, void* stream) {
-    WC_CHECK_ARG(groups >= 1 && groups <= 256 && gA % 8 == 0 && gW % 8 == 0 && gB % 4 == 0 && gC % 4 == 0 && gX % 8 == 0,
-                 "wc_gemm_row_f16_grouped: 1..256 groups, group strides that keep every row 16-byte aligned");
-    return gemm_row_impl(A, lda, W, ldw, M, N, K, bias, nullptr, act, nullptr, auxh, ldaux, nullptr, 0, C32, C16, nullptr, ldc, ldc16,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-5f, groups, gA, gW, gB, gC, gX, stream);
 }
 
 static int gemm_row_impl(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
@@ -430,14 +412,12 @@ static int gemm_row_impl(const void* A, long lda, const void* W, long ldw, int M
     WC_CHECK_ARG(!resid || (ldr >= N && ldr % 4 == 0), "wc_gemm_row_f16: ldr %% 4 != 0");
     WC_CHECK_ARG((!ln_o0 && !ln_o1) || (N == 256 && ln_o0 && ln_g0 && ln_b0 && (!ln_o1 || (ln_g1 && ln_b1))),
                  "wc_gemm_row_f16: fused LayerNorm needs N == 256 and gamma / beta (slot 0 first)");
-    if (!g_row_cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&g_row_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g_row_cus <= 0)
-            g_row_cus = 256;
+    static bool lds_attr_set = false;
+    if (!lds_attr_set) {
         WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_row_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 79872) == hipSuccess &&
                      hipFuncSetAttribute((const void*)gemm_row_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 79872) == hipSuccess,
                      "wc_gemm_row_f16: cannot reserve 78 KiB of LDS");
+        lds_attr_set = true;
     }
     RowArgs g;
     g.A = (const __half*)A; g.W = (const __half*)W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw;
@@ -450,7 +430,7 @@ static int gemm_row_impl(const void* A, long lda, const void* W, long ldw, int M
     g.groups = groups; g.gA = gA; g.gW = gW; g.gB = gB; g.gC = gC; g.gX = gX;
     // two persistent workgroups per CU (measured at 86 016 x 256 x 256, fp16 out: 35.8 / 29.8 / 34.4 / 34.9 us with 1 / 2 / 3 / 4 per CU),
     // dealt evenly over the groups
-    int wpg = 2 * g_row_cus / groups;
+    int wpg = 2 * gemm_cu_count() / groups;
     if (wpg < 1) wpg = 1;
     if (wpg > g.ntiles) wpg = g.ntiles;
     g.wpg = wpg;
@@ -474,4 +454,21 @@ static int gemm_row_impl(const void* A, long lda, const void* W, long ldw, int M
                               : (erf ? "gemm_row_kernel<2, true>" : "gemm_row_kernel<2, false>"), 2.0 * groups * M * N * K, nb, stream);
     WC_LAUNCH_CHECK("gemm_row_kernel");
     return WC_OK;
+}
+
+extern "C" int wc_gemm_row_f16(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
+                               const float* cscale, int act, const float* aux, const void* auxh, long ldaux, const float* resid,
+                               long ldr, float* C32, void* C16, float* P32, long ldc, long ldc16, const float* ln_g0, const float* ln_b0,
+                               void* ln_o0, const float* ln_g1, const float* ln_b1, void* ln_o1, float eps, void* stream) {
+    return gemm_row_impl(A, lda, W, ldw, M, N, K, bias, cscale, act, aux, auxh, ldaux, resid, ldr, C32, C16, P32, ldc, ldc16, ln_g0,
+                         ln_b0, ln_o0, ln_g1, ln_b1, ln_o1, eps, 1, 0, 0, 0, 0, 0, stream);
+}
+
+extern "C" int wc_gemm_row_f16_grouped(const void* A, long lda, const void* W, long ldw, int M, int N, int K, const float* bias,
+                                       int act, const void* auxh, long ldaux, float* C32, void* C16, long ldc, long ldc16, int groups,
+                                       long gA, long gW, long gB, long gC, long gX, void* stream) {
+    WC_CHECK_ARG(groups >= 1 && groups <= 256 && gA % 8 == 0 && gW % 8 == 0 && gB % 4 == 0 && gC % 4 == 0 && gX % 8 == 0,
+                 "wc_gemm_row_f16_grouped: 1..256 groups, group strides that keep every row 16-byte aligned");
+    return gemm_row_impl(A, lda, W, ldw, M, N, K, bias, nullptr, act, nullptr, auxh, ldaux, nullptr, 0, C32, C16, nullptr, ldc, ldc16,
+                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-5f, groups, gA, gW, gB, gC, gX, stream);
 }
