@@ -242,6 +242,21 @@ int wc_gemm_km_f16(const void* dY, long lda, const void* X, long ldx, const void
 int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N, int K,
                            int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, int groups, long gA,
                            long gX, void* stream);
+/* Many weight-gradient GEMMs in one grid (all Linear / 1x1 conv weight gradients of a backward pass, reference
+ * WeCLIP_model/segformer_head.py:22-28,58-80; Decoder/TransDecoder.py:98-125: nothing reads one before the optimizer).
+ * jobs: HOST array of count x 16 int64 {dY, X, part (device pointers), M, N, K, lda, ldx, x_rpg, x_gs, x_off, mslice, bias,
+ * groups, gA, gX}; each job = one wc_gemm_km_f16_grouped call and writes the partials that call would write (same kernel
+ * form, bit-identical).  Jobs run longest K loop first; the table travels by value in the kernel arguments
+ * (graph-capturable), 32 jobs per launch and one launch per kernel form. */
+int wc_gemm_km_f16_multi(const int64_t* jobs, int count, const void* zeros, void* stream);
+/* The launches wc_gemm_km_f16_multi would make, without a GPU.  cus: CU count the kernel form is chosen for (<= 0: the
+ * current device's).  Per job i: launch[i], first[i] = its first workgroup id there (a multiple of 8), pos[i] = its place
+ * in that launch's table; per launch l < *nlaunches: grids[l] workgroups and forms[l] (1: 4 waves, 2: 8 waves). */
+int wc_gemm_km_multi_plan(const int64_t* jobs, int count, int cus, int* launch, int* first, int* pos, int* grids,
+                          int* forms, int max_launches, int* nlaunches);
+/* The kernel's job search and index arithmetic for workgroup wg of launch l, run on the host:
+ * out[0] = job (input order; -1: a padding id that exits at once), out[1] = unit (group * slices + slice), out[2] = tile. */
+int wc_gemm_km_multi_locate(const int64_t* jobs, int count, int cus, int l, int wg, int* out);
 /* fp32 -> fp16 hi (+ lo = fp16(x - hi), may be NULL): `.half()` casts of weights/activations
  * (clip/model.py:457-478 convert_weights; clip/myAtt.py:321). */
 int wc_split_f16(const float* x, void* hi, void* lo, long n, void* stream);

@@ -21,7 +21,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=o
 
 # kernels whose hand-counted `s_waitcnt vmcnt(n)` waits are only correct without register spills (a spill's scratch access is
 # one more entry in the in-order vmcnt queue): the build fails if the compiler reports scratch use for them
-NO_SCRATCH = ("gemm_row.hip",)
+NO_SCRATCH = ("gemm_row.hip", "gemm_km.hip")
 
 
 def _sources():

@@ -15,7 +15,8 @@ and element-wise glue; this engine runs the same arithmetic on token rows end to
   * MRFP's depth-wise 3x3 / 5x5 convolutions of all pyramid levels are one launch on NHWC rows with the GELU fused
     (csrc/comer.hip mrfp_dwconv_*): no NCHW transposes, no channel concatenations;
   * the backward pass is written out (no autograd graph inside): weight gradients by the split-K row-major GEMM
-    (gemm_km), their reductions collected into one launch, gradients carried multiplied by GRAD_SCALE like the head's.
+    (gemm_km), queued and launched as one grid with their reductions behind it, gradients carried multiplied by GRAD_SCALE like
+    the head's.
 
 The conv stem (`SpatialPrior`) stays on its autograd Functions (hip_functional.conv3x3_rows / groupnorm_relu_rows); the
 engine starts from its output and hands its gradient back.  With `adapters` set (`CoMerInteraction.forward_tokens`) the four
@@ -47,6 +48,9 @@ def _shape_array(shapes):
 
 
 class ComerEngine:
+    # weight-gradient GEMMs queued into one launch at the end of the backward (False: each where it is requested: tests, A/B)
+    defer_wgrads = True
+
     def __init__(self, net):
         self.net = net
         self.wc = ops.WeightCache()
@@ -411,12 +415,13 @@ class ComerEngine:
         sink.wgrad(dow16, q16, M, n, K, INV, outs, ns=slices(M, ops.wgrad_tiles(n, K), _WGRAD_WGS), lda=ld)
 
     def run_backward(self, ctx, dy):
-        """dy (B*h*w, C) f32 -> (dc0 (B, S, C), [dv x 4], {id(param): grad}): the backward pass, its weight-gradient reductions
-        as ONE launch, then the tiny post-processing that needs the reduced partials: gamma's gradient comes out of the output
+        """dy (B*h*w, C) f32 -> (dc0 (B, S, C), [dv x 4], {id(param): grad}): the backward pass, its weight-gradient GEMMs
+        and their reductions as one launch each at the sink's exit, then the tiny post-processing that needs the reduced
+        partials: gamma's gradient comes out of the output
         projection's un-gated weight gradient G = dv1^T o1:  dWop = diag(gamma) G,  dbop = gamma * s,
         dgamma = rowsum(Wop * G) + bop * s  (s = dv1^T 1)."""
         self._gamma_jobs = []
-        with GradSink(self.net.direct_grads) as sink:
+        with GradSink(self.net.direct_grads, defer=self.defer_wgrads) as sink:
             dc0, dvs = self._backward(ctx, dy, sink)
         for t, G, gsum in self._gamma_jobs:
             op = t.to_v.output_proj

@@ -2,6 +2,7 @@
 #include "gemm_common.h"
 #include <cstring>
 #include <stdlib.h>
+#include <vector>
 
 // ---------------------------------------------------------------------------------------------
 // Weight-gradient GEMM on row-major operands ("KM" layout):  C[n, k] = sum_m dY[m, n] * X[m, k]
@@ -33,6 +34,20 @@ struct KmArgs {
     GemmArgs e;           // epilogue: M = N, N = K + bias, C32 = partials, ldc, sC
 };
 
+// Workgroup `bid` of a job -> (unit, tile).  XCD-aware order (xcd != 0; needs units % 8 == 0 and the job's first workgroup id a
+// multiple of 8): workgroup ids go round-robin over the 8 XCDs, so unit u takes the ids congruent to u mod 8 of its block of 8
+// units (see the kernel).  Host and device share this function: the planner test walks it on the CPU.
+__host__ __device__ __forceinline__ void km_unit_tile(int bid, int tiles, int xcd, int& unit, int& tile) {
+    if (xcd) {
+        const int chunk = bid / (8 * tiles), within = bid - chunk * (8 * tiles);
+        unit = chunk * 8 + (within & 7);
+        tile = within >> 3;
+    } else {
+        unit = bid / tiles;
+        tile = bid - unit * tiles;
+    }
+}
+
 typedef short s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
 typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 
@@ -49,8 +64,9 @@ typedef short s16x8 __attribute__((__vector_size__(8 * sizeof(short))));
 // per SIMD interleave their chains like two workgroups would, the ring is 4 x 32 KiB with 96 KiB in flight, and the launch
 // writes HALF the partial tiles of the two-workgroups-per-CU form (17 MB instead of 34 MB per 256 x 257 gradient, read once
 // more by the slice reduction).
+// (the body of both kernels below: `bid` is the workgroup's index inside its job -- blockIdx.x of a single-job launch)
 template <int NST, int HV>
-__global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_km_kernel(KmArgs g) {
+__device__ __forceinline__ void gemm_km_body(const KmArgs& g, const int bid) {
     // ring of NST stages x [ST tokens]: [A tile | X tile] of ST x 256 B each; NST - 1 stages in flight while one is consumed,
     // counted vmcnt waits + raw s_barrier (a __syncthreads() drains every outstanding LDS-DMA: with 2 stages of 64
     // tokens the loop ran at one global-memory latency per stage)
@@ -67,14 +83,7 @@ __global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_
     // 16 slices).  Only when the units divide evenly over the XCDs: 33 units of 14 long tiles (the grouped adapters)
     // would put 70 workgroups on the first XCD's 64 slots and run two rounds there (173 -> 265 us).
     int unit, tile;
-    if (g.xcd) {
-        const int chunk = blockIdx.x / (8 * g.tiles), within = blockIdx.x - chunk * (8 * g.tiles);
-        unit = chunk * 8 + (within & 7);
-        tile = within >> 3;
-    } else {
-        unit = blockIdx.x / g.tiles;
-        tile = blockIdx.x - unit * g.tiles;
-    }
+    km_unit_tile(bid, g.tiles, g.xcd, unit, tile);
     const int grp = unit / g.ns;
     const int z = unit - grp * g.ns;
     const int ty = tile / g.gx, tx = tile - ty * g.gx;
@@ -287,54 +296,86 @@ __global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_
     gemm_epilogue<0>(g.e, acc, n0, k0, wr, wc, lane, z, smem + w4 * 8192, bv, sc, (long)z * g.e.sC + (long)grp * g.gP);
 }
 
+template <int NST, int HV>
+__global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_km_kernel(KmArgs g) {
+    gemm_km_body<NST, HV>(g, blockIdx.x);
+}
+
+// Everything the kernel derives from a job's arguments, in ONE place for the single-job launcher (host) and the multi-job
+// kernel (device): both forms then run gemm_km_body on the same KmArgs.
+__host__ __device__ __forceinline__ void km_fill(KmArgs& g, const __half* A, const __half* X, const __half* zeros, float* part, int M,
+                                                 int N, int K, long lda, long ldx, int x_rpg, int x_gs, int x_off, int mslice,
+                                                 int bias, int ns, int units, long gA, long gX) {
+    g.A = A; g.X = X; g.zeros = zeros;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldx = ldx;
+    g.x_rpg = x_rpg; g.x_gs = x_gs; g.x_off = x_off; g.mslice = mslice; g.bias = bias ? 1 : 0;
+    const int K1 = K + g.bias, gy = (N + 127) / 128;
+    g.bias_edge = (g.bias && K % 128 == 0) ? 1 : 0;
+    g.gx = g.bias_edge ? K / 128 : (K1 + 127) / 128;
+    GemmArgs& e = g.e;      // a plain fp32 store of the partials: everything else stays zero / null
+    e.nseg = 1; e.M = N; e.N = K1; e.sC = (long)N * K1; e.C32 = part; e.ldc = K1;
+    e.scale = 1.f; e.rpg = 1; e.zdiv = 1; e.gx = g.gx; e.gy = gy;
+    g.gA = gA; g.gX = gX; g.gP = (long)ns * N * K1;
+    g.tiles = g.gx * gy; g.ns = ns; g.units = units;
+    g.xcd = units % 8 == 0 ? 1 : 0;
+}
+
+// One weight gradient as the launchers take it (the arguments of wc_gemm_km_f16_grouped)
+struct KmJob {
+    const void* dY; const void* X; float* part;
+    int M, N, K; long lda, ldx; int x_rpg, x_gs, x_off, mslice, bias, groups; long gA, gX;
+    int ns, wgs, hv;      // derived by km_check: slices, workgroups, kernel form (1: <5, 1>, 2: <4, 2>)
+};
+
+// Argument checks + the derived fields.  `cus` <= 0: the current device's CU count.
+static int km_check(KmJob& j, int cus) {
+    WC_CHECK_ARG(j.dY && j.X && j.part && j.M > 0 && j.N > 0 && j.K > 0, "wc_gemm_km_f16: bad argument");
+    WC_CHECK_ARG(j.groups >= 1 && j.groups <= 65535 && j.gA % 8 == 0 && j.gX % 8 == 0, "wc_gemm_km_f16_grouped: bad group strides");
+    WC_CHECK_ARG(j.lda % 8 == 0 && j.ldx % 8 == 0 && j.lda >= j.N && j.ldx >= j.K && ((uintptr_t)j.dY | (uintptr_t)j.X) % 16 == 0,
+                 "wc_gemm_km_f16: operand rows must be 16-byte aligned (lda, ldx %% 8 == 0)");
+    WC_CHECK_ARG(j.mslice > 0 && j.mslice % 64 == 0, "wc_gemm_km_f16: mslice must be a positive multiple of 64");
+    WC_CHECK_ARG(j.x_rpg >= 1 && j.x_gs >= 0 && j.x_off >= 0, "wc_gemm_km_f16: bad row map");
+    {   // the kernel addresses both operands with 32-bit byte offsets from their (group) bases
+        const int M = j.M;
+        const long xrows = (long)((M - 1) / j.x_rpg) * j.x_gs + (j.x_rpg - 1 < M - 1 ? j.x_rpg - 1 : M - 1) + j.x_off + 1;
+        WC_CHECK_ARG((long)M * j.lda * 2 < (1L << 32) && xrows * j.ldx * 2 < (1L << 32), "wc_gemm_km_f16: operands of 4 GiB and more are not supported");
+    }
+    j.ns = wc_cdiv(j.M, j.mslice);
+    WC_CHECK_ARG(j.ns <= 65535, "wc_gemm_km_f16: too many slices");
+    KmArgs g = {};
+    km_fill(g, nullptr, nullptr, nullptr, nullptr, j.M, j.N, j.K, j.lda, j.ldx, j.x_rpg, j.x_gs, j.x_off, j.mslice, j.bias, j.ns,
+            j.groups * j.ns, j.gA, j.gX);
+    WC_CHECK_ARG((long)g.tiles * g.units < (1L << 31), "wc_gemm_km_f16: grid too large");
+    j.wgs = g.tiles * g.units;
+    // at most one workgroup per CU: eight waves, 64-token stages
+    j.hv = (j.wgs <= (cus > 0 ? cus : gemm_cu_count()) && j.mslice >= 128) ? 2 : 1;
+    return WC_OK;
+}
+
+static int km_reserve_lds();      // (defined behind the multi-job kernel)
+
 // part: (nslices, N, K + bias) fp32 with nslices = ceil(M / mslice); zeros: device buffer of >= 16 zero bytes.
-// groups > 1: `groups` weight gradients of one shape in one launch (blockIdx.y): group i reads dY + i*gA and X + i*gX
+// groups > 1: `groups` weight gradients of one shape in one launch: group i reads dY + i*gA and X + i*gX
 // (elements) and writes part + i * nslices * N * (K + bias).
 extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N,
                                       int K, int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, int groups,
                                       long gA, long gX, void* stream) {
-    WC_CHECK_ARG(dY && X && zeros && part && M > 0 && N > 0 && K > 0, "wc_gemm_km_f16: bad argument");
-    WC_CHECK_ARG(groups >= 1 && groups <= 65535 && gA % 8 == 0 && gX % 8 == 0, "wc_gemm_km_f16_grouped: bad group strides");
-    WC_CHECK_ARG(lda % 8 == 0 && ldx % 8 == 0 && lda >= N && ldx >= K && ((uintptr_t)dY | (uintptr_t)X | (uintptr_t)zeros) % 16 == 0,
-                 "wc_gemm_km_f16: operand rows must be 16-byte aligned (lda, ldx %% 8 == 0)");
-    WC_CHECK_ARG(mslice > 0 && mslice % 64 == 0, "wc_gemm_km_f16: mslice must be a positive multiple of 64");
-    WC_CHECK_ARG(x_rpg >= 1 && x_gs >= 0 && x_off >= 0, "wc_gemm_km_f16: bad row map");
-    {   // the kernel addresses both operands with 32-bit byte offsets from their (group) bases
-        const long xrows = (long)((M - 1) / x_rpg) * x_gs + (x_rpg - 1 < M - 1 ? x_rpg - 1 : M - 1) + x_off + 1;
-        WC_CHECK_ARG((long)M * lda * 2 < (1L << 32) && xrows * ldx * 2 < (1L << 32), "wc_gemm_km_f16: operands of 4 GiB and more are not supported");
-    }
-    const int ns = wc_cdiv(M, mslice);
-    WC_CHECK_ARG(ns <= 65535, "wc_gemm_km_f16: too many slices");
+    WC_CHECK_ARG(zeros && (uintptr_t)zeros % 16 == 0, "wc_gemm_km_f16: bad argument");
+    KmJob j = {dY, X, part, M, N, K, lda, ldx, x_rpg, x_gs, x_off, mslice, bias, groups, gA, gX, 0, 0, 0};
+    if (const int rc = km_check(j, 0)) return rc;
     KmArgs g = {};
-    g.A = (const __half*)dY; g.X = (const __half*)X; g.zeros = (const __half*)zeros;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldx = ldx;
-    g.x_rpg = x_rpg; g.x_gs = x_gs; g.x_off = x_off; g.mslice = mslice; g.bias = bias ? 1 : 0;
-    const int K1 = K + g.bias;
-    g.bias_edge = (g.bias && K % 128 == 0) ? 1 : 0;
-    g.gx = g.bias_edge ? K / 128 : wc_cdiv(K1, 128);
-    GemmArgs& e = g.e;      // a plain fp32 store of the partials: everything else stays zero / null
-    e.nseg = 1; e.M = N; e.N = K1; e.sC = (long)N * K1; e.C32 = part; e.ldc = K1;
-    e.scale = 1.f; e.rpg = 1; e.zdiv = 1; e.gx = g.gx; e.gy = wc_cdiv(N, 128);
-    g.gA = gA; g.gX = gX; g.gP = (long)ns * N * K1;
-    g.tiles = g.gx * wc_cdiv(N, 128); g.ns = ns; g.units = groups * ns;
-    g.xcd = g.units % 8 == 0 ? 1 : 0;
-    WC_CHECK_ARG((long)g.tiles * g.units < (1L << 31), "wc_gemm_km_f16: grid too large");
-    dim3 grid((unsigned)(g.tiles * g.units));
+    km_fill(g, (const __half*)dY, (const __half*)X, (const __half*)zeros, part, M, N, K, lda, ldx, x_rpg, x_gs, x_off, mslice, bias,
+            j.ns, groups * j.ns, gA, gX);
+    dim3 grid((unsigned)j.wgs);
     const int pr = wc_prof_begin(stream);
     const int sl = shape_log_begin(stream);
-    static bool lds_attr_set = false;
-    if (!lds_attr_set) {
-        WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_km_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256) == hipSuccess &&
-                         hipFuncSetAttribute((const void*)gemm_km_kernel<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 64 * 256) == hipSuccess,
-                     "wc_gemm_km_f16: cannot reserve 128 KiB of LDS");
-        lds_attr_set = true;
-    }
-    if ((long)g.tiles * g.units <= gemm_cu_count() && mslice >= 128)      // at most one workgroup per CU: eight waves, 64-token stages
+    if (const int rc = km_reserve_lds()) return rc;
+    if (j.hv == 2)
         hipLaunchKernelGGL((gemm_km_kernel<4, 2>), grid, dim3(512), 4 * 128 * 256, (hipStream_t)stream, g);
     else
         hipLaunchKernelGGL((gemm_km_kernel<5, 1>), grid, dim3(256), 5 * 64 * 256, (hipStream_t)stream, g);
-    shape_log_end(sl, "km", M, N, K1, 1, groups, ns, 0, stream);
-    wc_prof_end(pr, "gemm_km_kernel", 2.0 * M * N * K1 * groups, stream);
+    shape_log_end(sl, "km", M, N, g.e.N, 1, groups, j.ns, 0, stream);
+    wc_prof_end(pr, "gemm_km_kernel", 2.0 * M * N * g.e.N * groups, stream);
     WC_LAUNCH_CHECK("gemm_km_kernel");
     return WC_OK;
 }
@@ -342,6 +383,186 @@ extern "C" int wc_gemm_km_f16_grouped(const void* dY, long lda, const void* X, l
 extern "C" int wc_gemm_km_f16(const void* dY, long lda, const void* X, long ldx, const void* zeros, int M, int N, int K,
                               int x_rpg, int x_gs, int x_off, int mslice, int bias, float* part, void* stream) {
     return wc_gemm_km_f16_grouped(dY, lda, X, ldx, zeros, M, N, K, x_rpg, x_gs, x_off, mslice, bias, part, 1, 0, 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// MANY weight gradients in ONE grid.  A training step's backward has 16 of them (70 with the ViT-CoMer inserts) and nothing
+// consumes one before the optimizer: launched alone, each must fill the chip by itself (fine split-K slices, a launch ramp,
+// prologue and tail per gradient); queued and launched together they are thousands of workgroups that back-fill each other.
+// The table travels BY VALUE in the kernel arguments, like SumJobs below (nothing a captured graph could find overwritten on
+// replay); KMJ_MAX jobs of 92 bytes stay under the 4 KiB argument limit, longer queues go out as several launches.
+// first[q] = id of job q's first workgroup, a MULTIPLE OF 8 so that `id % 8` (the XCD a workgroup lands on) is the same inside
+// the job as in a launch of its own; the up to 7 ids between a job's end and the next start exit at once.  Entries behind
+// the last job hold INT_MAX: the search below never looks past the table and never selects them.
+#define KMJ_MAX 32
+struct KmJobs {
+    const __half* zeros;
+    int first[KMJ_MAX];
+    const __half* A[KMJ_MAX];
+    const __half* X[KMJ_MAX];
+    float* P[KMJ_MAX];
+    long gA[KMJ_MAX], gX[KMJ_MAX];
+    int M[KMJ_MAX], N[KMJ_MAX], K[KMJ_MAX], lda[KMJ_MAX], ldx[KMJ_MAX], x_rpg[KMJ_MAX], x_gs[KMJ_MAX], x_off[KMJ_MAX];
+    int mslice[KMJ_MAX], bias[KMJ_MAX], ns[KMJ_MAX], units[KMJ_MAX];
+};
+static_assert(sizeof(KmJobs) <= 3072, "KmJobs must stay well under the 4 KiB kernel-argument limit");
+
+// job of workgroup id `bid`: the last one whose first id is <= bid (a fixed-length scan of wave-uniform values)
+__host__ __device__ __forceinline__ int km_find_job(const int* first, int bid) {
+    int q = 0;
+#pragma unroll
+    for (int i = 1; i < KMJ_MAX; ++i) q += bid >= first[i] ? 1 : 0;
+    return q;
+}
+
+template <int NST, int HV>
+__global__ __launch_bounds__(256 * HV, (HV == 1 && NST <= 5) ? 2 : 1) void gemm_km_multi_kernel(KmJobs j) {
+    const int q = km_find_job(j.first, blockIdx.x);      // 0 .. KMJ_MAX - 1
+    KmArgs g = {};
+    km_fill(g, j.A[q], j.X[q], j.zeros, j.P[q], j.M[q], j.N[q], j.K[q], j.lda[q], j.ldx[q], j.x_rpg[q], j.x_gs[q], j.x_off[q],
+            j.mslice[q], j.bias[q], j.ns[q], j.units[q], j.gA[q], j.gX[q]);
+    const int bid = blockIdx.x - j.first[q];
+    if (bid >= g.tiles * g.units) return;                // padding up to the next job's multiple of 8
+    gemm_km_body<NST, HV>(g, bid);
+}
+
+static int km_reserve_lds() {
+    static bool lds_attr_set = false;
+    if (!lds_attr_set) {
+        WC_CHECK_ARG(hipFuncSetAttribute((const void*)gemm_km_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256) == hipSuccess &&
+                         hipFuncSetAttribute((const void*)gemm_km_kernel<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 64 * 256) == hipSuccess &&
+                         hipFuncSetAttribute((const void*)gemm_km_multi_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 256) == hipSuccess &&
+                         hipFuncSetAttribute((const void*)gemm_km_multi_kernel<5, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 64 * 256) == hipSuccess,
+                     "wc_gemm_km_f16: cannot reserve 128 KiB of LDS");
+        lds_attr_set = true;
+    }
+    return WC_OK;
+}
+
+// The launches of a job list: jobs sorted by the length of a workgroup's K loop, longest first (the tail of a launch is then
+// made of short workgroups; stable, so equal jobs keep their order), split by kernel form -- each job runs in the form a launch
+// of its own would pick, so its partials are bit-identical to that launch's -- and into chunks of KMJ_MAX.
+struct KmLaunch { int hv, n, grid; int job[KMJ_MAX], first[KMJ_MAX]; };
+#define KM_JOB_FIELDS 16
+static int km_plan(const int64_t* jobs, int count, int cus, KmJob* js, KmLaunch* ls, int max_launches, int* nl) {
+    int* order = (int*)alloca(sizeof(int) * count);
+    for (int i = 0; i < count; ++i) {
+        const int64_t* e = jobs + (long)i * KM_JOB_FIELDS;
+        for (int k = 3; k < 14; ++k) WC_CHECK_ARG(e[k] >= 0 && e[k] < (1L << 31), "wc_gemm_km_f16_multi: job field out of range");
+        js[i] = KmJob{reinterpret_cast<const void*>(e[0]), reinterpret_cast<const void*>(e[1]), reinterpret_cast<float*>(e[2]),
+                      (int)e[3], (int)e[4], (int)e[5], (long)e[6], (long)e[7], (int)e[8], (int)e[9], (int)e[10], (int)e[11],
+                      (int)e[12], (int)e[13], (long)e[14], (long)e[15], 0, 0, 0};
+        if (const int rc = km_check(js[i], cus)) return rc;
+        // insertion sort on the tokens of a workgroup's loop, descending, stable
+        const int len = js[i].M < js[i].mslice ? js[i].M : js[i].mslice;
+        int p = i;
+        for (; p > 0; --p) {
+            const KmJob& o = js[order[p - 1]];
+            if ((o.M < o.mslice ? o.M : o.mslice) >= len) break;
+            order[p] = order[p - 1];
+        }
+        order[p] = i;
+    }
+    *nl = 0;
+    for (int hv = 1; hv <= 2; ++hv) {
+        KmLaunch* cur = nullptr;
+        for (int p = 0; p < count; ++p) {
+            const KmJob& j = js[order[p]];
+            if (j.hv != hv) continue;
+            if (!cur || cur->n == KMJ_MAX || (long)cur->grid + j.wgs + 8 >= (1L << 31)) {
+                WC_CHECK_ARG(*nl < max_launches, "wc_gemm_km_f16_multi: too many launches");
+                cur = ls + (*nl)++;
+                cur->hv = hv; cur->n = 0; cur->grid = 0;
+            }
+            cur->job[cur->n] = order[p];
+            cur->first[cur->n] = cur->grid;
+            cur->n += 1;
+            cur->grid += (j.wgs + 7) / 8 * 8;
+        }
+    }
+    return WC_OK;
+}
+
+static void km_table(const KmLaunch& l, const KmJob* js, const void* zeros, KmJobs& t) {
+    t.zeros = (const __half*)zeros;
+    for (int q = 0; q < KMJ_MAX; ++q) {
+        const KmJob& j = js[l.job[q < l.n ? q : 0]];     // unused entries: a valid job that no workgroup id selects
+        t.first[q] = q < l.n ? l.first[q] : 0x7fffffff;
+        t.A[q] = (const __half*)j.dY; t.X[q] = (const __half*)j.X; t.P[q] = j.part;
+        t.gA[q] = j.gA; t.gX[q] = j.gX;
+        t.M[q] = j.M; t.N[q] = j.N; t.K[q] = j.K; t.lda[q] = (int)j.lda; t.ldx[q] = (int)j.ldx;
+        t.x_rpg[q] = j.x_rpg; t.x_gs[q] = j.x_gs; t.x_off[q] = j.x_off; t.mslice[q] = j.mslice; t.bias[q] = j.bias;
+        t.ns[q] = j.ns; t.units[q] = j.groups * j.ns;
+    }
+}
+
+// jobs: count x 16 host int64 {dY, X, part (device pointers), M, N, K, lda, ldx, x_rpg, x_gs, x_off, mslice, bias, groups, gA, gX}:
+// each job = one wc_gemm_km_f16_grouped call, in the kernel form and with the partials that call would give.
+extern "C" int wc_gemm_km_f16_multi(const int64_t* jobs, int count, const void* zeros, void* stream) {
+    WC_CHECK_ARG(jobs && count > 0 && count <= 4096 && zeros && (uintptr_t)zeros % 16 == 0, "wc_gemm_km_f16_multi: bad argument");
+    std::vector<KmJob> js(count);
+    std::vector<KmLaunch> ls(2 * (count / KMJ_MAX + 1));
+    int nl = 0;
+    if (const int rc = km_plan(jobs, count, 0, js.data(), ls.data(), (int)ls.size(), &nl)) return rc;
+    if (const int rc = km_reserve_lds()) return rc;
+    for (int i = 0; i < nl; ++i) {
+        KmJobs t;
+        km_table(ls[i], js.data(), zeros, t);
+        double flops = 0;
+        for (int q = 0; q < ls[i].n; ++q) {
+            const KmJob& j = js[ls[i].job[q]];
+            flops += 2.0 * j.M * j.N * (j.K + (j.bias ? 1 : 0)) * j.groups;
+        }
+        const int pr = wc_prof_begin(stream);
+        if (ls[i].hv == 2)
+            hipLaunchKernelGGL((gemm_km_multi_kernel<4, 2>), dim3((unsigned)ls[i].grid), dim3(512), 4 * 128 * 256, (hipStream_t)stream, t);
+        else
+            hipLaunchKernelGGL((gemm_km_multi_kernel<5, 1>), dim3((unsigned)ls[i].grid), dim3(256), 5 * 64 * 256, (hipStream_t)stream, t);
+        wc_prof_end(pr, "gemm_km_multi_kernel", flops, stream);
+        WC_LAUNCH_CHECK("gemm_km_multi_kernel");
+    }
+    return WC_OK;
+}
+
+// The plan of wc_gemm_km_f16_multi without launching (host only; cus = CU count the kernel form is chosen for, <= 0: the
+// device's).  Per job i (input order): launch[i], first[i] (its first workgroup id there), pos[i] (its place in that launch's
+// table); per launch l < *nlaunches (<= max_launches): grids[l] workgroups, forms[l] = 1 (<5, 1>) or 2 (<4, 2>).
+extern "C" int wc_gemm_km_multi_plan(const int64_t* jobs, int count, int cus, int* launch, int* first, int* pos, int* grids,
+                                     int* forms, int max_launches, int* nlaunches) {
+    WC_CHECK_ARG(jobs && count > 0 && count <= 4096 && launch && first && pos && grids && forms && nlaunches && max_launches > 0,
+                 "wc_gemm_km_multi_plan: bad argument");
+    std::vector<KmJob> js(count);
+    std::vector<KmLaunch> ls(max_launches);
+    if (const int rc = km_plan(jobs, count, cus, js.data(), ls.data(), max_launches, nlaunches)) return rc;
+    for (int l = 0; l < *nlaunches; ++l) {
+        grids[l] = ls[l].grid; forms[l] = ls[l].hv;
+        for (int q = 0; q < ls[l].n; ++q) { launch[ls[l].job[q]] = l; first[ls[l].job[q]] = ls[l].first[q]; pos[ls[l].job[q]] = q; }
+    }
+    return WC_OK;
+}
+
+// Which (job, unit, tile) workgroup `wg` of launch `l` computes: the kernel's own table, search and index arithmetic run on the
+// host.  out[0] = job (input order) or -1 for a padding id, out[1] = unit (group * slices + slice), out[2] = output tile.
+extern "C" int wc_gemm_km_multi_locate(const int64_t* jobs, int count, int cus, int l, int wg, int* out) {
+    WC_CHECK_ARG(jobs && count > 0 && count <= 4096 && out && l >= 0 && wg >= 0, "wc_gemm_km_multi_locate: bad argument");
+    std::vector<KmJob> js(count);
+    std::vector<KmLaunch> ls(2 * (count / KMJ_MAX + 1));
+    int nl = 0;
+    if (const int rc = km_plan(jobs, count, cus, js.data(), ls.data(), (int)ls.size(), &nl)) return rc;
+    WC_CHECK_ARG(l < nl && wg < ls[l].grid, "wc_gemm_km_multi_locate: no such workgroup");
+    KmJobs t;
+    km_table(ls[l], js.data(), nullptr, t);
+    const int q = km_find_job(t.first, wg);
+    KmArgs g = {};
+    km_fill(g, t.A[q], t.X[q], t.zeros, t.P[q], t.M[q], t.N[q], t.K[q], t.lda[q], t.ldx[q], t.x_rpg[q], t.x_gs[q], t.x_off[q],
+            t.mslice[q], t.bias[q], t.ns[q], t.units[q], t.gA[q], t.gX[q]);
+    const int bid = wg - t.first[q];
+    out[0] = -1; out[1] = out[2] = 0;
+    if (bid < g.tiles * g.units) {
+        out[0] = ls[l].job[q];
+        km_unit_tile(bid, g.tiles, g.xcd, out[1], out[2]);
+    }
+    return WC_OK;
 }
 
 // out[i] = alpha * sum_s part[s*n + i]   (split-K reduction: slices are a batched GEMM over K ranges)

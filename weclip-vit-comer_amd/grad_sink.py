@@ -1,10 +1,17 @@
 """Where the explicit backward engines (head_engine, comer_engine) put their parameter gradients.
 
 One decision, shared by both: this step's flat all-reduce bucket (train_step.GradBucket, zeroed every step) is WRITTEN in
-place, each gradient exactly once per backward, and the split-K reductions of all weight gradients go out as ONE launch
-(wc_sum_slices_wb_multi, instead of one launch of 5-7 us at the launch floor per weight gradient).  A `.grad` outside the
-bucket (gradient accumulation, a TrainStep without a bucket, a harness calling backward twice) gets a fresh tensor that
-autograd accumulates as usual.
+place, each gradient exactly once per backward, and the weight-gradient GEMMs and their split-K reductions are QUEUED: nothing
+in a backward pass reads a weight gradient, so all GEMMs go out as one grid per kernel form (wc_gemm_km_f16_multi: launched
+alone, each of them has to fill the chip by itself and pays its own ramp, prologue and tail) and all reductions as ONE
+launch behind them (wc_sum_slices_wb_multi, instead of one launch of 5-7 us at the launch floor per weight gradient).  A
+`.grad` outside the bucket (gradient accumulation, a TrainStep without a bucket, a harness calling backward twice) gets a
+fresh tensor that autograd accumulates as usual.
+
+The queue holds references to dY, X and the partials until the launch, so the caching allocator cannot hand their memory
+out again; what it cannot see is a caller that WRITES an operand again before the sink exits (an in-place kernel, a scratch
+buffer used twice, a view of a buffer that is rewritten).  Such a gradient has to be launched at once
+(`GradSink(defer=False)`, or a `flush()` in front of the overwrite); the engines have none.
 """
 import ctypes
 import struct
@@ -39,11 +46,13 @@ def handback(params, grads):
 
 class GradSink:
     """The parameter gradients of one backward pass: `bucket` is the (lo, hi) byte address range of the gradient bucket
-    that may be written in place, or None.  Use as a context manager around the backward: the queued reductions are
-    launched on a clean exit."""
+    that may be written in place, or None.  Use as a context manager around the backward: the queued GEMMs and reductions
+    are launched on a clean exit.  defer=False launches every GEMM where it is requested (tests, A/B): same partials."""
 
-    def __init__(self, bucket=None):
+    def __init__(self, bucket=None, defer=True):
         self.bucket = bucket
+        self.defer = defer
+        self._gemms = []            # ops.wgrad_partials(queue=...) jobs: ((dY, X, partials kept alive), [16 int64 job fields])
         self.grads = {}             # id(param) -> gradient tensor
         self._jobs = []             # ((tensors kept alive until the launch), [8 int64 job fields])
 
@@ -84,13 +93,15 @@ class GradSink:
 
     def wgrad(self, dy16, x16, M, N, K, alpha, outs, *, ns, groups=1, sw=0, sb=0, **kw):
         """Split-K partials of dY^T [X | 1] (ops.wgrad_partials with `ns` slices; kw: lda, ldx, xmap, gA, gX) and their
-        reduction, alpha * the slice sum, queued into outs = [(dw, db)]:
+        reduction, alpha * the slice sum, both queued until `flush`, into outs = [(dw, db)]:
           * one Linear: dw (N, K), db (N);
           * Linears stacked along N (one GEMM over their columns): each pair takes the next db.numel() rows of the partials;
           * groups > 1: `groups` gradients of one shape in one GEMM, outs holds group 0's and group g's lie at dw + g * sw,
             db + g * sb (elements)."""
         if sum(db.numel() for _, db in outs) != N:
             raise ValueError("GradSink.wgrad: the destinations do not cover the N gradient rows")
+        if self.defer:
+            kw["queue"] = self._gemms
         part, ns = ops.wgrad_partials(dy16, x16, M, N, K, slices=ns, bias=True, groups=groups, **kw)
         abits = struct.unpack("<I", struct.pack("<f", alpha))[0]
         stride = N * (K + 1)                # elements between two slices
@@ -104,7 +115,8 @@ class GradSink:
             r0 += rows
 
     def flush(self):
-        """Every queued reduction in ONE launch."""
+        """Every queued GEMM in one grid per kernel form, then every queued reduction in ONE launch."""
+        ops.wgrad_launch(self._gemms)
         jobs, self._jobs = self._jobs, []
         if jobs:
             flat = [v for _, fields in jobs for v in fields]

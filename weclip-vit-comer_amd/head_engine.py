@@ -43,6 +43,9 @@ def _uniform_stride(ts):
 
 
 class HeadEngine:
+    # weight-gradient GEMMs queued into one launch at the end of the backward (False: each where it is requested: tests, A/B)
+    defer_wgrads = True
+
     def __init__(self, fuse, dec, attn_pred=True):
         """attn_pred=False: seg-only mode (the supervised variant, WeCLIP_model/model_attn_aff_voc_seg.py): no Gram GEMM, no
         sigmoid and no fp16 hi/lo copy of F (only the Gram product reads it); forward returns (seg, None, ctx) and the
@@ -206,9 +209,10 @@ class HeadEngine:
     # ------------------------------------------------------------------------------ backward
     def backward(self, ctx, dseg, dap):
         """dseg (B,nc,h,w) / dap (B,hw,hw) fp32 (either may be None).  Returns ({id(param): grad}, the gradient w.r.t.
-        F_rows or None).  The split-K reductions of all weight gradients are collected and run as ONE launch at the end."""
+        F_rows or None).  The weight-gradient GEMMs and their split-K reductions are collected and run at the end: one grid
+        per kernel form, then ONE reduction launch (`defer_wgrads` False: every GEMM where it is requested, for A/B)."""
         # (the weight-gradient GEMMs on a second stream beside the data-gradient chain were measured neutral in round 3: one stream)
-        with GradSink(self.direct_grads) as sink:
+        with GradSink(self.direct_grads, defer=self.defer_wgrads) as sink:
             dF = self._backward_impl(ctx, dseg, dap, sink)
         return sink.grads, dF
 

@@ -1,6 +1,7 @@
 """Typed Python wrappers over the C ABI (include/weclip_hip.h).  Tensors in, tensors out; every
 wrapper allocates its outputs with torch (device memory + current stream only) and calls the
 HIP library.  No arithmetic happens in torch here."""
+import ctypes
 import math
 
 import torch
@@ -270,27 +271,47 @@ def wgrad_tiles(N, K, bias=True):
     return ((N + 127) // 128) * kt
 
 
-def wgrad_partials(dy16, x16, M, N, K, *, lda=None, ldx=None, slices=1, bias=True, xmap=None, groups=1, gA=0, gX=0):
+def wgrad_partials(dy16, x16, M, N, K, *, lda=None, ldx=None, slices=1, bias=True, xmap=None, groups=1, gA=0, gX=0, queue=None):
     """Split-K partials of dW = dY^T X (and db = dY^T 1 as column K) from ROW-MAJOR fp16 operands
     dy16 (M, lda), x16 (rows, ldx): -> (part (ns, N, K + bias) fp32, ns).  xmap = (rows_per_group, group_stride,
     offset): token m reads X row (m // rpg) * stride + m % rpg + offset (patch rows of a (B, 1 + hw, C) tensor).
     groups > 1: that many gradients of one shape in one launch, group i reading dy16 + i*gA and x16 + i*gX (elements);
-    part is then (groups, ns, N, K + bias)."""
+    part is then (groups, ns, N, K + bias).
+    queue (a list): the GEMM is not launched but appended as a job of `wgrad_launch` -- the partials are allocated and
+    returned, and the queue keeps dy16, x16 and the partials alive until that launch."""
     L.require_gpu()
     lda = N if lda is None else lda
     ldx = K if ldx is None else ldx
     dev = dy16.device
-    z = _ZEROS.get(dev)
-    if z is None:
-        z = _ZEROS[dev] = torch.zeros(64, device=dev, dtype=F16)
     mslice = (-(-M // slices) + 63) // 64 * 64
     ns = -(-M // mslice)
     K1 = K + (1 if bias else 0)
     part = torch.empty((ns, N, K1) if groups == 1 else (groups, ns, N, K1), device=dev, dtype=F32)
     rpg, gs, off = xmap if xmap is not None else (max(M, 64), 0, 0)
-    L.lib().wc_gemm_km_f16_grouped(L.ptr(dy16, F16, "dY"), lda, L.ptr(x16, F16, "X"), ldx, L.ptr(z), M, N, K, rpg, gs, off,
+    if queue is not None:
+        queue.append(((dy16, x16, part), [L.ptr(dy16, F16, "dY").value, L.ptr(x16, F16, "X").value, part.data_ptr(), M, N, K, lda,
+                                          ldx, rpg, gs, off, mslice, 1 if bias else 0, groups, gA, gX]))
+        return part, ns
+    L.lib().wc_gemm_km_f16_grouped(L.ptr(dy16, F16, "dY"), lda, L.ptr(x16, F16, "X"), ldx, L.ptr(_zeros(dev)), M, N, K, rpg, gs, off,
                                    mslice, 1 if bias else 0, L.ptr(part), groups, gA, gX, L.stream())
     return part, ns
+
+
+def _zeros(dev):
+    z = _ZEROS.get(dev)
+    if z is None:
+        z = _ZEROS[dev] = torch.zeros(64, device=dev, dtype=F16)
+    return z
+
+
+def wgrad_launch(queue):
+    """Every weight-gradient GEMM queued by `wgrad_partials(queue=...)` in one grid per kernel form (csrc/gemm_km.hip
+    gemm_km_multi_kernel): each job writes exactly the partials a launch of its own would.  Empties the queue."""
+    jobs = list(queue)
+    del queue[:]
+    if jobs:
+        flat = [v for _, fields in jobs for v in fields]
+        L.lib().wc_gemm_km_f16_multi((ctypes.c_int64 * len(flat))(*flat), len(jobs), L.ptr(_zeros(jobs[0][0][0].device)), L.stream())
 
 
 def colsum(src, R, C, *, ld=None, alpha=1.0, round16=False, out=None):
