@@ -758,6 +758,51 @@ int wc_eval_finish(const float* seg1, const float* msc, const long* cam, const l
 int wc_label_finish(const long* pred, const long* gt, void* out_u8, void* cmap_rgb, long* hist, int* flag, int H, int W, int nc,
                     void* stream);
 
+/* ---- the AFA pseudo-label chain of utils/camutils.py (csrc/camlabel.hip) ----------------------- */
+/* Every entry checks its limits first and returns WC_ERR_ARG with nothing launched; everything runs on `stream`; no entry
+ * allocates, reads device memory on the host or uses an atomic (two calls on the same input give the same bits).
+ * A box is a row (y0, y1, x0, x1) of int32 in device memory, applied as the Python slices [y0:y1, x0:x1] are (clamped to the
+ * axis, a negative bound counted from its end).
+ * wc_aff_propagate: utils/camutils.py:249-275 (with_bkg = 0) and :277-317 (with_bkg = 1), the random walk of the CAMs over the
+ *   learned affinity.  aff (B,n,n) f32, read once and NOT modified (the reference zeroes it in place); mask (n,n) f32 or NULL;
+ *   cams (B,C,n) f32; cls (B,C) f32, needed with with_bkg and ignored without; out (B,C+with_bkg,n) f32.
+ *     A[b,i,j] = (aff[b,i,j] * [mask[i,j] != 0])^2,  s[b,j] = sum_i A[b,i,j],  out[b,k,j] = (sum_i X[b,k,i] A[b,i,j]) / (s[b,j] + eps)
+ *   with_bkg = 1: eps = 1e-1, rows k in {0} + {1 + c : cls[b,c] != 0}, X = soft-max over exactly those rows of [bkg_score, cams],
+ *   every other row of out is 0.  with_bkg = 0: eps = 1e-4, X = cams.  f32-input MFMA products, |error| <= 2^-20 of the value.
+ *   ws: *n_floats floats from wc_aff_propagate_workspace_floats (the operand X, transposed and padded).
+ *   Limits: non-null pointers, B in [1,65535], n in [1,4096], C + with_bkg in [1,128], finite bkg_score.
+ * wc_cam_to_label: utils/camutils.py:8-28.  cam (B,C,H,W) f32, cls (B,C) f32, box (B,4) or NULL, label (B,H,W) int64,
+ *   valid_cam (B,C,H,W) f32 = cls * cam or NULL.  v = max_c cls * cam (the first maximum wins), label = 1 + argmax, 0 where
+ *   v <= bkg_score; with a box and ignore_mid: ignore_index where v <= high_thre, then 0 where v <= low_thre; with a box:
+ *   ignore_index outside it.  Without a box the thresholds of ignore_mid are not applied, as in the reference (:17-18).
+ * wc_box_ignore: utils/camutils.py:30-37.  label / out (B,H,W) int64 (is_f32 = 0) or f32 (is_f32 = 1): ignore_index outside the box.
+ * wc_bkg_refine_prep / wc_bkg_refine_finish: utils/camutils.py:149-198 on either side of ONE refinement call for the batch.
+ *   meta (B, 1 + Kmax) int32 per image: its channel count nch in [1,Kmax], then the label value of each channel (0 = background,
+ *   1 + class, ascending).  prep: cams (B,C,H,W) -> stack (B, 2 Kmax, h2, w2): per pixel of the (h2,w2) grid the bilinear
+ *   (align_corners=False) down-sample of the image's channels, the background being the constant high_thre (first half) or
+ *   low_thre (second half), and the soft-max over the image's nch channels; channels >= nch are 0.  finish: stack as refined,
+ *   bilinear up-sample to (H,W) of both halves, arg-max over nch channels (first maximum), label values lh / ll through meta;
+ *   out (B,H,W) f32 = lh where lh != 0, ignore_index where lh == 0, 0 where lh == ll == 0, ignore_index outside the box.
+ * wc_box_gather / wc_box_scatter: utils/camutils.py:200-223 for G images whose boxes have one size (hb,wb).  meta (G, 3 + Kg)
+ *   int32 per member: image index, y0, x0 of the (already clamped) box, the channel of each compact slot or -1.  gather:
+ *   cams_out (G,Kg,hb,wb) = the crop of the listed channels, 0 in padding slots; img_out (G,3,hb/2,wb/2) = the bilinear
+ *   (align_corners=False) down-sample of the image crop.  scatter: out[image, channel, box] = src (G,Kg,hb,wb); out is zeroed by
+ *   the caller.  A member that does not fit (B,C,H,W) is skipped.  hb, wb >= 2. */
+int wc_aff_propagate_workspace_floats(int B, int n, int C, int with_bkg, long* n_floats);           /* HOST out-parameter */
+int wc_aff_propagate(const float* aff, const float* mask, const float* cams, const float* cls, float* out, void* ws, int B, int n,
+                     int C, float bkg_score, int with_bkg, void* stream);
+int wc_cam_to_label(const float* cam, const float* cls, const int* box, long* label, float* valid_cam, int B, int C, int H, int W,
+                    float bkg_score, float high_thre, float low_thre, int ignore_mid, long ignore_index, void* stream);
+int wc_box_ignore(const void* label, const int* box, void* out, int B, int H, int W, int is_f32, long ignore_index, void* stream);
+int wc_bkg_refine_prep(const float* cams, const int* meta, float* stack, int B, int C, int H, int W, int h2, int w2, int Kmax,
+                       float high_thre, float low_thre, void* stream);
+int wc_bkg_refine_finish(const float* stack, const int* meta, const int* box, float* out, int B, int H, int W, int h2, int w2,
+                         int Kmax, float ignore_index, void* stream);
+int wc_box_gather(const float* cams, const float* images, const int* meta, float* cams_out, float* img_out, int G, int B, int C,
+                  int H, int W, int hb, int wb, int Kg, void* stream);
+int wc_box_scatter(const float* src, const int* meta, float* out, int G, int B, int C, int H, int W, int hb, int wb, int Kg,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -401,6 +401,21 @@ def _energy_backward(ctx, grad_loss, grad_A):
 torch.library.register_autograd(f"{_LIB}::dense_energy", _energy_backward, setup_context=_energy_setup)
 
 
+@torch.library.custom_op(f"{_LIB}::aff_propagate", mutates_args=(), device_types="cuda")
+def aff_propagate(aff: Tensor, cams: Tensor, mask: Optional[Tensor], cls: Optional[Tensor], bkg_score: float,
+                  with_bkg: bool) -> Tensor:
+    """The random walk of the CAMs over the learned affinity (reference utils/camutils.py:249-317; csrc/camlabel.hip): aff
+    (B,n,n), cams (B,C,n), mask (n,n) or None, cls (B,C) (needed with with_bkg) -> (B,C+with_bkg,n) f32.  `aff` is not modified.
+    No autograd: the reference detaches."""
+    from .utils.camutils import _aff_propagate as walk
+    return walk(aff, cams, mask, cls, bkg_score, with_bkg)
+
+
+@aff_propagate.register_fake
+def _(aff, cams, mask, cls, bkg_score, with_bkg):
+    return cams.new_empty((cams.shape[0], cams.shape[1] + (1 if with_bkg else 0), cams.shape[2]), dtype=F32)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
-       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd")
+       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "aff_propagate")
