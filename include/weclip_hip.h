@@ -86,23 +86,16 @@ int wc_bilinear_resize_bwd(const float* gdst, float* gsrc, float* tmp, int plane
  * wc_seg_loss_fwd: sums (8) = [sum nll over label==0, #label==0, sum nll over fg labels, #fg,
  *                  loss = 0.5*(sums[0]/sums[1] + sums[2]/sums[3]), 0.5/sums[1], 0.5/sums[3], 0]
  *                  (sums[5..6]: the backward weights wts for an upstream gradient of 1);
- *                  part: ceil(W/64)*ceil(H/4)*B*4 f32.
- * wc_seg_loss_bwd: ghr (B,nc,H,W) = wts[bg|fg] * (softmax - onehot) per pixel (0 for ignored); the
- *                  low-res gradient is wc_bilinear_resize_bwd(ghr). */
+ *                  part: ceil(W/64)*ceil(H/4)*B*4 f32.  Forward only; 1 <= nc <= 128, H >= h, W >= w. */
 int wc_seg_loss_fwd(const float* seg, const int64_t* label, float* part, float* sums, int B, int nc, int h, int w,
                     int H, int W, int ignore, void* stream);
-int wc_seg_loss_bwd(const float* seg, const int64_t* label, const float* wts, float* ghr, int B, int nc, int h,
-                    int w, int H, int W, int ignore, void* stream);
-/* The same backward without the (B,nc,H,W) high-resolution gradient: the soft-max gradient is formed per pixel inside the
- * Y pass of the separable bilinear backward (fixed summation order), then the X pass.  tmp: workspace B*nc*h*W f32;
- * out: (B,nc,h,w).  Same summation order as wc_seg_loss_bwd + wc_bilinear_resize_bwd (bit-identical for nc > 24; for
- * nc <= 24 the per-pixel log-sum-exp is formed max-first: equal to rounding). */
-int wc_seg_loss_bwd_fused(const float* seg, const int64_t* label, const float* wts, float* tmp, float* out, int B, int nc,
-                          int h, int w, int H, int W, int ignore, void* stream);
 
-/* Training form of the two above: loss sums (as wc_seg_loss_fwd) AND d loss / d seg for an upstream gradient of 1 in ONE
- * pass over the pixels (a label count first gives the class weights).  cnt: 2048 floats, part: 4 floats per 64 x 4 block
- * of (W, h) per image, tmp: 2*B*nc*h*W floats, grad: (B,nc,h,w).  nc <= 24.  (scripts/dist_clip_voc.py:105-113,250) */
+/* Training form: loss sums (as wc_seg_loss_fwd) AND d loss / d seg for an upstream gradient of 1 in ONE pass over the
+ * pixels (a label count first gives the class weights), a one-block reduce and the X pass of the separable bilinear
+ * backward; no host synchronisation, no atomics (bit-identical between calls).  The pixel pass is that of
+ * wc_ce_loss_fwd_bwd with the two-term weighting, and the sizes are its sizes: 1 <= nc <= 128, label at any H x W,
+ * W <= 8192.  cnt: 2048 floats; part: 4 * ceil(W/64) * ceil(h/4) * B * nchunk floats, 16-byte aligned, nchunk = 1 for
+ * nc <= 32, else ceil(nc/32); tmp: 2*B*nc*h*W floats; grad: (B,nc,h,w).  (scripts/dist_clip_voc.py:105-113,250) */
 int wc_seg_loss_fwd_bwd(const float* seg, const int64_t* label, float* cnt, float* part, float* sums, float* tmp, float* grad,
                         int B, int nc, int h, int w, int H, int W, int ignore, void* stream);
 

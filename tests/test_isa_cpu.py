@@ -19,7 +19,6 @@ ALLOWED = {
     "msda_fwd_kernel": "one-thread-per-channel fallback for head widths that are not a multiple of 4",
     "matvec_cols_kernel": "fallback of the affinity sweeps for hw % 4 != 0",
     "matvec_rows_kernel": "fallback of the affinity sweeps for hw % 4 != 0",
-    "seg_loss_bwd_y_kernel": "eight int64 label loads of a row group (COCO path); the class loads are batched",
 }
 
 

@@ -10,7 +10,10 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("B,nc,h,w,scale", [(2, 21, 4, 6, 16), (1, 5, 7, 5, 16), (2, 21, 32, 32, 16),
-                                           (1, 4, 5, 7, 9.5), (1, 3, 12, 10, 1), (1, 40, 4, 6, 16)])
+                                           (1, 4, 5, 7, 9.5), (1, 3, 12, 10, 1), (1, 40, 4, 6, 16),
+                                           # the class chunks of the pixel pass: 81 (COCO, three chunks), 32 (one chunk of 32 at
+                                           # its upper edge), 33 (one class in the second chunk), 128 (the class limit)
+                                           (1, 81, 5, 3, 16), (1, 32, 4, 6, 16), (2, 33, 3, 5, 9.5), (1, 128, 3, 4, 16)])
 def test_fused_seg_loss_forward_backward(B, nc, h, w, scale):
     from weclip_vit_comer_amd.utils.losses import get_seg_loss_fused
     g = torch.Generator().manual_seed(h)
@@ -27,7 +30,7 @@ def test_fused_seg_loss_forward_backward(B, nc, h, w, scale):
     (3.0 * out).backward()
     assert abs(out.item() - ref.item()) < 2e-5 * max(1.0, abs(ref.item()))
     np.testing.assert_allclose(x.grad.cpu().numpy(), 3.0 * ref_in.grad.numpy(), rtol=2e-3, atol=2e-7)
-    # without a gradient request the forward-only kernel runs (nc <= 24 with one: loss + gradient in one pixel pass)
+    # without a gradient request the forward-only kernel runs (with one: loss + gradient in one pixel pass)
     with torch.no_grad():
         out_ng = get_seg_loss_fused(seg.cuda(), lab.cuda())
     assert abs(out_ng.item() - out.item()) < 2e-6 * max(1.0, abs(out.item()))
@@ -67,28 +70,29 @@ def test_fused_affinity_loss_forward_backward(B, h, w, radius):
     np.testing.assert_allclose(x.grad.cpu().numpy(), 0.1 * ref_in.grad.numpy(), rtol=1e-4, atol=1e-10)
 
 
-@pytest.mark.parametrize("B,nc,h,w,scale", [(2, 21, 4, 6, 16), (1, 81, 5, 3, 16), (2, 21, 32, 32, 16)])
-def test_fused_seg_loss_backward_matches_the_two_kernel_path(B, nc, h, w, scale):
-    """wc_seg_loss_bwd_fused (soft-max gradient formed inside the Y pass, no (B, nc, H, W) tensor) vs wc_seg_loss_bwd +
-    wc_bilinear_resize_bwd: same per-pixel arithmetic, same summation order -> the same bits."""
+def test_fused_seg_loss_is_deterministic_and_refuses_bad_arguments():
     from weclip_vit_comer_amd import _lib as L
-    H, W = h * scale, w * scale
-    g = torch.Generator().manual_seed(B * nc + h)
-    seg = torch.randn(B, nc, h, w, generator=g).cuda()
-    lab = torch.randint(0, nc, (B, H, W), generator=g)
-    lab[:, :3] = 255
-    lab = lab.cuda()
-    wts = torch.tensor([0.37e-4, 0.81e-4], device="cuda")
-    F32 = torch.float32
-    ghr = torch.empty(B, nc, H, W, device="cuda")
-    L.lib().wc_seg_loss_bwd(L.ptr(seg, F32), L.ptr(lab, torch.int64), L.ptr(wts, F32), L.ptr(ghr), B, nc, h, w, H, W, 255, L.stream())
-    ref, tmp = torch.empty_like(seg), torch.empty(B * nc * h * W, device="cuda")
-    L.lib().wc_bilinear_resize_bwd(L.ptr(ghr), L.ptr(ref), L.ptr(tmp), B * nc, h, w, H, W, 0, L.stream())
-    out, tmp2 = torch.empty_like(seg), torch.empty(B * nc * h * W, device="cuda")
-    L.lib().wc_seg_loss_bwd_fused(L.ptr(seg, F32), L.ptr(lab, torch.int64), L.ptr(wts, F32), L.ptr(tmp2), L.ptr(out), B, nc, h, w, H, W,
-                                  255, L.stream())
-    assert ref.abs().max().item() > 0
-    if nc > 24:
-        assert torch.equal(out, ref)
-    else:       # the small-class-count form takes the per-pixel maximum first instead of the online log-sum-exp: equal to rounding
-        assert (out - ref).abs().max().item() <= 2e-6 * ref.abs().max().item()
+    from weclip_vit_comer_amd.utils.losses import get_seg_loss_fused
+    g = torch.Generator().manual_seed(4)
+    seg = torch.randn(4, 81, 8, 8, generator=g).cuda()
+    label = torch.randint(0, 81, (4, 128, 128), generator=g).cuda()
+    outs = []
+    for _ in range(2):
+        x = seg.clone().requires_grad_(True)
+        loss = get_seg_loss_fused(x, label, 255)
+        loss.backward()
+        outs.append((loss.detach().clone(), x.grad.clone()))
+    assert torch.isfinite(outs[0][0]).item() and outs[0][1].abs().max().item() > 0
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    # the C entry refuses before launching anything: the output buffers stay as they were
+    f32 = torch.float32
+    cnt, part, sums = torch.empty(2048, device="cuda"), torch.empty(4096, device="cuda"), torch.full((8,), 7.0, device="cuda")
+    tmp, grad = torch.empty(2 * 4 * 129 * 8 * 128, device="cuda"), torch.full((4, 129, 8, 8), 7.0, device="cuda")
+    with pytest.raises(RuntimeError, match="bad size"):
+        L.lib().wc_seg_loss_fwd_bwd(L.ptr(seg, f32), L.ptr(label, torch.int64), L.ptr(cnt), L.ptr(part), L.ptr(sums), L.ptr(tmp),
+                                    L.ptr(grad), 4, 129, 8, 8, 128, 128, 255, L.stream())
+    with pytest.raises(RuntimeError, match="null"):
+        L.lib().wc_seg_loss_fwd_bwd(L.ptr(seg, f32), None, L.ptr(cnt), L.ptr(part), L.ptr(sums), L.ptr(tmp), L.ptr(grad), 4, 81, 8, 8,
+                                    128, 128, 255, L.stream())
+    torch.cuda.synchronize()
+    assert (sums == 7.0).all().item() and (grad == 7.0).all().item()

@@ -6,6 +6,9 @@
 Medians of CUDA-event timings after warm-up.  Not part of bench.py.
 
     python tools/seg_bench.py [--batch 16] [--size 512] [--steps 10] [--warmup 3]
+
+--loss-only skips the model legs: one JSON line with us of forward + backward of get_seg_loss_fused and get_ce_loss_fused
+at nc = 21 (VOC) and nc = 81 (COCO), B x nc x size/16 x size/16 logits against size x size labels.
 """
 import argparse
 import json
@@ -35,13 +38,31 @@ def _median_ms(fn, steps, warmup):
     return ts[len(ts) // 2]
 
 
+def loss_only(B, S, steps, warmup):
+    from weclip_vit_comer_amd.utils.losses import get_ce_loss_fused, get_seg_loss_fused
+    out = {"batch": B, "size": S}
+    for nc in (21, 81):
+        g = torch.Generator().manual_seed(7)
+        lab = torch.randint(0, nc, (B, S // 16, S // 16), generator=g).repeat_interleave(16, 1).repeat_interleave(16, 2)
+        lab[:, :8] = 255
+        lab = lab.cuda()
+        seg = torch.randn(B, nc, S // 16, S // 16, generator=g).cuda().requires_grad_(True)
+        for name, fn in (("seg", get_seg_loss_fused), ("ce", get_ce_loss_fused)):
+            out[f"{name}_us_nc{nc}"] = round(_median_ms(lambda: fn(seg, lab, 255).backward(), 4 * steps, warmup) * 1e3, 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--loss-only", action="store_true")
     a = ap.parse_args()
+    if a.loss_only:
+        print(json.dumps(loss_only(a.batch, a.size, a.steps, a.warmup)), flush=True)
+        return
     from oracle import synth
     from weclip_vit_comer_amd.train_step import SupervisedTrainStep
     from weclip_vit_comer_amd.utils.losses import get_ce_loss_fused

@@ -1,23 +1,25 @@
-// Segmentation loss of the training step, fused with the bilinear up-sampling of the logits.
-// reference scripts/dist_clip_voc.py:250 (F.interpolate(segs, size=(H,W), bilinear, align_corners=False))
-// + get_seg_loss :105-113:  0.5 * (CE(pred, label with fg->ignore) + CE(pred, label with bg->ignore)),
-// each CE a mean over its non-ignored pixels.  The reference materialises the (B, nc, H, W) up-sampled
-// logits (352 MB at 16x21x512x512) for log_softmax forward and backward; here every high-res pixel
-// interpolates its nc logits from the low-res map on the fly.
-//   seg_loss_kernel<false>  : per pixel nll; block sums of (nll_bg, n_bg, nll_fg, n_fg) -> partials (forward only)
-//   seg_loss_kernel<true>   : per pixel g[c] = w_pix * (softmax_c - [c == label]) written as (B, nc, H, W);
-//                             the low-res gradient is then the separable bilinear backward (resize.hip).
-//   seg_loss_bwd_y_kernel   : the same gradient formed inside the Y pass (no (B, nc, H, W) tensor), + seg_bwd_x_kernel
-//   seg_loss_fused_kernel   : TRAINING: loss and gradient in one pixel pass (nc <= 24), + seg_count / seg_bwd_x2 kernels
+// Losses of the training steps.
+// Soft-max cross-entropy of the bilinearly up-sampled logits, with its gradient pulled back to the low-resolution map:
+// reference scripts/dist_clip_voc.py:250 (F.interpolate(segs, size=(H,W), bilinear, align_corners=False)) followed by
+//   get_seg_loss :105-113:  0.5 * (CE(pred, label with fg->ignore) + CE(pred, label with bg->ignore)), each CE a mean over
+//                           its non-ignored pixels (the weakly supervised step), or
+//   F.cross_entropy(pred, label, ignore_index)  (the supervised variant's step).
+// The reference materialises the (B, nc, H, W) up-sampled logits (352 MB at 16x21x512x512) for log_softmax forward and
+// backward; here every high-res pixel interpolates its nc logits from the low-res map on the fly.
+//   seg_loss_kernel              : forward only (no gradient requested): per pixel nll, block sums of
+//                                  (nll_bg, n_bg, nll_fg, n_fg) -> seg_loss_reduce_kernel                 wc_seg_loss_fwd
+//   ce_loss_fused_kernel<CH, MULTI, TWO_TERM> : TRAINING: loss and gradient in one pixel pass, 1..128 classes in register
+//                                  chunks of CH, + seg_bwd_x2_kernel (X pass of the separable bilinear backward)
+//       TWO_TERM = true          : get_seg_loss weighting; seg_count_kernel first, seg_loss_reduce_kernel  wc_seg_loss_fwd_bwd
+//       TWO_TERM = false         : plain cross-entropy; ce_loss_reduce_kernel, X pass scaled by 1/N_valid wc_ce_loss_fwd_bwd
+// and the affinity loss fused with the affinity-label construction (aff_loss_kernel, wc_aff_loss_fwd / wc_aff_loss_bwd).
 #include "common.h"
 #include "resample.h"
 
-#define SEG_MAX_C 96
+#define LOSS_MAX_C 128   // class limit of every entry of this file
 
-template <bool BWD>
 __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__ seg, const long* __restrict__ label,
-                                                        float* __restrict__ part, const float* __restrict__ wts,
-                                                        float* __restrict__ ghr, int nc, int h, int w, int H, int W,
+                                                        float* __restrict__ part, int nc, int h, int w, int H, int W,
                                                         float sy, float sx, int ignore) {
     __shared__ float red[16];
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
@@ -41,29 +43,16 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
             sum = sum * __expf(mx - nm) + __expf(z - nm);
             mx = nm;
         }
-        const bool valid = lab != ignore && lab >= 0 && lab < nc;
-        if (valid) {
+        if (lab != ignore && lab >= 0 && lab < nc) {
             cls = lab == 0 ? 0 : 1;
             nll = mx + __logf(sum) - zl;
         }
-        if (BWD) {
-            const float wp = valid ? wts[cls] : 0.f;     // 0.5 / n_bg or 0.5 / n_fg (times upstream grad)
-            float* G = ghr + (long)b * nc * H * W + (long)y * W + x;
-            const float lse = mx + __logf(sum);
-            for (int c = 0; c < nc; ++c) {
-                const float* Sc = S + (long)c * h * w;
-                const float z = w00 * Sc[o00] + w01 * Sc[o01] + w10 * Sc[o10] + w11 * Sc[o11];
-                G[(long)c * H * W] = wp * (__expf(z - lse) - (c == lab ? 1.f : 0.f));
-            }
-        }
     }
-    if (!BWD) {
-        const float a0 = block_sum(cls == 0 ? nll : 0.f, red), a1 = block_sum(cls == 0 ? 1.f : 0.f, red);
-        const float a2 = block_sum(cls == 1 ? nll : 0.f, red), a3 = block_sum(cls == 1 ? 1.f : 0.f, red);
-        if (threadIdx.x == 0) {
-            const long blk = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-            part[blk * 4] = a0; part[blk * 4 + 1] = a1; part[blk * 4 + 2] = a2; part[blk * 4 + 3] = a3;
-        }
+    const float a0 = block_sum(cls == 0 ? nll : 0.f, red), a1 = block_sum(cls == 0 ? 1.f : 0.f, red);
+    const float a2 = block_sum(cls == 1 ? nll : 0.f, red), a3 = block_sum(cls == 1 ? 1.f : 0.f, red);
+    if (threadIdx.x == 0) {
+        const long blk = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        part[blk * 4] = a0; part[blk * 4 + 1] = a1; part[blk * 4 + 2] = a2; part[blk * 4 + 3] = a3;
     }
 }
 
@@ -102,209 +91,35 @@ __global__ __launch_bounds__(1024) void seg_loss_reduce_kernel(const float* __re
 
 extern "C" int wc_seg_loss_fwd(const float* seg, const int64_t* label, float* part, float* sums, int B, int nc, int h,
                                int w, int H, int W, int ignore, void* stream) {
-    WC_CHECK_ARG(seg && label && part && sums && B > 0 && nc > 0 && nc <= SEG_MAX_C && h > 0 && w > 0 && H >= h && W >= w,
+    WC_CHECK_ARG(seg && label && part && sums && B > 0 && nc > 0 && nc <= LOSS_MAX_C && h > 0 && w > 0 && H >= h && W >= w,
                  "wc_seg_loss_fwd: bad argument");
     dim3 grid(wc_cdiv(W, 64), wc_cdiv(H, 4), B);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(seg_loss_kernel<false>, grid, dim3(256), 0, st, seg, (const long*)label, part, nullptr, nullptr, nc,
-                       h, w, H, W, (float)h / H, (float)w / W, ignore);
-    WC_LAUNCH_CHECK("seg_loss_kernel<fwd>");
+    hipLaunchKernelGGL(seg_loss_kernel, grid, dim3(256), 0, st, seg, (const long*)label, part, nc, h, w, H, W, (float)h / H,
+                       (float)w / W, ignore);
+    WC_LAUNCH_CHECK("seg_loss_kernel");
     hipLaunchKernelGGL(seg_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, (long)grid.x * grid.y * grid.z, 0);
     WC_LAUNCH_CHECK("seg_loss_reduce_kernel");
     return WC_OK;
 }
 
-// wts (2) device floats: gradient weight of a background / foreground pixel.  ghr: (B, nc, H, W) workspace.
-extern "C" int wc_seg_loss_bwd(const float* seg, const int64_t* label, const float* wts, float* ghr, int B, int nc, int h,
-                               int w, int H, int W, int ignore, void* stream) {
-    WC_CHECK_ARG(seg && label && wts && ghr && B > 0 && nc > 0 && nc <= SEG_MAX_C && h > 0 && w > 0 && H >= h && W >= w,
-                 "wc_seg_loss_bwd: bad argument");
-    dim3 grid(wc_cdiv(W, 64), wc_cdiv(H, 4), B);
-    hipLaunchKernelGGL(seg_loss_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, seg, (const long*)label, nullptr, wts,
-                       ghr, nc, h, w, H, W, (float)h / H, (float)w / W, ignore);
-    WC_LAUNCH_CHECK("seg_loss_kernel<bwd>");
-    return WC_OK;
-}
-
-
-// Backward of the fused up-sampling + cross-entropy WITHOUT the (B, nc, H, W) high-resolution gradient (352 MB written and
-// read back at 16 x 21 x 512 x 512): bilinear interpolation is separable, so the low-resolution gradient is
-//   tmp[b,c,ys,X] = sum_Y wy(Y -> ys) * g[b,c,Y,X]      (this kernel: g is formed on the fly, per pixel, from the logits)
-//   out[b,c,ys,xs] = sum_X wx(X -> xs) * tmp[b,c,ys,X]  (seg_bwd_x_kernel)
-// A thread owns one high-resolution column X of one low-resolution row ys and walks the ~2/sy rows Y that touch ys in
-// ascending order (fixed summation order: deterministic; for nc > 24 bit-identical to the two-kernel path it replaces, for
-// nc <= 24 the log-sum-exp is formed max-first instead of online: same value to rounding); every pixel's soft-max is
-// evaluated for both low-resolution rows it feeds (2 x the exponentials, none of the HBM traffic).
-template <int NCT>
-__global__ __launch_bounds__(256) void seg_loss_bwd_y_kernel(const float* __restrict__ seg, const long* __restrict__ label,
-                                                              const float* __restrict__ wts, float* __restrict__ tmp, int nc,
-                                                              int h, int w, int H, int W, float sy, float sx, int ignore) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
-    if (x >= W || ys >= h) return;
-    int x0, x1;
-    float lx;
-    wc_bil_src(x, w, sx, x0, x1, lx);
-    const float iy = 1.0f / sy;
-    int y_lo = (int)floorf((ys - 1.5f) * iy) - 1, y_hi = (int)ceilf((ys + 1.5f) * iy) + 1;
-    if (y_lo < 0) y_lo = 0;
-    if (y_hi > H - 1) y_hi = H - 1;
-    float acc[NCT];
-#pragma unroll
-    for (int c = 0; c < NCT; ++c) acc[c] = 0.f;
-    const float* S = seg + (long)b * nc * h * w;
-    const float wbg = wts[0], wfg = wts[1];
-    // CACHE (small class counts): the four low-resolution neighbours of this column for every class live in registers and
-    // are re-read only when the source row pair (y0, y1) changes (every ~1/sy rows): a row then costs FMAs and
-    // exponentials, not 2 x 4 x nc loads
-    constexpr bool CACHE = NCT <= 24;
-    float s00[CACHE ? NCT : 1], s01[CACHE ? NCT : 1], s10[CACHE ? NCT : 1], s11[CACHE ? NCT : 1];
-    int cy0 = -1, cy1 = -1;
-    long labs[8];
-    for (int y = y_lo; y <= y_hi; ++y) {
-        if (((y - y_lo) & 7) == 0) {               // the labels of the next 8 rows in one go: 8 independent loads in flight
-#pragma unroll
-            for (int u = 0; u < 8; ++u) labs[u] = label[((long)b * H + min(y + u, H - 1)) * W + x];
-        }
-        int y0, y1;
-        float ly;
-        wc_bil_src(y, h, sy, y0, y1, ly);
-        const float wy = (y0 == ys ? 1.f - ly : 0.f) + (y1 == ys ? ly : 0.f);       // wave-uniform
-        long lab = labs[0];
-#pragma unroll
-        for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;
-        if (wy == 0.f) continue;
-        const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-        const long o00 = (long)y0 * w + x0, o01 = (long)y0 * w + x1, o10 = (long)y1 * w + x0, o11 = (long)y1 * w + x1;
-        if constexpr (CACHE) {
-            if (y0 != cy0 || y1 != cy1) {          // wave-uniform
-                cy0 = y0; cy1 = y1;
-#pragma unroll
-                for (int c = 0; c < NCT; ++c) {          // (classes past nc re-read class nc - 1: no branch around the loads)
-                    const float* Sc = S + (long)min(c, nc - 1) * h * w;
-                    s00[c] = Sc[o00]; s01[c] = Sc[o01]; s10[c] = Sc[o10]; s11[c] = Sc[o11];
-                }
-            }
-        }
-        float mx = -INFINITY, sum = 0.f;
-        float zc[CACHE ? NCT : 1];
-        if constexpr (CACHE) {
-            // maximum first, then independent exponentials (the online form's max -> rescale -> add chain is serial over
-            // the classes); the interpolated logits stay in registers for the gradient pass
-#pragma unroll
-            for (int c = 0; c < NCT; ++c) {
-                zc[c] = c < nc ? w00 * s00[c] + w01 * s01[c] + w10 * s10[c] + w11 * s11[c] : -INFINITY;
-                mx = fmaxf(mx, zc[c]);
-            }
-#pragma unroll
-            for (int c = 0; c < NCT; ++c) sum += c < nc ? __expf(zc[c] - mx) : 0.f;
-        } else {
-            // (the logits of eight classes are requested together from clamped class indices; a class past nc enters the online
-            //  log-sum-exp as -inf: exp(-inf - max) = 0, the maximum is unchanged -- behind `if (c < nc)` every class's four
-            //  loads were waited for before the next class's were issued: 81 dependent latencies per pixel row at COCO's nc)
-#pragma unroll
-            for (int c0 = 0; c0 < NCT; c0 += 8) {
-                float zz[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = c0 + u;
-                    const float* Sc = S + (long)min(c, nc - 1) * h * w;
-                    zz[u] = w00 * Sc[o00] + w01 * Sc[o01] + w10 * Sc[o10] + w11 * Sc[o11];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    if (c0 + u < nc) {
-                        const float nm = fmaxf(mx, zz[u]);
-                        sum = sum * __expf(mx - nm) + __expf(zz[u] - nm);
-                        mx = nm;
-                    }
-                }
-            }
-        }
-        const bool valid = lab != ignore && lab >= 0 && lab < nc;
-        const float wp = valid ? (lab == 0 ? wbg : wfg) : 0.f;
-        const float lse = mx + __logf(sum);
-        if constexpr (CACHE) {
-#pragma unroll
-            for (int c = 0; c < NCT; ++c) {
-                if (c < nc) {
-                    const float gval = wp * (__expf(zc[c] - lse) - (c == lab ? 1.f : 0.f));
-                    acc[c] = fmaf(wy, gval, acc[c]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int c0 = 0; c0 < NCT; c0 += 8) {
-                float zz[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float* Sc = S + (long)min(c0 + u, nc - 1) * h * w;
-                    zz[u] = w00 * Sc[o00] + w01 * Sc[o01] + w10 * Sc[o10] + w11 * Sc[o11];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = c0 + u;
-                    if (c < nc) {
-                        const float gval = wp * (__expf(zz[u] - lse) - (c == lab ? 1.f : 0.f));
-                        acc[c] = fmaf(wy, gval, acc[c]);
-                    }
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-        if (c < nc) tmp[(((long)b * nc + c) * h + ys) * W + x] = acc[c];
-}
-
-__global__ __launch_bounds__(256) void seg_bwd_x_kernel(const float* __restrict__ tmp, float* __restrict__ gsrc, int Hs, int Ws,
-                                                         int Wd, float sx) {
-    const int xs = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (xs >= Ws || ys >= Hs) return;
-    const float* T = tmp + ((long)blockIdx.z * Hs + ys) * Wd;
-    const float ix = 1.0f / sx;
-    int x_lo = (int)floorf((xs - 1.5f) * ix) - 1, x_hi = (int)ceilf((xs + 1.5f) * ix) + 1;
-    if (x_lo < 0) x_lo = 0;
-    if (x_hi > Wd - 1) x_hi = Wd - 1;
-    float acc = 0.f;
-    for (int x = x_lo; x <= x_hi; ++x) {
-        int x0, x1;
-        float lx;
-        wc_bil_src(x, Ws, sx, x0, x1, lx);
-        const float wx = (x0 == xs ? 1.f - lx : 0.f) + (x1 == xs ? lx : 0.f);
-        acc = fmaf(wx, T[x], acc);
-    }
-    gsrc[((long)blockIdx.z * Hs + ys) * Ws + xs] = acc;
-}
-
-// d loss / d seg (B, nc, h, w) of get_seg_loss(F.interpolate(seg, (H, W)), label) in two launches.
-// wts (2) device floats: gradient weight of a background / foreground pixel.  tmp: workspace B*nc*h*W floats.
-extern "C" int wc_seg_loss_bwd_fused(const float* seg, const int64_t* label, const float* wts, float* tmp, float* out, int B,
-                                     int nc, int h, int w, int H, int W, int ignore, void* stream) {
-    WC_CHECK_ARG(seg && label && wts && tmp && out && B > 0 && B <= 65535 && nc > 0 && nc <= SEG_MAX_C && (long)B * nc <= 65535 &&
-                 h > 0 && w > 0 && H >= h && W >= w, "wc_seg_loss_bwd_fused: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid(wc_cdiv(W, 64), wc_cdiv(h, 4), B);
-    if (nc <= 24)
-        hipLaunchKernelGGL(seg_loss_bwd_y_kernel<24>, grid, dim3(256), 0, st, seg, (const long*)label, wts, tmp, nc, h, w, H, W,
-                           (float)h / H, (float)w / W, ignore);
-    else
-        hipLaunchKernelGGL(seg_loss_bwd_y_kernel<SEG_MAX_C>, grid, dim3(256), 0, st, seg, (const long*)label, wts, tmp, nc, h, w, H,
-                           W, (float)h / H, (float)w / W, ignore);
-    WC_LAUNCH_CHECK("seg_loss_bwd_y_kernel");
-    hipLaunchKernelGGL(seg_bwd_x_kernel, dim3(wc_cdiv(w, 64), wc_cdiv(h, 4), B * nc), dim3(256), 0, st, tmp, out, h, w, W,
-                       (float)w / W);
-    WC_LAUNCH_CHECK("seg_bwd_x_kernel");
-    return WC_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Training form: loss AND its gradient in one pass over the pixels (the soft-max of a pixel is formed once; the
-// separate forward + gradient passes formed it three times: once for the loss and once for each of the two low-resolution
-// rows a pixel contributes to).  The gradient needs the class weights 0.5 / n_bg, 0.5 / n_fg before the pass: a label
-// count runs first (SEG_CNT_BLOCKS block partials, summed in a fixed order by every workgroup of the main pass).
+// Training form: loss AND its gradient in one pass over the pixels (the soft-max of a pixel is formed once; separate
+// forward + gradient passes form it three times: once for the loss and once for each of the two low-resolution rows a
+// pixel contributes to), without the (B, nc, H, W) high-resolution gradient: bilinear interpolation is separable.
 // Thread (x, ys): the pixels of column x whose upper source row is ys.  Their logits are a_c + ly * (b_c - a_c) with
 // a_c, b_c = the x-interpolated logits of rows ys, ys + 1 (registers); their gradient goes to row ys with weight 1 - ly
-// (tmpA) and to row ys + 1 with ly (tmpB); the X pass adds the two in a fixed order.
+// (tmpA) and to row ys + 1 with ly (tmpB); the X pass adds the two in a fixed order.  H and W are free (down-sampling too:
+// a thread with no rows writes zeros).  Up to LOSS_MAX_C classes in chunks of CH per workgroup (blockIdx.z = image * nchunk
+// + chunk).  MULTI (nc > CH): the pixel's log-sum-exp runs over all classes from memory, CE_LSE_G classes' loads at a time;
+// the chunk's own logits stay in registers for the gradient.  Only chunk 0 contributes to the block partials.
+// A label outside [0, nc) that is not `ignore` is treated as ignored; it is compared, never used as an index.
+//   TWO_TERM = false (F.cross_entropy): every valid pixel weighs 1 (the 1 / N_valid is applied by the X pass from a device
+//     scalar, so no count pass runs first).  Block partials: (sum nll, n_valid, n_bad, 0), n_bad = the out-of-range labels.
+//   TWO_TERM = true (get_seg_loss): a valid pixel weighs 0.5 / n_bg or 0.5 / n_fg by its label.  The gradient needs these
+//     before the pass: a label count runs first (SEG_CNT_BLOCKS block partials, summed in a fixed order by every workgroup
+//     of the main pass).  Block partials: (nll_bg, n_bg, nll_fg, n_fg), as seg_loss_kernel's.
+#define SEG_CNT_BLOCKS 1024
 #define SEG_CNT_BLOCKS 1024
 __global__ __launch_bounds__(256) void seg_count_kernel(const long* __restrict__ label, float* __restrict__ cnt, long n, int nc,
                                                          int ignore) {
@@ -320,35 +135,43 @@ __global__ __launch_bounds__(256) void seg_count_kernel(const long* __restrict__
     if (threadIdx.x == 0) { cnt[2 * blockIdx.x] = a; cnt[2 * blockIdx.x + 1] = b; }
 }
 
-template <int NCT>
-__global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __restrict__ seg, const long* __restrict__ label,
-                                                              const float* __restrict__ cnt, float* __restrict__ part,
-                                                              float* __restrict__ tmpA, float* __restrict__ tmpB, int nc, int h,
-                                                              int w, int H, int W, float sy, float sx, int ignore) {
+#define CE_LSE_G 4       // classes whose logits the MULTI log-sum-exp requests together (8: the register file overflows, loads serialise)
+template <int CH, bool MULTI, bool TWO_TERM>
+__global__ __launch_bounds__(256) void ce_loss_fused_kernel(const float* __restrict__ seg, const long* __restrict__ label,
+                                                             const float* __restrict__ cnt, float* __restrict__ part,
+                                                             float* __restrict__ tmpA, float* __restrict__ tmpB, int nc,
+                                                             int nchunk, int h, int w, int H, int W, float sy, float sx,
+                                                             int ignore) {
     __shared__ float red[16];
-    float pb = 0.f, pf = 0.f;
-    for (int i = threadIdx.x; i < SEG_CNT_BLOCKS; i += 256) { pb += cnt[2 * i]; pf += cnt[2 * i + 1]; }
-    const float nbg = block_sum(pb, red), nfg = block_sum(pf, red);
-    const float wbg = nbg > 0.f ? 0.5f / nbg : 0.f, wfg = nfg > 0.f ? 0.5f / nfg : 0.f;
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6), b = blockIdx.z;
-    float l_bg = 0.f, c_bg = 0.f, l_fg = 0.f, c_fg = 0.f;
+    float wbg = 1.f, wfg = 1.f;
+    if constexpr (TWO_TERM) {
+        float pb = 0.f, pf = 0.f;
+        for (int i = threadIdx.x; i < SEG_CNT_BLOCKS; i += 256) { pb += cnt[2 * i]; pf += cnt[2 * i + 1]; }
+        const float nbg = block_sum(pb, red), nfg = block_sum(pf, red);
+        wbg = nbg > 0.f ? 0.5f / nbg : 0.f;
+        wfg = nfg > 0.f ? 0.5f / nfg : 0.f;
+    }
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int b = blockIdx.z / nchunk, ck = blockIdx.z - b * nchunk, c0 = ck * CH;
+    float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;     // this thread's share of the block partials
     if (x < W && ys < h) {
         int x0, x1;
         float lx;
         wc_bil_src(x, w, sx, x0, x1, lx);
         const int y1s = ys + (ys < h - 1 ? 1 : 0);
         const float* S = seg + (long)b * nc * h * w;
-        float av[NCT], dv[NCT], accT[NCT], accB[NCT];
+        const long r0 = (long)ys * w, r1 = (long)y1s * w;
+        float av[CH], dv[CH], accT[CH], accB[CH];
 #pragma unroll
-        for (int c = 0; c < NCT; ++c) {
+        for (int c = 0; c < CH; ++c) {
             accT[c] = accB[c] = 0.f;
-            // (classes past nc read class nc - 1 and are masked: behind an `if (c < nc)` hipcc waited for the four loads of a
-            //  class before issuing the next class's -- 24 dependent latencies at the head of every thread)
-            const float* Sc = S + (long)min(c, nc - 1) * h * w;
-            const float a = (1.f - lx) * Sc[ys * w + x0] + lx * Sc[ys * w + x1];
-            const float bb = (1.f - lx) * Sc[y1s * w + x0] + lx * Sc[y1s * w + x1];
-            av[c] = c < nc ? a : 0.f;
-            dv[c] = c < nc ? bb - a : 0.f;
+            // clamped class: no branch around the loads (behind an `if (c < nc)` hipcc waited for the four loads of a class
+            // before issuing the next class's -- CH dependent latencies at the head of every thread)
+            const float* Sc = S + (long)min(c0 + c, nc - 1) * h * w;
+            const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
+            const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
+            av[c] = a;
+            dv[c] = bb - a;
         }
         const float iy = 1.0f / sy;
         int y_lo = ys == 0 ? 0 : (int)floorf((ys + 0.5f) * iy - 0.5f) - 1;
@@ -368,37 +191,72 @@ __global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __rest
 #pragma unroll
             for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;
             if (y0 != ys) continue;                      // wave-uniform
-            float zc[NCT];
-            float mx = -INFINITY, zl = 0.f;
+            float zc[CH];
+            float mx = -INFINITY, sum = 0.f, zl = 0.f;
 #pragma unroll
-            for (int c = 0; c < NCT; ++c) {
-                zc[c] = c < nc ? fmaf(ly, dv[c], av[c]) : -INFINITY;
-                mx = fmaxf(mx, zc[c]);
-                zl = c == lab ? zc[c] : zl;
+            for (int c = 0; c < CH; ++c) zc[c] = c0 + c < nc ? fmaf(ly, dv[c], av[c]) : -INFINITY;
+            if constexpr (!MULTI) {
+                // maximum first, then independent exponentials (an online form's max -> rescale -> add chain is serial over
+                // the classes)
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    mx = fmaxf(mx, zc[c]);
+                    zl = c == lab ? zc[c] : zl;
+                }
+            } else {
+                // online log-sum-exp over all nc classes, CE_LSE_G at a time (loads from clamped class indices, issued together)
+                for (int cb = 0; cb < nc; cb += CE_LSE_G) {
+                    float zz[CE_LSE_G];
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) {
+                        const float* Sc = S + (long)min(cb + u, nc - 1) * h * w;
+                        const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
+                        const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
+                        zz[u] = cb + u < nc ? fmaf(ly, bb - a, a) : -INFINITY;
+                    }
+                    float m8 = mx;
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) {
+                        m8 = fmaxf(m8, zz[u]);
+                        zl = cb + u == lab ? zz[u] : zl;
+                    }
+                    float s8 = 0.f;
+#pragma unroll
+                    for (int u = 0; u < CE_LSE_G; ++u) s8 += __expf(zz[u] - m8);
+                    sum = sum * __expf(mx - m8) + s8;
+                    mx = m8;
+                }
             }
-            float sum = 0.f;
 #pragma unroll
-            for (int c = 0; c < NCT; ++c) {
-                zc[c] = c < nc ? __expf(zc[c] - mx) : 0.f;
-                sum += zc[c];
+            for (int c = 0; c < CH; ++c) {
+                zc[c] = __expf(zc[c] - mx);                // class past nc: exp(-inf) = 0
+                if constexpr (!MULTI) sum += zc[c];
             }
             const bool valid = lab != ignore && lab >= 0 && lab < nc;
-            const float nll = mx + __logf(sum) - zl;
-            if (valid && lab == 0) { l_bg += nll; c_bg += 1.f; }
-            if (valid && lab != 0) { l_fg += nll; c_fg += 1.f; }
-            const float wp = valid ? (lab == 0 ? wbg : wfg) : 0.f;
+            if (ck == 0) {
+                const float nll = mx + __logf(sum) - zl;
+                if constexpr (TWO_TERM) {
+                    if (valid && lab == 0) { p0 += nll; p1 += 1.f; }
+                    if (valid && lab != 0) { p2 += nll; p3 += 1.f; }
+                } else {
+                    p0 += valid ? nll : 0.f;
+                    p1 += valid ? 1.f : 0.f;
+                    p2 += (!valid && lab != ignore) ? 1.f : 0.f;
+                }
+            }
+            const float wp = valid ? (TWO_TERM ? (lab == 0 ? wbg : wfg) : 1.f) : 0.f;
             const float u = wp / sum;
 #pragma unroll
-            for (int c = 0; c < NCT; ++c) {
-                const float gval = fmaf(u, zc[c], c == lab ? -wp : 0.f);       // wp * (softmax_c - [c == label])
+            for (int c = 0; c < CH; ++c) {
+                const float gval = fmaf(u, zc[c], c0 + c == lab ? -wp : 0.f);   // wp * (softmax_c - [c == label])
                 accT[c] += gval;
                 accB[c] = fmaf(ly, gval, accB[c]);
             }
         }
 #pragma unroll
-        for (int c = 0; c < NCT; ++c)
-            if (c < nc) {
-                const long o = (((long)b * nc + c) * h) * W + x;
+        for (int c = 0; c < CH; ++c)
+            if (c0 + c < nc) {
+                const long o = (((long)b * nc + c0 + c) * h) * W + x;
                 if (y1s == ys) tmpA[o + (long)ys * W] = accT[c];               // last row: both weights land on it
                 else {
                     tmpA[o + (long)ys * W] = accT[c] - accB[c];
@@ -406,10 +264,11 @@ __global__ __launch_bounds__(256) void seg_loss_fused_kernel(const float* __rest
                 }
             }
     }
-    const float a0 = block_sum(l_bg, red), a1 = block_sum(c_bg, red), a2 = block_sum(l_fg, red), a3 = block_sum(c_fg, red);
+    const float a0 = block_sum(p0, red), a1 = block_sum(p1, red), a2 = block_sum(p2, red);
+    const float a3 = TWO_TERM ? block_sum(p3, red) : 0.f;
     if (threadIdx.x == 0) {
         const long blk = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        part[blk * 4] = a0; part[blk * 4 + 1] = a1; part[blk * 4 + 2] = a2; part[blk * 4 + 3] = a3;
+        *reinterpret_cast<float4*>(part + blk * 4) = make_float4(a0, a1, a2, a3);
     }
 }
 
@@ -452,160 +311,6 @@ __global__ __launch_bounds__(256) void seg_bwd_x2_kernel(const float* __restrict
     }
 }
 
-// Loss (sums, as wc_seg_loss_fwd) and d loss / d seg for an upstream gradient of 1 (grad, (B,nc,h,w)) in one pixel pass.
-// cnt: 2 * 1024 floats, part: 4 floats per 64 x 4 block of (W, h) per image, tmp: 2 * B*nc*h*W floats.  nc <= 24.
-extern "C" int wc_seg_loss_fwd_bwd(const float* seg, const int64_t* label, float* cnt, float* part, float* sums, float* tmp,
-                                   float* grad, int B, int nc, int h, int w, int H, int W, int ignore, void* stream) {
-    WC_CHECK_ARG(seg && label && cnt && part && sums && tmp && grad && B > 0 && B <= 65535 && nc > 0 && nc <= 24 &&
-                 (long)B * nc <= 65535 && h > 0 && w > 0 && H >= h && W >= w, "wc_seg_loss_fwd_bwd: bad argument (nc <= 24)");
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(seg_count_kernel, dim3(SEG_CNT_BLOCKS), dim3(256), 0, st, (const long*)label, cnt, (long)B * H * W, nc, ignore);
-    WC_LAUNCH_CHECK("seg_count_kernel");
-    dim3 grid(wc_cdiv(W, 64), wc_cdiv(h, 4), B);
-    float* tmpB = tmp + (long)B * nc * h * W;
-    hipLaunchKernelGGL(seg_loss_fused_kernel<24>, grid, dim3(256), 0, st, seg, (const long*)label, cnt, part, tmp, tmpB, nc, h, w, H,
-                       W, (float)h / H, (float)w / W, ignore);
-    WC_LAUNCH_CHECK("seg_loss_fused_kernel");
-    hipLaunchKernelGGL(seg_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, (long)grid.x * grid.y * grid.z, 0);
-    WC_LAUNCH_CHECK("seg_loss_reduce_kernel");
-    const long rows = (long)B * nc * h;
-    WC_CHECK_ARG(W <= 8192, "wc_seg_loss_fwd_bwd: W too large for the row buffer");
-    hipLaunchKernelGGL(seg_bwd_x2_kernel<false>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
-                       st, tmp, tmpB, grad, rows, h, w, W, (float)w / W, nullptr);
-    WC_LAUNCH_CHECK("seg_bwd_x2_kernel");
-    return WC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Plain cross-entropy with an ignore index, fused with the bilinear up-sampling of the logits (the supervised WeCLIP
-// variant's loss, WeCLIP_model/model_attn_aff_voc_seg.py in this package):
-//   loss = mean over pixels with label != ignore of  -log softmax(F.interpolate(seg, (H, W), bilinear, align_corners=False))[label]
-// = F.cross_entropy(F.interpolate(...), label, ignore_index=ignore).  Same pixel pass as seg_loss_fused_kernel (thread (x, ys)
-// walks the high-resolution rows whose upper source row is ys; gradient split over rows ys / ys + 1 into tmpA / tmpB), with
-// three differences: every valid pixel weighs 1 (the 1 / N_valid is applied by the X pass from a device scalar, so no count
-// pass runs first), H and W are free (down-sampling too: a thread with no rows writes zeros), and up to CE_MAX_C classes in
-// chunks of CH per workgroup (blockIdx.z = image * nchunk + chunk).  MULTI (nc > CH): the pixel's log-sum-exp runs over all
-// classes from memory, CE_LSE_G classes' loads at a time; the chunk's own logits stay in registers for the gradient.
-// A label outside [0, nc) that is not `ignore` is treated as ignored and counted (part[.. + 2]); it is compared, never used
-// as an index.  Block partials: (sum nll, n_valid, n_bad, 0) -- only chunk 0 counts.
-#define CE_MAX_C 128
-#define CE_LSE_G 4       // classes whose logits the MULTI log-sum-exp requests together (8: the register file overflows, loads serialise)
-template <int CH, bool MULTI>
-__global__ __launch_bounds__(256) void ce_loss_fused_kernel(const float* __restrict__ seg, const long* __restrict__ label,
-                                                             float* __restrict__ part, float* __restrict__ tmpA,
-                                                             float* __restrict__ tmpB, int nc, int nchunk, int h, int w, int H,
-                                                             int W, float sy, float sx, int ignore) {
-    __shared__ float red[16];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), ys = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int b = blockIdx.z / nchunk, ck = blockIdx.z - b * nchunk, c0 = ck * CH;
-    float l_sum = 0.f, n_ok = 0.f, n_bad = 0.f;
-    if (x < W && ys < h) {
-        int x0, x1;
-        float lx;
-        wc_bil_src(x, w, sx, x0, x1, lx);
-        const int y1s = ys + (ys < h - 1 ? 1 : 0);
-        const float* S = seg + (long)b * nc * h * w;
-        const long r0 = (long)ys * w, r1 = (long)y1s * w;
-        float av[CH], dv[CH], accT[CH], accB[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            accT[c] = accB[c] = 0.f;
-            const float* Sc = S + (long)min(c0 + c, nc - 1) * h * w;        // clamped class: no branch around the loads
-            const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
-            const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
-            av[c] = a;
-            dv[c] = bb - a;
-        }
-        const float iy = 1.0f / sy;
-        int y_lo = ys == 0 ? 0 : (int)floorf((ys + 0.5f) * iy - 0.5f) - 1;
-        int y_hi = ys == h - 1 ? H - 1 : (int)ceilf((ys + 1.5f) * iy - 0.5f) + 1;
-        if (y_lo < 0) y_lo = 0;
-        if (y_hi > H - 1) y_hi = H - 1;
-        long labs[8];
-        for (int y = y_lo; y <= y_hi; ++y) {
-            if (((y - y_lo) & 7) == 0) {               // the labels of the next 8 rows: 8 independent loads in flight
-#pragma unroll
-                for (int u = 0; u < 8; ++u) labs[u] = label[((long)b * H + min(y + u, H - 1)) * W + x];
-            }
-            int y0, y1;
-            float ly;
-            wc_bil_src(y, h, sy, y0, y1, ly);
-            long lab = labs[0];
-#pragma unroll
-            for (int u = 1; u < 8; ++u) lab = ((y - y_lo) & 7) == u ? labs[u] : lab;
-            if (y0 != ys) continue;                      // wave-uniform
-            float zc[CH];
-            float mx = -INFINITY, sum = 0.f, zl = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) zc[c] = c0 + c < nc ? fmaf(ly, dv[c], av[c]) : -INFINITY;
-            if constexpr (!MULTI) {
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    mx = fmaxf(mx, zc[c]);
-                    zl = c == lab ? zc[c] : zl;
-                }
-            } else {
-                // online log-sum-exp over all nc classes, CE_LSE_G at a time (loads from clamped class indices, issued together)
-                for (int cb = 0; cb < nc; cb += CE_LSE_G) {
-                    float zz[CE_LSE_G];
-#pragma unroll
-                    for (int u = 0; u < CE_LSE_G; ++u) {
-                        const float* Sc = S + (long)min(cb + u, nc - 1) * h * w;
-                        const float a = (1.f - lx) * Sc[r0 + x0] + lx * Sc[r0 + x1];
-                        const float bb = (1.f - lx) * Sc[r1 + x0] + lx * Sc[r1 + x1];
-                        zz[u] = cb + u < nc ? fmaf(ly, bb - a, a) : -INFINITY;
-                    }
-                    float m8 = mx;
-#pragma unroll
-                    for (int u = 0; u < CE_LSE_G; ++u) {
-                        m8 = fmaxf(m8, zz[u]);
-                        zl = cb + u == lab ? zz[u] : zl;
-                    }
-                    float s8 = 0.f;
-#pragma unroll
-                    for (int u = 0; u < CE_LSE_G; ++u) s8 += __expf(zz[u] - m8);
-                    sum = sum * __expf(mx - m8) + s8;
-                    mx = m8;
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                zc[c] = __expf(zc[c] - mx);                // class past nc: exp(-inf) = 0
-                if constexpr (!MULTI) sum += zc[c];
-            }
-            const bool valid = lab != ignore && lab >= 0 && lab < nc;
-            if (ck == 0) {
-                l_sum += valid ? mx + __logf(sum) - zl : 0.f;
-                n_ok += valid ? 1.f : 0.f;
-                n_bad += (!valid && lab != ignore) ? 1.f : 0.f;
-            }
-            const float wp = valid ? 1.f : 0.f;
-            const float u = wp / sum;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                const float gval = fmaf(u, zc[c], c0 + c == lab ? -wp : 0.f);   // [valid] * (softmax_c - [c == label])
-                accT[c] += gval;
-                accB[c] = fmaf(ly, gval, accB[c]);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-            if (c0 + c < nc) {
-                const long o = (((long)b * nc + c0 + c) * h) * W + x;
-                if (y1s == ys) tmpA[o + (long)ys * W] = accT[c];               // last row: both weights land on it
-                else {
-                    tmpA[o + (long)ys * W] = accT[c] - accB[c];
-                    tmpB[o + (long)y1s * W] = accB[c];
-                }
-            }
-    }
-    const float a0 = block_sum(l_sum, red), a1 = block_sum(n_ok, red), a2 = block_sum(n_bad, red);
-    if (threadIdx.x == 0) {
-        const long blk = ((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        *reinterpret_cast<float4*>(part + blk * 4) = make_float4(a0, a1, a2, 0.f);
-    }
-}
-
 // sums = [loss = s0 / s1 (NaN when no pixel is valid, as F.cross_entropy), 1 / s1 (0 when s1 == 0: the gradient is then 0,
 // as torch's), n_valid, n_bad]: block partials in a fixed order, accumulated in double.
 __global__ __launch_bounds__(1024) void ce_loss_reduce_kernel(const float* __restrict__ part, float* __restrict__ sums, long nblk) {
@@ -634,36 +339,56 @@ __global__ __launch_bounds__(1024) void ce_loss_reduce_kernel(const float* __res
     }
 }
 
-extern "C" int wc_ce_loss_fwd_bwd(const float* seg, const int64_t* label, float* part, float* sums, float* tmp, float* grad, int B,
-                                  int nc, int h, int w, int H, int W, int ignore, void* stream) {
-    WC_CHECK_ARG(seg && label && part && sums && tmp && grad, "wc_ce_loss_fwd_bwd: null pointer");
-    WC_CHECK_ARG(B > 0 && nc >= 1 && nc <= CE_MAX_C && h > 0 && w > 0 && H > 0 && W > 0 && W <= 8192,
-                 "wc_ce_loss_fwd_bwd: bad size (1 <= nc <= 128, W <= 8192)");
+// Both training entries: [label count,] pixel pass, one-block reduce, X pass.
+template <bool TWO_TERM>
+static int up_ce_fwd_bwd(const char* who, const float* seg, const int64_t* label, float* cnt, float* part, float* sums,
+                         float* tmp, float* grad, int B, int nc, int h, int w, int H, int W, int ignore, void* stream) {
+    WC_CHECK_ARG(seg && label && (cnt || !TWO_TERM) && part && sums && tmp && grad, "%s: null pointer", who);
+    WC_CHECK_ARG(B > 0 && nc >= 1 && nc <= LOSS_MAX_C && h > 0 && w > 0 && H > 0 && W > 0 && W <= 8192,
+                 "%s: bad size (1 <= nc <= 128, W <= 8192)", who);
     const int nchunk = nc <= 32 ? 1 : (nc + 31) / 32;
-    WC_CHECK_ARG((long)B * nchunk <= 65535 && (long)B * nc * h * W < (1L << 40), "wc_ce_loss_fwd_bwd: batch too large");
-    WC_CHECK_ARG((uintptr_t)part % 16 == 0 && ((uintptr_t)seg | (uintptr_t)sums | (uintptr_t)tmp | (uintptr_t)grad) % 4 == 0 &&
-                 (uintptr_t)label % 8 == 0, "wc_ce_loss_fwd_bwd: misaligned pointer");
+    WC_CHECK_ARG((long)B * nchunk <= 65535 && (long)B * nc * h * W < (1L << 40), "%s: batch too large", who);
+    WC_CHECK_ARG((uintptr_t)part % 16 == 0 && ((uintptr_t)seg | (uintptr_t)cnt | (uintptr_t)sums | (uintptr_t)tmp | (uintptr_t)grad) % 4 == 0 &&
+                 (uintptr_t)label % 8 == 0, "%s: misaligned pointer", who);
     hipStream_t st = (hipStream_t)stream;
+    if (TWO_TERM) {
+        hipLaunchKernelGGL(seg_count_kernel, dim3(SEG_CNT_BLOCKS), dim3(256), 0, st, (const long*)label, cnt, (long)B * H * W, nc,
+                           ignore);
+        WC_LAUNCH_CHECK("seg_count_kernel");
+    }
     dim3 grid(wc_cdiv(W, 64), wc_cdiv(h, 4), B * nchunk);
     float* tmpB = tmp + (long)B * nc * h * W;
     const float sy = (float)h / H, sx = (float)w / W;
-    if (nc <= 24)
-        hipLaunchKernelGGL((ce_loss_fused_kernel<24, false>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
-                           nchunk, h, w, H, W, sy, sx, ignore);
-    else if (nc <= 32)
-        hipLaunchKernelGGL((ce_loss_fused_kernel<32, false>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
-                           nchunk, h, w, H, W, sy, sx, ignore);
-    else
-        hipLaunchKernelGGL((ce_loss_fused_kernel<32, true>), grid, dim3(256), 0, st, seg, (const long*)label, part, tmp, tmpB, nc,
-                           nchunk, h, w, H, W, sy, sx, ignore);
+    const auto pass = nc <= 24 ? ce_loss_fused_kernel<24, false, TWO_TERM>
+                    : nc <= 32 ? ce_loss_fused_kernel<32, false, TWO_TERM> : ce_loss_fused_kernel<32, true, TWO_TERM>;
+    hipLaunchKernelGGL(pass, grid, dim3(256), 0, st, seg, (const long*)label, cnt, part, tmp, tmpB, nc, nchunk, h, w, H, W, sy, sx,
+                       ignore);
     WC_LAUNCH_CHECK("ce_loss_fused_kernel");
-    hipLaunchKernelGGL(ce_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, (long)grid.x * grid.y * grid.z);
-    WC_LAUNCH_CHECK("ce_loss_reduce_kernel");
+    const long nblk = (long)grid.x * grid.y * grid.z;
+    if (TWO_TERM) hipLaunchKernelGGL(seg_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, nblk, 0);
+    else hipLaunchKernelGGL(ce_loss_reduce_kernel, dim3(1), dim3(1024), 0, st, part, sums, nblk);
+    WC_LAUNCH_CHECK("loss reduce kernel");
     const long rows = (long)B * nc * h;
-    hipLaunchKernelGGL(seg_bwd_x2_kernel<true>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
-                       st, tmp, tmpB, grad, rows, h, w, W, sx, sums + 1);
-    WC_LAUNCH_CHECK("seg_bwd_x2_kernel<scaled>");
+    // two-term: the pixel weights are final before the pass; cross-entropy: 1 / N_valid = sums[1] after it
+    hipLaunchKernelGGL(seg_bwd_x2_kernel<!TWO_TERM>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
+                       st, tmp, tmpB, grad, rows, h, w, W, sx, TWO_TERM ? nullptr : sums + 1);
+    WC_LAUNCH_CHECK("seg_bwd_x2_kernel");
     return WC_OK;
+}
+
+// get_seg_loss: sums (8) as wc_seg_loss_fwd and d loss / d seg for an upstream gradient of 1 (grad, (B,nc,h,w)).
+// cnt: 2 * SEG_CNT_BLOCKS floats; part, tmp: as wc_ce_loss_fwd_bwd.
+extern "C" int wc_seg_loss_fwd_bwd(const float* seg, const int64_t* label, float* cnt, float* part, float* sums, float* tmp,
+                                   float* grad, int B, int nc, int h, int w, int H, int W, int ignore, void* stream) {
+    return up_ce_fwd_bwd<true>("wc_seg_loss_fwd_bwd", seg, label, cnt, part, sums, tmp, grad, B, nc, h, w, H, W, ignore, stream);
+}
+
+// F.cross_entropy(F.interpolate(seg, (H, W), bilinear, align_corners=False), label, ignore_index=ignore), the supervised
+// WeCLIP variant's loss (WeCLIP_model/model_attn_aff_voc_seg.py in this package): sums (4) from ce_loss_reduce_kernel.
+// part: 4 floats per workgroup of the pixel pass; tmp: 2 * B*nc*h*W floats.
+extern "C" int wc_ce_loss_fwd_bwd(const float* seg, const int64_t* label, float* part, float* sums, float* tmp, float* grad, int B,
+                                  int nc, int h, int w, int H, int W, int ignore, void* stream) {
+    return up_ce_fwd_bwd<false>("wc_ce_loss_fwd_bwd", seg, label, nullptr, part, sums, tmp, grad, B, nc, h, w, H, W, ignore, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -24,58 +24,56 @@ def get_seg_loss(pred, label, ignore_index=255):
                   + F.cross_entropy(pred, fg.long(), ignore_index=ignore_index))
 
 
-class _SegLossFn(torch.autograd.Function):
-    """get_seg_loss(F.interpolate(seg, (H,W), bilinear), label) without materialising the up-sampled
-    logits (csrc/losses.hip); backward = per-pixel softmax gradient + separable bilinear backward."""
+def _one_pass(entry, seg, label, ignore_index, n_sums):
+    """The training form of csrc/losses.hip (`entry` = wc_seg_loss_fwd_bwd or wc_ce_loss_fwd_bwd): the loss sums and the
+    gradient for an upstream gradient of 1 from one pass over the pixels -- the soft-max of a pixel is formed once, the
+    up-sampled logits are never materialised, and there is no host synchronisation (the whole training step can be
+    captured in a graph).  Returns (sums, grad)."""
+    from .. import _lib as L
+    B, nc, h, w = seg.shape
+    H, W = label.shape[1:]
+    nchunk = 1 if nc <= 32 else (nc + 31) // 32                    # classes go through the kernel in register chunks of 32
+    nblk = ((W + 63) // 64) * ((h + 3) // 4) * B * nchunk
+    part, sums, tmp = (torch.empty(n, device=seg.device, dtype=torch.float32) for n in (4 * nblk, n_sums, 2 * B * nc * h * W))
+    grad = torch.empty_like(seg)
+    # the two-term loss counts its background / foreground labels first: 2 x 1024 block partials
+    cnt = [torch.empty(2048, device=seg.device, dtype=torch.float32)] if entry == "wc_seg_loss_fwd_bwd" else []
+    getattr(L.lib(), entry)(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"),
+                            *[L.ptr(t) for t in cnt + [part, sums, tmp, grad]], B, nc, h, w, H, W, int(ignore_index), L.stream())
+    return sums, grad
+
+
+class _OnePassLossFn(torch.autograd.Function):
+    """A loss whose forward saved its gradient for an upstream gradient of 1 (`_one_pass`): backward only scales it."""
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class _SegLossFn(_OnePassLossFn):
+    """get_seg_loss(F.interpolate(seg, (H,W), bilinear), label) without materialising the up-sampled logits
+    (csrc/losses.hip): wc_seg_loss_fwd_bwd when a gradient is requested, else the forward-only wc_seg_loss_fwd."""
 
     @staticmethod
     def forward(ctx, seg, label, ignore_index):
         from .. import _lib as L
         seg = seg.float().contiguous()
         label = label.long().contiguous()
-        B, nc, h, w = seg.shape
-        H, W = label.shape[1:]
-        sums = torch.empty(8, device=seg.device, dtype=torch.float32)
-        ctx.ignore = int(ignore_index)
-        ctx.one_pass = bool(ctx.needs_input_grad[0]) and nc <= 24
-        if ctx.one_pass:
-            # training: loss and gradient (for an upstream gradient of 1) in one pass over the pixels -- the soft-max of a
-            # pixel is formed once instead of three times (csrc/losses.hip seg_loss_fused_kernel)
-            nblk = ((W + 63) // 64) * ((h + 3) // 4) * B
-            part = torch.empty(nblk * 4, device=seg.device, dtype=torch.float32)
-            cnt = torch.empty(2048, device=seg.device, dtype=torch.float32)
-            tmp = torch.empty(2 * B * nc * h * W, device=seg.device, dtype=torch.float32)
-            grad = torch.empty_like(seg)
-            L.lib().wc_seg_loss_fwd_bwd(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(cnt),
-                                        L.ptr(part), L.ptr(sums), L.ptr(tmp), L.ptr(grad), B, nc, h, w, H, W, ctx.ignore,
-                                        L.stream())
+        if ctx.needs_input_grad[0]:
+            sums, grad = _one_pass("wc_seg_loss_fwd_bwd", seg, label, ignore_index, 8)
             ctx.save_for_backward(grad)
             return sums[4].clone()
-        nblk = ((W + 63) // 64) * ((H + 3) // 4) * B
-        part = torch.empty(nblk * 4, device=seg.device, dtype=torch.float32)
-        L.lib().wc_seg_loss_fwd(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(part),
-                                L.ptr(sums), B, nc, h, w, H, W, ctx.ignore, L.stream())
-        ctx.save_for_backward(seg, label, sums)
-        # mean over an empty set is NaN in F.cross_entropy too (0/0); the scalar tail is computed by the reduce kernel
-        return sums[4].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        from .. import _lib as L
-        if ctx.one_pass:
-            (grad,) = ctx.saved_tensors
-            return grad * g, None, None
-        seg, label, sums = ctx.saved_tensors
         B, nc, h, w = seg.shape
         H, W = label.shape[1:]
-        wts = sums[5:7] * g            # (0.5 / n_bg, 0.5 / n_fg) from the forward reduce kernel: no host sync
-        out = torch.empty_like(seg)
-        # soft-max gradient formed inside the Y pass of the separable bilinear backward: the (B, nc, H, W) gradient
-        # (352 MB at 16 x 21 x 512 x 512) is never written (csrc/losses.hip seg_loss_bwd_y_kernel)
-        tmp = torch.empty(B * nc * h * W, device=seg.device, dtype=torch.float32)
-        L.lib().wc_seg_loss_bwd_fused(L.ptr(seg), L.ptr(label), L.ptr(wts, torch.float32, "wts"), L.ptr(tmp), L.ptr(out), B, nc,
-                                      h, w, H, W, ctx.ignore, L.stream())
-        return out, None, None
+        nblk = ((W + 63) // 64) * ((H + 3) // 4) * B
+        part = torch.empty(nblk * 4, device=seg.device, dtype=torch.float32)
+        sums = torch.empty(8, device=seg.device, dtype=torch.float32)
+        L.lib().wc_seg_loss_fwd(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(part),
+                                L.ptr(sums), B, nc, h, w, H, W, int(ignore_index), L.stream())
+        # mean over an empty set is NaN in F.cross_entropy too (0/0); the scalar tail is computed by the reduce kernel
+        return sums[4].clone()
 
 
 def get_seg_loss_fused(seg_lowres, label, ignore_index=255):
@@ -105,35 +103,17 @@ def _ce_check(seg, label):
         raise ValueError(f"get_ce_loss_fused: seg on {seg.device}, label on {label.device}")
 
 
-class _CELossFn(torch.autograd.Function):
+class _CELossFn(_OnePassLossFn):
     """F.cross_entropy(F.interpolate(seg, label.shape[1:], 'bilinear', align_corners=False), label, ignore_index) without
-    materialising the up-sampled logits (csrc/losses.hip wc_ce_loss_fwd_bwd): loss and the gradient for an upstream
-    gradient of 1 come out of one pixel pass; backward only scales the saved gradient (no host synchronisation, so the
-    whole training step can be captured in a graph).  `ctx.sums` keeps [loss, 1/N_valid, N_valid, N_bad] on the device."""
+    materialising the up-sampled logits (csrc/losses.hip wc_ce_loss_fwd_bwd).  `last_sums` keeps
+    [loss, 1/N_valid, N_valid, N_bad] of the last call on the device."""
 
     @staticmethod
     def forward(ctx, seg, label, ignore_index):
-        from .. import _lib as L
-        seg = seg.float().contiguous()
-        label = label.long().contiguous()
-        B, nc, h, w = seg.shape
-        H, W = label.shape[1:]
-        nchunk = 1 if nc <= 32 else (nc + 31) // 32
-        nblk = ((W + 63) // 64) * ((h + 3) // 4) * B * nchunk
-        part = torch.empty(nblk * 4, device=seg.device, dtype=torch.float32)
-        sums = torch.empty(4, device=seg.device, dtype=torch.float32)
-        tmp = torch.empty(2 * B * nc * h * W, device=seg.device, dtype=torch.float32)
-        grad = torch.empty_like(seg)
-        L.lib().wc_ce_loss_fwd_bwd(L.ptr(seg, torch.float32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(part), L.ptr(sums),
-                                   L.ptr(tmp), L.ptr(grad), B, nc, h, w, H, W, int(ignore_index), L.stream())
+        sums, grad = _one_pass("wc_ce_loss_fwd_bwd", seg.float().contiguous(), label.long().contiguous(), ignore_index, 4)
         ctx.save_for_backward(grad)
         _CELossFn.last_sums = sums
         return sums[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None
 
 
 def get_ce_loss_fused(seg_lowres, label, ignore_index=255):
