@@ -661,6 +661,30 @@ int wc_dense_energy_fwd(const float* images, const float* segs, const float* roi
 int wc_dense_energy_bwd(const float* A, const float* rois, const float* grad_out, float* grad_segs, int N, int K, int H, int W,
                         void* stream);
 
+/* ---- dense energy loss as a term of the training step (csrc/energy_prep.hip) ------------------ */
+/* get_energy_loss (utils/losses.py:35-50) on F.interpolate(seg, (H,W), bilinear, align_corners=False) followed by
+ * DenseEnergyLoss.forward (:102-111) at scale_factor = 2^-e, e in {0,1,2}, around the unchanged wc_dense_energy_fwd: the
+ * up-sampled logits, their soft-max and the full-resolution gradient are never written.  Hs = H >> e, Ws = W >> e.
+ * Limits (WC_ERR_ARG, nothing launched): non-null pointers (img_box may be NULL), 1 <= K <= 128, 0 <= e <= 2, Hs, Ws >= 1,
+ * Hs*Ws <= 640*640, W <= 8192, 1 <= N <= 65535 / ceil(K/32).  No allocation, no host synchronisation, every launch on `stream`; no
+ * atomics, fixed-order sums: bit-identical from run to run.
+ * wc_energy_prep_fwd: img (N,3,H,W) f32 normalised, seg (N,K,h,w) f32, label (N,H,W) int64, img_box (N,4) int32 rows
+ *                     (y0, y1, x0, x1) in DEVICE memory, 16-byte aligned, or NULL = the whole image; mean, std: 3 HOST floats.
+ *                     Out, at the scaled size: images_s (N,3,Hs,Ws) = img * std + mean (two roundings) at the nearest source
+ *                     (Y << e, X << e); rois_s (N,Hs,Ws) = 1 inside the box at the nearest source, else 0; unlabel_u8 (N,Hs,Ws)
+ *                     = 1 where the low byte of the label at the nearest source is 255; P_s (N,K,Hs,Ws) = the bilinear
+ *                     down-sample of soft-max_k of the up-sampled logits.  |P_s - P64| <= (16 max|logit| + K + 16) * 2^-24.
+ * wc_energy_prep_workspace_floats: *n_floats (HOST out-parameter) = 2*N*K*h*W: the workspace of wc_energy_prep_bwd.
+ * wc_energy_prep_bwd: A (N,K,Hs,Ws) as wc_dense_energy_fwd wrote it, rois_s as above, seg as above, coef a host float
+ *                     (-2 * weight / N) -> grad_seg (N,K,h,w): G_s = coef * A * rois_s pulled back through the down-sample,
+ *                     the soft-max Jacobian (soft-max recomputed) and the up-sample.  The Gate is a constant. */
+int wc_energy_prep_fwd(const float* img, const float* seg, const int64_t* label, const int* img_box, const float* mean,
+                       const float* std, float* images_s, float* P_s, float* rois_s, void* unlabel_u8, int N, int K, int h, int w,
+                       int H, int W, int e, void* stream);
+int wc_energy_prep_workspace_floats(int N, int K, int h, int W, long* n_floats);
+int wc_energy_prep_bwd(const float* A, const float* rois_s, const float* seg, float* grad_seg, void* ws, float coef, int N, int K,
+                       int h, int w, int H, int W, int e, void* stream);
+
 /* ---- CLIP text tower (csrc/text.hip; DESIGN.md "Text tower") -------------------------------------------------------- */
 /* wc_text_embed:      clip/model.py:393-395 (token_embedding(text) + positional_embedding) and :403 (`text.argmax(-1)`).
  *                     tokens (N, Lctx) int32; tok_emb (V, W) f32; pos (>= L, W) f32.  eot (N) int32 = index of the first

@@ -339,6 +339,15 @@ __global__ __launch_bounds__(1024) void ce_loss_reduce_kernel(const float* __res
     }
 }
 
+// The unscaled X pass alone (resample.h), for a pixel pass of another file that leaves the same tmpA / tmpB rows
+// (csrc/energy_prep.hip): rows = (images * classes) * h.
+int wc_bilinear_bwd_x(const float* tmpA, const float* tmpB, float* grad, long rows, int h, int w, int W, void* stream) {
+    hipLaunchKernelGGL(seg_bwd_x2_kernel<false>, dim3((unsigned)wc_cdiv(rows, 4)), dim3(256), 4 * (W + (W >> 4) + 1) * sizeof(float),
+                       (hipStream_t)stream, tmpA, tmpB, grad, rows, h, w, W, (float)w / W, nullptr);
+    WC_LAUNCH_CHECK("seg_bwd_x2_kernel");
+    return WC_OK;
+}
+
 // Both training entries: [label count,] pixel pass, one-block reduce, X pass.
 template <bool TWO_TERM>
 static int up_ce_fwd_bwd(const char* who, const float* seg, const int64_t* label, float* cnt, float* part, float* sums,

@@ -49,6 +49,10 @@ __device__ __forceinline__ int wc_resize_argmax_at(const float* __restrict__ seg
     return arg;
 }
 
+// X pass of the separable bilinear backward (csrc/losses.hip, seg_bwd_x2_kernel): grad (rows, w) from the row passes' tmpA (rows, W)
+// + tmpB (rows, W; the first of every h rows is not read), every output's window summed in ascending x.  W <= 8192 (LDS).
+int wc_bilinear_bwd_x(const float* tmpA, const float* tmpB, float* grad, long rows, int h, int w, int W, void* stream);
+
 // ---- Pillow ImagingResample, 8 bits per channel ------------------------------------------------------------------
 #define PIL_PREC 22                      // Pillow: PRECISION_BITS = 32 - 8 - 2
 #define PIL_ENT(KMAX) ((KMAX) + 3)       // ints per table entry: first tap, tap count, KMAX fixed-point weights, pad

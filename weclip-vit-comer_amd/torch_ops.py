@@ -401,6 +401,34 @@ def _energy_backward(ctx, grad_loss, grad_A):
 torch.library.register_autograd(f"{_LIB}::dense_energy", _energy_backward, setup_context=_energy_setup)
 
 
+@torch.library.custom_op(f"{_LIB}::energy_term", mutates_args=(), device_types="cuda")
+def energy_term(img: Tensor, seg_lowres: Tensor, label: Tensor, img_box: Optional[Tensor], weight: float, sigma_rgb: float,
+                sigma_xy: float, scale_factor: float, mean: List[float], std: List[float]) -> Tuple[Tensor, Tensor]:
+    """utils.losses.get_energy_loss_fused (csrc/energy_prep.hip around the filter of csrc/energy.hip): the dense energy loss of
+    the bilinearly up-sampled logits at scale_factor 1, 0.5 or 0.25 -> (weight * loss (1,), d(weight * loss) / d seg_lowres
+    (N,K,h,w) for an upstream gradient of 1).  Differentiable in `seg_lowres` (register_autograd scales the second output; the
+    gradient arriving at it is ignored); img_box (N,4) integer rows (y0, y1, x0, x1) on the device, or None."""
+    from .utils.losses import energy_term as term
+    return term(img, seg_lowres, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, list(mean), list(std))
+
+
+@energy_term.register_fake
+def _(img, seg_lowres, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std):
+    return seg_lowres.new_empty((1,), dtype=F32), seg_lowres.new_empty(seg_lowres.shape, dtype=F32)
+
+
+def _energy_term_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _energy_term_backward(ctx, grad_loss, grad_grad):
+    (grad,) = ctx.saved_tensors
+    return (None, grad * grad_loss) + (None,) * 8
+
+
+torch.library.register_autograd(f"{_LIB}::energy_term", _energy_term_backward, setup_context=_energy_term_setup)
+
+
 @torch.library.custom_op(f"{_LIB}::aff_propagate", mutates_args=(), device_types="cuda")
 def aff_propagate(aff: Tensor, cams: Tensor, mask: Optional[Tensor], cls: Optional[Tensor], bkg_score: float,
                   with_bkg: bool) -> Tensor:
@@ -418,4 +446,4 @@ def _(aff, cams, mask, cls, bkg_score, with_bkg):
 
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
-       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "aff_propagate")
+       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate")

@@ -3,10 +3,12 @@ scripts/dist_clip_coco.py) around this package's graph-replayed step.
 
     python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
         [--dataset voc|coco] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
+        [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>]]
 
 The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
 into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is counted by `wc_label_match_count`
 (csrc/trainlog.hip) inside the captured step; every `log_iters` ONE read fetches both.  Validation is `validate.Validator`.
+--reg_loss adds the dense energy (regularised) loss as a fourth scalar of the same accumulator (TrainStep(reg=...)).
 Under `python -m torch.distributed.run` every rank trains on its share of each epoch (DeviceLoader rank / world), gradients
 are averaged through `GradBucket`, every rank validates its share of the images, and rank 0 alone logs and saves.
 
@@ -30,6 +32,7 @@ from .train_step import TrainStep, make_optimizer
 
 LOG = logging.getLogger("weclip.train")
 LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, pseudo_seg_loss: %.4f, attn_loss: %.4f, pseudo_seg_mAcc: %.4f"   # :280
+REG_FORMAT = ", reg_loss: %.4e"                         # appended with --reg_loss only
 SAVE_AFTER = {"voc": 26000, "coco": 40000}              # dist_clip_voc.py:288, dist_clip_coco.py:287
 MODEL_FILE, STATE_FILE = "WeCLIP_model_iter_%d.pth", "train_state_iter_%d.pth"
 _SCI = re.compile(r"^[+-]?(\d+\.?\d*|\.\d+)[eE][+-]?\d+$")
@@ -87,6 +90,12 @@ def build_parser():
     p.add_argument("--max_iters", type=int, default=None, help="overrides train.max_iters")
     p.add_argument("--save_after", type=int, default=None, help="checkpoints are written past this iteration (voc 26000, coco 40000)")
     p.add_argument("--resume", type=str, default=None, help="a WeCLIP_model_iter_N.pth; its train_state_iter_N.pth is loaded with it")
+    p.add_argument("--reg_loss", action="store_true",
+                   help="add the dense energy (regularised) loss to the step; its all-pairs filter costs about four plain steps at "
+                        "batch 16 / crop 512 (DESIGN.md section 15.2)")
+    p.add_argument("--reg_coef", type=float, default=0.01, help="weight of the energy term in the step's loss")
+    p.add_argument("--reg_scale", type=float, default=0.5, choices=(1.0, 0.5, 0.25), help="scale_factor of the DenseEnergyLoss")
+    p.add_argument("--reg_start", type=int, default=None, help="the term starts after this iteration (default: train.cam_iters)")
     return p
 
 
@@ -118,8 +127,27 @@ def state_path_of(model_path):
     return os.path.join(d, STATE_FILE % int(m.group(1)))
 
 
-def format_log_line(n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc):
-    return LOG_FORMAT % (n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc)
+def format_log_line(n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc, reg_loss=None):
+    line = LOG_FORMAT % (n_iter, delta, eta, lr, seg_loss, attn_loss, seg_macc)
+    return line if reg_loss is None else line + REG_FORMAT % reg_loss
+
+
+def log_record(n_iter, lr, host, steps):
+    """The metrics.jsonl record of a window of `steps` steps from the one host read: host = the window sums (loss, seg_loss,
+    attn_loss[, reg_loss with --reg_loss]) followed by the last step's (matches, pixels)."""
+    rec = {"iter": n_iter, "lr": lr, "seg_loss": host[1] / steps, "attn_loss": host[2] / steps, "pseudo_seg_mAcc": host[-2] / host[-1]}
+    if len(host) == 6:
+        rec["reg_loss"] = host[3] / steps
+    return rec
+
+
+def reg_settings(cfg, args):
+    """The `reg` argument of the train step from the command line: None without --reg_loss."""
+    if not getattr(args, "reg_loss", False):
+        return None
+    start = getattr(args, "reg_start", None)
+    return {"coef": float(getattr(args, "reg_coef", 0.01)), "scale_factor": float(getattr(args, "reg_scale", 0.5)),
+            "start_iter": int(cfg.train.cam_iters if start is None else start)}
 
 
 def strict_json(v):
@@ -263,11 +291,13 @@ class Trainer:
         self.opt = make_optimizer(self.model, lr=float(opt.learning_rate), weight_decay=float(opt.weight_decay),
                                   betas=tuple(float(b) for b in opt.betas), warmup_iter=int(sch.warmup_iter),
                                   max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power))
+        self.reg = reg_settings(cfg, args)
         self.step = LoggedTrainStep(self.model, self.opt, radius=getattr(args, "radius", 8), ignore_index=ds.ignore_index,
-                                    graph=bool(getattr(args, "graph", True)))
+                                    graph=bool(getattr(args, "graph", True)), reg=self.reg)
         self.validator = Validator(self.model, ds.num_classes, self.rank, self.world)
         dev = next(self.model.parameters()).device
-        self.acc = torch.zeros(3, device=dev, dtype=torch.float32)      # window sums of (loss, seg_loss, attn_loss)
+        # window sums of (loss, seg_loss, attn_loss[, reg_loss with --reg_loss])
+        self.acc = torch.zeros(3 if self.reg is None else 4, device=dev, dtype=torch.float32)
         self.window = 0                                                 # steps in the window (host)
         self.n_iter = 0
         self.time0 = datetime.datetime.now().replace(microsecond=0)
@@ -297,11 +327,11 @@ class Trainer:
                 self._batches = None
 
     def step_once(self):
-        """One training iteration -> the step's (loss, seg_loss, attn_loss) device scalars.  No host read."""
+        """One training iteration -> the step's (loss, seg_loss, attn_loss[, reg_loss]) device scalars.  No host read."""
         from .datasets import labels_from_onehot
-        _, inputs, _, _ = self._next_batch()
+        _, inputs, _, img_box = self._next_batch()
         labels = labels_from_onehot(self.train_loader.last_cls_labels)      # the host copy: graph mode needs explicit labels
-        out = self.step(inputs, labels=labels)
+        out = self.step(inputs, labels=labels) if self.reg is None else self.step(inputs, labels=labels, img_box=img_box)
         self.acc.add_(torch.stack(out))
         self.window += 1
         self.n_iter += 1
@@ -317,10 +347,10 @@ class Trainer:
         steps, self.window = self.window, 0
         if host is None:
             return None
-        rec = {"iter": self.n_iter, "lr": self.opt.param_groups[0]["lr"], "seg_loss": host[1] / steps,
-               "attn_loss": host[2] / steps, "pseudo_seg_mAcc": host[3] / host[4]}
+        rec = log_record(self.n_iter, self.opt.param_groups[0]["lr"], host, steps)
         delta, eta = cal_eta(self.time0, max(self.n_iter, 1), self.max_iters)
-        LOG.info(format_log_line(rec["iter"], delta, eta, rec["lr"], rec["seg_loss"], rec["attn_loss"], rec["pseudo_seg_mAcc"]))
+        LOG.info(format_log_line(rec["iter"], delta, eta, rec["lr"], rec["seg_loss"], rec["attn_loss"], rec["pseudo_seg_mAcc"],
+                                 rec.get("reg_loss")))
         append_metrics(self.metrics_path, rec)
         if self.writer is not None:
             self.writer.add_scalars("train/loss", {"seg_loss": rec["seg_loss"], "attn_loss": rec["attn_loss"]}, global_step=self.n_iter)
@@ -376,6 +406,8 @@ class Trainer:
         self.opt.load_state_dict(state["optimizer"])
         self.opt.global_step = int(state["global_step"])
         self.n_iter = int(state["iter"])
+        if self.step.reg is not None:
+            self.step.reg.step_num = self.n_iter         # the term's start counts the training iterations
         self.model.iter_num = int(state["model_iter_num"])
         self.train_loader.set_epoch(int(state["loader_epoch"]))
         self._batches = None

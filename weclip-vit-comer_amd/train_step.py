@@ -11,7 +11,8 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from .utils.camutils import cams_to_affinity_label, get_mask_by_radius
-from .utils.losses import get_aff_loss, get_aff_loss_fused, get_ce_loss_fused, get_seg_loss, get_seg_loss_fused
+from .utils.losses import (DenseEnergyLoss, get_aff_loss, get_aff_loss_fused, get_ce_loss_fused, get_energy_loss_fused,
+                           get_seg_loss, get_seg_loss_fused)
 from .utils.optimizer import PolyWarmupAdamW
 
 
@@ -28,6 +29,56 @@ def make_optimizer(model, lr=2e-4, weight_decay=0.01, betas=(0.9, 0.999), warmup
     ]
     return PolyWarmupAdamW(groups, lr=lr, weight_decay=weight_decay, betas=list(betas),
                            warmup_iter=warmup_iter, max_iter=max_iter, warmup_ratio=warmup_ratio, power=power)
+
+
+class RegTerm:
+    """The regularised (dense energy) loss as a term of a training step: `reg` (RegTerm.of(None) is None: no term) is a dict
+    or an object with any of
+        coef (0.01): the term's weight in the step's loss;  start_iter (0): the term is active at 1-based step numbers > start_iter;
+        weight (1e-7), sigma_rgb (15), sigma_xy (100), scale_factor (0.5): the DenseEnergyLoss, the lineage's parameters.
+    `coef` and `start_iter` are this package's choice (the reference checkout never calls its get_energy_loss; DESIGN.md
+    section 15.2).  scale_factor must be 1, 0.5 or 0.25 (utils.losses.get_energy_loss_fused)."""
+
+    DEFAULTS = dict(coef=0.01, weight=1e-7, sigma_rgb=15, sigma_xy=100, scale_factor=0.5, start_iter=0)
+
+    @classmethod
+    def of(cls, reg):
+        return None if reg is None else cls(reg)
+
+    def __init__(self, reg):
+        if isinstance(reg, dict):
+            unknown = set(reg) - set(self.DEFAULTS)
+            if unknown:
+                raise ValueError(f"reg: unknown keys {sorted(unknown)} (known: {sorted(self.DEFAULTS)})")
+            reg = type("reg", (), reg)
+        for k, v in self.DEFAULTS.items():
+            setattr(self, k, getattr(reg, k, v))
+        if float(self.scale_factor) not in (1.0, 0.5, 0.25):
+            raise ValueError(f"reg: scale_factor must be 1, 0.5 or 0.25, got {self.scale_factor}")
+        self.start_iter = int(self.start_iter)
+        self.layer = DenseEnergyLoss(self.weight, self.sigma_rgb, self.sigma_xy, self.scale_factor)
+        self.step_num = 0                    # steps begun (1-based number of the current one)
+
+    def begin_step(self):
+        """Counts the step that begins and returns whether the term is active in it."""
+        self.step_num += 1
+        return self.step_num > self.start_iter
+
+    def box_buffer(self, img):
+        return torch.empty(img.shape[0], 4, device=img.device, dtype=torch.int32)
+
+    def fill_box(self, buf, img_box, img):
+        """img_box (None: the whole image, rows, or a tensor on either side) -> the static (B, 4) int32 buffer, no host read."""
+        if img_box is None:
+            img_box = [[0, img.shape[2], 0, img.shape[3]]] * img.shape[0]
+        buf.copy_(torch.as_tensor(img_box).reshape(buf.shape))
+
+    def add(self, loss, img, seg, label, img_box, active):
+        """(loss + coef * energy, energy) when active, else (loss, 0): energy = the DenseEnergyLoss of the up-sampled `seg`."""
+        if not active:
+            return loss, torch.zeros((), device=seg.device, dtype=torch.float32)
+        energy = get_energy_loss_fused(img, seg, label, img_box, self.layer)[0]
+        return loss + self.coef * energy, energy.detach()
 
 
 class GradBucket:
@@ -69,10 +120,17 @@ class TrainStep:
     pad_plans (default on in graph mode): the signature is BUCKETED (clip_tool.PairPlan pad=True: pair count to a multiple
     of 8 with dropped dummy pairs, channel capacity K to the next even number), so batches whose images carry 1..5
     classes share a few graphs instead of one per distinct (pair count, max classes); losses, gradients and parameters
-    stay bit-identical to the unpadded eager step (tests/test_graph_step_gpu.py)."""
+    stay bit-identical to the unpadded eager step (tests/test_graph_step_gpu.py).
 
-    def __init__(self, model, optimizer=None, radius=8, ignore_index=255, bucket=True, graph=False, pad_plans=True):
+    reg (default None: nothing changes): a `RegTerm` description.  The loss becomes seg_loss + 0.1 * attn_loss + coef * energy
+    at step numbers > start_iter, energy = the dense energy loss of the up-sampled logits against the step's input image and
+    pseudo labels inside `img_box` (an argument of the call: None = the whole image, or (B, 4) rows (y0, y1, x0, x1) on either
+    side); the step then returns a fourth value, the energy before `coef` (zero while the term is inactive).  Whether the term
+    is active is part of the graph signature, and img_box goes through a static buffer."""
+
+    def __init__(self, model, optimizer=None, radius=8, ignore_index=255, bucket=True, graph=False, pad_plans=True, reg=None):
         self.model = model
+        self.reg = RegTerm.of(reg)
         self.opt = optimizer or make_optimizer(model)
         self.radius, self.ignore = radius, ignore_index
         self._mask = {}
@@ -123,10 +181,14 @@ class TrainStep:
                     dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)
                     p.grad.div_(world)
 
-    def _fwd_bwd(self, img, names, labels, plan=None):
+    def _fwd_bwd(self, img, names, labels, plan=None, img_box=None, reg_active=False):
         kw = {"plan": plan} if plan is not None else {}
         seg, cam, attn_pred = self.model(img, names if names is not None else [""] * img.shape[0], labels=labels, **kw)
         loss, seg_loss, attn_loss = self.losses(seg, cam, attn_pred)
+        extra = ()
+        if self.reg is not None:
+            loss, energy = self.reg.add(loss, img, seg, cam, img_box, reg_active)
+            extra = (energy,)
         if self.bucket is not None:
             self.bucket.zero()
         else:
@@ -136,37 +198,44 @@ class TrainStep:
             cur = torch.cuda.current_stream()
             for s in getattr(self.model, "side_streams", lambda: [])():
                 cur.wait_stream(s)
-        return loss.detach(), seg_loss.detach(), attn_loss.detach()
+        return (loss.detach(), seg_loss.detach(), attn_loss.detach()) + extra
 
-    def __call__(self, img, names=None, labels=None):
+    def __call__(self, img, names=None, labels=None, img_box=None):
+        active = self.reg is not None and self.reg.begin_step()
         if self.graph and labels is not None and img.is_cuda and self.bucket is not None:
-            out = self._graphed(img, labels)
+            out = self._graphed(img, labels, img_box, active)
         else:
-            out = self._fwd_bwd(img, names, labels)
+            out = self._fwd_bwd(img, names, labels, img_box=img_box, reg_active=active)
         self._reduce_grads()
         self.opt.step()
         return out
 
     # ---------------------------------------------------------------------------------- HIP-graph replay
-    def _signature(self, img, labels):
+    def _signature(self, img, labels, reg_active=False):
         from .clip.clip_tool import PairPlan
         m = self.model
         seg_trans = (m.iter_num + 1) > m.seg_trans_after
-        return (tuple(img.shape), PairPlan.signature(labels, self.pad_plans), bool(seg_trans), bool(m.training))
+        sig = (tuple(img.shape), PairPlan.signature(labels, self.pad_plans), bool(seg_trans), bool(m.training))
+        return sig + (True,) if reg_active else sig
 
-    def _graphed(self, img, labels):
+    def _graphed(self, img, labels, img_box=None, reg_active=False):
         from .clip.clip_tool import PairPlan
         m = self.model
-        sig = self._signature(img, labels)
+        sig = self._signature(img, labels, reg_active)
         ent = self._graphs.get(sig)
         if ent is None:                      # first step of this signature: eager (warms lazy state), sets up the statics
             ent = self._graphs[sig] = {"graph": None, "img": torch.empty_like(img, dtype=torch.float32).contiguous(),
                                        "plan": PairPlan(labels, m.fg_text_features.shape[0], m.bg_text_features.shape[0],
-                                                        img.device, pad=self.pad_plans)}
+                                                        img.device, pad=self.pad_plans),
+                                       "box": self.reg.box_buffer(img) if reg_active else None}
             ent["img"].copy_(img)
-            return self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"])
+            if reg_active:
+                self.reg.fill_box(ent["box"], img_box, img)
+            return self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"], img_box=ent["box"], reg_active=reg_active)
         ent["img"].copy_(img)
         ent["plan"].update(labels)
+        if reg_active:
+            self.reg.fill_box(ent["box"], img_box, img)
         if ent["graph"] is None:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
@@ -174,7 +243,7 @@ class TrainStep:
             # thread_local: other threads (RCCL's watchdog polling its events, the autograd workers allocating) must not
             # abort the capture; the kernels the autograd workers launch on the capturing stream are captured all the same
             with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                out = self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"])
+                out = self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"], img_box=ent["box"], reg_active=reg_active)
                 ent["out"] = torch.stack(out)
             m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
             self._pool = self._pool or g.pool()
@@ -182,7 +251,7 @@ class TrainStep:
         ent["graph"].replay()
         m.iter_num += 1
         o = ent["out"].clone()               # the graph's pool memory is rewritten by the next replay
-        return o[0], o[1], o[2]
+        return tuple(o[i] for i in range(o.shape[0]))
 
 
 class SupervisedTrainStep:
@@ -196,10 +265,15 @@ class SupervisedTrainStep:
     augmentation happens before); returns the detached loss.  graph=True (CUDA tensors, with a bucket): forward + loss +
     backward are captured once per (image shape, label shape, training flag) -- the first step of a signature runs eagerly,
     the second captures -- and replayed from static input buffers; the all-reduce and the optimizer stay outside the graph,
-    as in TrainStep."""
+    as in TrainStep.
 
-    def __init__(self, model, optimizer=None, ignore_index=255, bucket=True, graph=False):
+    reg (default None: nothing changes): a `RegTerm` description, as in TrainStep.  The loss becomes ce + coef * energy at step
+    numbers > start_iter, with the ground-truth label and `img_box` (third argument of the call; None = the whole image); the
+    step then returns (loss, energy before `coef`), the energy zero while the term is inactive."""
+
+    def __init__(self, model, optimizer=None, ignore_index=255, bucket=True, graph=False, reg=None):
         self.model = model
+        self.reg = RegTerm.of(reg)
         self.opt = optimizer or make_optimizer(model)
         self.ignore = int(ignore_index)
         self.bucket = GradBucket(model.get_param_groups()[3]) if bucket else None
@@ -222,48 +296,58 @@ class SupervisedTrainStep:
         segs = F.interpolate(seg, size=label.shape[1:], mode="bilinear", align_corners=False)
         return F.cross_entropy(segs, label.long(), ignore_index=self.ignore)
 
-    def _fwd_bwd(self, img, label):
+    def _fwd_bwd(self, img, label, img_box=None, reg_active=False):
         seg = self.model(img, mode="train")
         loss = self.loss(seg, label)
+        if self.reg is not None:
+            loss, energy = self.reg.add(loss, img, seg, label, img_box, reg_active)
         if self.bucket is not None:
             self.bucket.zero()
         else:
             self.opt.zero_grad()
         loss.backward()
-        return loss.detach()
+        return loss.detach() if self.reg is None else (loss.detach(), energy)
 
-    def __call__(self, img, label):
+    def __call__(self, img, label, img_box=None):
+        active = self.reg is not None and self.reg.begin_step()
         if self.graph and img.is_cuda and self.bucket is not None:
-            out = self._graphed(img, label)
+            out = self._graphed(img, label, img_box, active)
         else:
-            out = self._fwd_bwd(img, label)
+            out = self._fwd_bwd(img, label, img_box, active)
         self._reduce_grads()
         self.opt.step()
         return out
 
     step = __call__
 
-    def _graphed(self, img, label):
+    def _graphed(self, img, label, img_box=None, reg_active=False):
         m = self.model
-        sig = (tuple(img.shape), tuple(label.shape), bool(m.training))
+        sig = (tuple(img.shape), tuple(label.shape), bool(m.training)) + ((True,) if reg_active else ())
         ent = self._graphs.get(sig)
         if ent is None:                      # first step of this signature: eager (warms lazy state), sets up the statics
             ent = self._graphs[sig] = {"graph": None, "img": torch.empty(img.shape, device=img.device, dtype=torch.float32),
-                                       "label": torch.empty(label.shape, device=img.device, dtype=torch.int64)}
+                                       "label": torch.empty(label.shape, device=img.device, dtype=torch.int64),
+                                       "box": self.reg.box_buffer(img) if reg_active else None}
             ent["img"].copy_(img)
             ent["label"].copy_(label)
-            return self._fwd_bwd(ent["img"], ent["label"])
+            if reg_active:
+                self.reg.fill_box(ent["box"], img_box, img)
+            return self._fwd_bwd(ent["img"], ent["label"], ent["box"], reg_active)
         ent["img"].copy_(img)
         ent["label"].copy_(label)
+        if reg_active:
+            self.reg.fill_box(ent["box"], img_box, img)
         if ent["graph"] is None:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             it = m.iter_num
             with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                ent["out"] = self._fwd_bwd(ent["img"], ent["label"])
+                out = self._fwd_bwd(ent["img"], ent["label"], ent["box"], reg_active)
+                ent["out"] = out if self.reg is None else torch.stack(out)
             m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
             self._pool = self._pool or g.pool()
             ent["graph"] = g
         ent["graph"].replay()
         m.iter_num += 1
-        return ent["out"].clone()            # the graph's pool memory is rewritten by the next replay
+        o = ent["out"].clone()               # the graph's pool memory is rewritten by the next replay
+        return o if self.reg is None else (o[0], o[1])

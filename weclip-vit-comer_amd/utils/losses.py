@@ -1,6 +1,7 @@
 """Loss functions of the reference (utils/losses.py:11-22 get_aff_loss; scripts/dist_clip_voc.py:105-113 get_seg_loss) in
 stock PyTorch-ROCm ops, their fused HIP forms, and the dense energy loss (utils/losses.py:35-116:
-get_energy_loss, DenseEnergyLossFunction, DenseEnergyLoss) on the GPU (csrc/energy.hip)."""
+get_energy_loss, DenseEnergyLossFunction, DenseEnergyLoss) on the GPU (csrc/energy.hip), with its training-step form
+get_energy_loss_fused (csrc/energy_prep.hip)."""
 import torch
 import torch.nn.functional as F
 
@@ -303,3 +304,156 @@ def get_energy_loss(img, logit, label, img_box, loss_layer, mean=[123.675, 116.2
         crop_mask[idx, int(coord[0]):int(coord[1]), int(coord[2]):int(coord[3])] = 1
     _img = torch.stack([img[:, c] * std[c] + mean[c] for c in range(3)], dim=1)
     return loss_layer(_img, pred_prob, crop_mask, label.type(torch.uint8).unsqueeze(1))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The same loss as a term of the training step (csrc/energy_prep.hip): from the low-resolution head
+# output to a low-resolution gradient around the unchanged filter, with no full-resolution (N, K, H, W) tensor and no host
+# read of a device img_box, so the step that contains it can be captured in a graph.
+_ENERGY_SCALES = {1.0: 0, 0.5: 1, 0.25: 2}         # scale_factor = 2^-e: ATen's nearest / bilinear sources are exact
+_ENERGY_MAX_HW = 640 * 640                        # the filter's limit on the scaled size
+
+
+def _energy_term_check(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std):
+    """Host-side checks of get_energy_loss_fused, before anything is allocated or launched.  Returns e (scale_factor = 2^-e)."""
+    who = "get_energy_loss_fused"
+    if not all(isinstance(t, torch.Tensor) for t in (img, seg, label)):
+        raise TypeError(f"{who}: img, seg_lowres and label must be tensors")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"{who}: img must be (N, 3, H, W), got shape {tuple(img.shape)}")
+    if seg.dim() != 4:
+        raise ValueError(f"{who}: seg_lowres must be (N, K, h, w), got shape {tuple(seg.shape)}")
+    if label.dim() != 3:
+        raise ValueError(f"{who}: label must be (N, H, W), got shape {tuple(label.shape)}")
+    if not img.dtype.is_floating_point or not seg.dtype.is_floating_point:
+        raise TypeError(f"{who}: img and seg_lowres must be floating-point tensors, got {img.dtype} and {seg.dtype}")
+    if label.dtype.is_floating_point or label.dtype.is_complex or label.dtype == torch.bool:
+        raise TypeError(f"{who}: label must be an integer tensor, got {label.dtype}")
+    if not (img.shape[0] == seg.shape[0] == label.shape[0]):
+        raise ValueError(f"{who}: batch sizes differ (img {img.shape[0]}, seg_lowres {seg.shape[0]}, label {label.shape[0]})")
+    if tuple(img.shape[2:]) != tuple(label.shape[1:]):
+        raise ValueError(f"{who}: img {tuple(img.shape[2:])} and label {tuple(label.shape[1:])} differ in size")
+    if not 1 <= seg.shape[1] <= 128:
+        raise ValueError(f"{who}: 1 <= K <= 128, got {seg.shape[1]}")
+    if min(img.shape) == 0 or min(seg.shape) == 0:
+        raise ValueError(f"{who}: empty input")
+    if not (img.device == seg.device == label.device):
+        raise ValueError(f"{who}: img on {img.device}, seg_lowres on {seg.device}, label on {label.device}")
+    e = _ENERGY_SCALES.get(float(scale_factor))
+    if e is None:
+        raise ValueError(f"{who}: scale_factor must be 1, 0.5 or 0.25, got {scale_factor} (DenseEnergyLoss serves the others)")
+    Hs, Ws = img.shape[2] >> e, img.shape[3] >> e
+    if Hs < 1 or Ws < 1 or Hs * Ws > _ENERGY_MAX_HW or img.shape[3] > 8192:
+        raise ValueError(f"{who}: the scaled size {Hs} x {Ws} must be 1 .. 640*640 pixels and W <= 8192")
+    for name, v in (("weight", weight), ("sigma_rgb", sigma_rgb), ("sigma_xy", sigma_xy)):
+        if not isinstance(v, (int, float)) or isinstance(v, bool):
+            raise TypeError(f"{who}: loss_layer.{name} must be a number, got {type(v).__name__}")
+    if not (sigma_rgb > 0 and sigma_xy > 0):
+        raise ValueError(f"{who}: sigmas must be > 0, got sigma_rgb {sigma_rgb}, sigma_xy {sigma_xy}")
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError(f"{who}: mean and std must have 3 entries")
+    if isinstance(img_box, torch.Tensor):
+        if img_box.dtype.is_floating_point or img_box.dtype.is_complex or img_box.dtype == torch.bool:
+            raise TypeError(f"{who}: img_box must be an integer tensor, got {img_box.dtype}")
+        if img_box.is_cuda and img_box.device != seg.device:
+            raise ValueError(f"{who}: img_box on {img_box.device}, seg_lowres on {seg.device}")
+        shape = tuple(img_box.shape)
+    elif img_box is not None:
+        try:
+            shape = (len(img_box),) + tuple({len(r) for r in img_box})
+        except TypeError:
+            raise TypeError(f"{who}: img_box must be None, rows of (y0, y1, x0, x1) or an integer tensor") from None
+    if img_box is not None and shape != (img.shape[0], 4):
+        raise ValueError(f"{who}: img_box must be ({img.shape[0]}, 4): rows (y0, y1, x0, x1), got {shape}")
+    return e
+
+
+def energy_prep_forward(img, seg, label, box, e, mean, std):
+    """wc_energy_prep_fwd: (images_s (N,3,Hs,Ws), P_s (N,K,Hs,Ws), rois_s (N,Hs,Ws), unlabel_u8 (N,Hs,Ws)), the inputs of
+    wc_dense_energy_fwd at scale 2^-e.  img, seg f32 and label int64, contiguous, on the device; box None or int32 (N, 4) there."""
+    import ctypes
+    from .. import _lib as L
+    N, K, h, w = seg.shape
+    H, W = label.shape[1:]
+    Hs, Ws = H >> e, W >> e
+    images_s, P_s, rois_s = (torch.empty(N, c, Hs, Ws, device=seg.device, dtype=torch.float32) for c in (3, K, 1))
+    rois_s = rois_s[:, 0]
+    unl = torch.empty(N, Hs, Ws, device=seg.device, dtype=torch.uint8)
+    F3 = ctypes.c_float * 3
+    L.lib().wc_energy_prep_fwd(L.ptr(img, torch.float32, "img"), L.ptr(seg, torch.float32, "seg_lowres"), L.ptr(label, torch.int64, "label"),
+                               L.ptr(box, torch.int32, "img_box"), F3(*[float(v) for v in mean]), F3(*[float(v) for v in std]),
+                               L.ptr(images_s), L.ptr(P_s), L.ptr(rois_s), L.ptr(unl), N, K, h, w, H, W, e, L.stream())
+    return images_s, P_s, rois_s, unl
+
+
+def energy_prep_backward(A, rois_s, seg, coef, size, e):
+    """wc_energy_prep_bwd: grad_seg (N,K,h,w) = coef * A * rois_s pulled back through the down-sample by 2^e, the soft-max and the
+    up-sample of seg to `size` = (H, W)."""
+    import ctypes
+    from .. import _lib as L
+    N, K, h, w = seg.shape
+    H, W = size
+    n = ctypes.c_long()
+    L.lib().wc_energy_prep_workspace_floats(N, K, h, W, ctypes.byref(n))
+    ws = torch.empty(n.value, device=seg.device, dtype=torch.float32)
+    grad = torch.empty_like(seg)
+    L.lib().wc_energy_prep_bwd(L.ptr(A, torch.float32, "A"), L.ptr(rois_s, torch.float32, "rois_s"), L.ptr(seg, torch.float32, "seg_lowres"),
+                               L.ptr(grad), L.ptr(ws), float(coef), N, K, h, w, H, W, e, L.stream())
+    return grad
+
+
+def energy_term(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std, need_grad=True):
+    """(weight * loss (1,), d(weight * loss) / d seg for an upstream gradient of 1, or None) of get_energy_loss_fused:
+    wc_energy_prep_fwd, the filter (wc_dense_energy_fwd, unchanged), wc_energy_prep_bwd.  No host synchronisation."""
+    from .. import _lib as L
+    e = _energy_term_check(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std)
+    L.require_gpu()
+    dev = seg.device
+    img = img.detach().float().contiguous()
+    seg = seg.detach().float().contiguous()
+    label = label.long().contiguous()
+    box = None
+    if img_box is not None:        # a device tensor stays on the device; rows and host tensors are host data
+        box = torch.as_tensor(img_box).to(device=dev, dtype=torch.int32).contiguous()
+        if box.data_ptr() % 16:
+            box = box.clone()
+    N, K = seg.shape[:2]
+    images_s, P_s, rois_s, unl = energy_prep_forward(img, seg, label, box, e, mean, std)
+    Hs, Ws = rois_s.shape[1:]
+    A, gate, loss = torch.empty_like(P_s), torch.empty_like(rois_s), torch.empty(1, device=dev, dtype=torch.float32)
+    L.lib().wc_dense_energy_fwd(L.ptr(images_s), L.ptr(P_s), L.ptr(rois_s), L.ptr(unl), L.ptr(A), L.ptr(gate), L.ptr(loss),
+                                L.ptr(_energy_workspace(N, K, Hs, Ws, dev)), N, K, Hs, Ws, float(sigma_rgb),
+                                float(sigma_xy * scale_factor), L.stream())
+    grad = energy_prep_backward(A, rois_s, seg, -2.0 * float(weight) / N, label.shape[1:], e) if need_grad else None
+    return weight * loss, grad
+
+
+class _EnergyTermFn(torch.autograd.Function):
+    """get_energy_loss_fused: like `_OnePassLossFn`, the forward saves the gradient for an upstream gradient of 1 and the
+    backward only scales it."""
+
+    @staticmethod
+    def forward(ctx, seg, img, label, img_box, params, mean, std):
+        loss, grad = energy_term(img, seg, label, img_box, *params, mean, std, need_grad=ctx.needs_input_grad[0])
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g,) + (None,) * 6
+
+
+def get_energy_loss_fused(img, seg_lowres, label, img_box, loss_layer, mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375]):
+    """== get_energy_loss(img, F.interpolate(seg_lowres, label.shape[1:], mode='bilinear', align_corners=False), label, img_box,
+    loss_layer) for a `DenseEnergyLoss` whose scale_factor is 1, 0.5 or 0.25 (any other: ValueError; the stock layer serves
+    those), without the up-sampled logits, their soft-max or a full-resolution gradient.  img (N, 3, H, W) normalised,
+    seg_lowres (N, K, h, w), 1 <= K <= 128, label (N, H, W) integer; img_box: None (the whole image), rows (y0, y1, x0, x1), or
+    an integer tensor (N, 4) on the host or on the device -- a device tensor is never read on the host (rows with 0 <= y0, x0;
+    Python's negative slice indices are not emulated).  Returns weight * loss, shape (1,); the Gate is a constant in backward."""
+    try:
+        params = tuple(getattr(loss_layer, k) for k in ("weight", "sigma_rgb", "sigma_xy", "scale_factor"))
+    except AttributeError:
+        raise TypeError("get_energy_loss_fused: loss_layer must be a DenseEnergyLoss (weight, sigma_rgb, sigma_xy, scale_factor)") from None
+    return _EnergyTermFn.apply(seg_lowres, img, label, img_box, params, mean, std)
