@@ -227,15 +227,15 @@ def _labels(seed, hw=(37, 53)):
     return lab
 
 
-def _run_steps(graph):
+def _run_steps(graph, batches=tuple((s, (37, 53)) for s in BATCHES), make_step=None):
     from weclip_vit_comer_amd.train_step import SupervisedTrainStep
     torch.manual_seed(0)
     m = _seg_model()                 # eval: no Dropout2d, so eager and replayed steps see the same arithmetic
-    step = SupervisedTrainStep(m, graph=graph)
+    step = (make_step or SupervisedTrainStep)(m, graph=graph)
     losses = []
-    for s in BATCHES:
+    for s, hw in batches:
         img = synth.make_images(2, H, W, seed=s).cuda()
-        losses.append(step(img, _labels(s).cuda()).item())
+        losses.append(step(img, _labels(s, hw).cuda()).item())
     params = torch.cat([p.detach().flatten() for p in m.get_param_groups()[3]])
     return losses, params, step, m
 
@@ -248,6 +248,34 @@ def test_supervised_step_graph_replay_is_bit_identical_to_eager():
     assert le == lg, (le, lg)
     assert torch.equal(pe, pg)
     assert len(set(le)) == 3 and all(np.isfinite(le))
+
+
+def test_supervised_step_second_signature_gets_its_own_graph():
+    """Two label sizes: two graphs out of one pool, `iter_num` counted once per step across both, all of it as in eager."""
+    batches = [(11, (37, 53)), (12, (37, 53)), (13, (40, 48)), (14, (40, 48)), (15, (40, 48))]
+    le, pe, _, me = _run_steps(False, batches)
+    lg, pg, step, mg = _run_steps(True, batches)
+    assert len(step._graphs) == 2 and all(ent["graph"] is not None for ent in step._graphs.values())
+    assert me.iter_num == mg.iter_num == 5
+    assert all(np.isfinite(lg)) and le == lg, (le, lg)
+    assert torch.equal(pe, pg)
+
+
+def test_supervised_step_subclass_loss_override_is_captured():
+    """A `loss` override that also writes to a device buffer runs inside the captured region: every replay refreshes the
+    buffer (what train.LoggedTrainStep.losses relies on for the weak class)."""
+    from weclip_vit_comer_amd.train_step import SupervisedTrainStep
+    buf = torch.full((), -1.0, device="cuda")
+
+    class Marked(SupervisedTrainStep):
+        def loss(self, seg, label):
+            loss = super().loss(seg, label)
+            buf.copy_(loss.detach())
+            return loss
+
+    losses, _, step, _ = _run_steps(True, make_step=Marked)
+    assert next(iter(step._graphs.values()))["graph"] is not None
+    assert len(set(losses)) == 3 and buf.item() == losses[2]
 
 
 def test_supervised_step_matches_stock_torch_step():

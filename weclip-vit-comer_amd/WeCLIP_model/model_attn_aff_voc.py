@@ -126,16 +126,8 @@ class WeCLIP(nn.Module):
         """Frozen encoder: token rows of blocks 1..11 and the head-mean maps the affinity needs (none when the
         caller returns before the CAM stage: the COCO model in 'val', model_attn_aff_coco.py:131-132).
         `x16` (a list) additionally receives fp16 copies of the block outputs (adapter operands)."""
-        vis = self.encoder.visual
-        rows, B, Lq = vis.embed(img)
         need = self._maps_needed(seg_trans) if want_maps else [False] * 11
-        xs, maps = [], []
-        for i in range(vis.transformer.layers - 1):
-            rows, m = VE.run_block(vis.transformer.resblocks[i].pack(), rows, B, Lq, want_mean=need[i], x16_out=x16,
-                                   tag=b"@vit_attn")
-            xs.append(rows)
-            maps.append(m)
-        return xs, maps, B, Lq
+        return VE.encode_blocks(self.encoder.visual, img, need, x16)
 
     def forward(self, img, img_names="2007_000032", mode="train", labels=None, plan=None, sizes=None):
         """-> (seg (B,nc,h,w), cam_labels (B,H,W) int64 [list of per-image maps in 'val' when the
@@ -158,10 +150,7 @@ class WeCLIP(nn.Module):
             xs, maps, _, Lq = self.encode(img, seg_trans, x16, want_maps=want_cam)
         if hip_head:
             # adapters + decoder + attn_pred, forward and backward as HIP launches (head_engine.py)
-            drop = None
-            if self.training:
-                p = self.decoder_fts_fuse.dropout.p
-                drop = ((torch.rand(B, self.embedding_dim, device=img.device) >= p).float() / (1.0 - p)).contiguous()
+            drop = self.head_engine.draw_dropout(B, img.device) if self.training else None
             # Outside the seg-trans branch the CAM -> affinity -> PAR chain reads nothing the head produces (clip_tool.py:146-176
             # takes attn_pred only after iteration 15000): the head's forward runs on a second stream beside it and joins before the
             # losses (measured: the gain comes from running beside the last-layer / GradCAM GEMMs; beside the PAR sweeps it is a loss).

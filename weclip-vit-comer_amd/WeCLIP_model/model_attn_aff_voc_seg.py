@@ -67,13 +67,7 @@ class WeCLIP(nn.Module):
     def encode(self, img, x16=None):
         """Frozen encoder: token rows of blocks 1..11 (the adapters' inputs), no head-mean maps.  `x16` (a list)
         additionally receives fp16 copies of the block outputs (the HIP head's operands)."""
-        vis = self.encoder.visual
-        rows, B, Lq = vis.embed(img)
-        xs = []
-        for i in range(vis.transformer.layers - 1):
-            rows, _ = VE.run_block(vis.transformer.resblocks[i].pack(), rows, B, Lq, want_mean=False, x16_out=x16,
-                                   tag=b"@vit_attn")
-            xs.append(rows)
+        xs, _, B, Lq = VE.encode_blocks(self.encoder.visual, img, [False] * 11, x16)
         return xs, B, Lq
 
     def forward(self, img, img_names="2007_000032", mode="train"):
@@ -88,10 +82,7 @@ class WeCLIP(nn.Module):
         with torch.no_grad():
             xs, _, Lq = self.encode(img, x16)
         if hip_head:
-            drop = None
-            if self.training:       # Dropout2d of the head: the same mask draw as the VOC model
-                p = self.decoder_fts_fuse.dropout.p
-                drop = ((torch.rand(B, self.embedding_dim, device=img.device) >= p).float() / (1.0 - p)).contiguous()
+            drop = self.head_engine.draw_dropout(B, img.device) if self.training else None
             seg, _ = HeadFunction.apply(self.head_engine, x16, B, Lq, h, w, drop, *self.head_engine.params())
             return seg
         fts = self.decoder_fts_fuse.forward_rows(xs, B, Lq, h, w)

@@ -100,6 +100,18 @@ def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, ca
     return x2, mean
 
 
+def encode_blocks(vis, img, need, x16=None):
+    """The frozen visual tower `vis` up to its last block but one: -> (token rows of blocks 1..11, their head-mean maps
+    [None where `need[i]` is false], B, Lq).  `x16` (a list) additionally receives fp16 copies of the block outputs."""
+    rows, B, Lq = vis.embed(img)
+    xs, maps = [], []
+    for i in range(vis.transformer.layers - 1):
+        rows, m = run_block(vis.transformer.resblocks[i].pack(), rows, B, Lq, want_mean=need[i], x16_out=x16, tag=b"@vit_attn")
+        xs.append(rows)
+        maps.append(m)
+    return xs, maps, B, Lq
+
+
 def to_rows(x_lne):
     """(L, N, E) reference layout -> ((N*L, E) fp32 image-major rows, N, L)."""
     Lq, N, E = x_lne.shape

@@ -68,6 +68,11 @@ class HeadEngine:
     def dec_params(self):
         return list(self.dec.parameters())
 
+    def draw_dropout(self, B, device):
+        """The Dropout2d of the fused features as forward()'s `drop_scale`: one draw of a (B, E) mask, over (1 - p)."""
+        p = self.fuse.dropout.p
+        return ((torch.rand(B, self.E, device=device) >= p).float() / (1.0 - p)).contiguous()
+
     def _weight_matrices(self):
         out = []
         for l, mlp in enumerate(self.fuse.linears_modulelist):

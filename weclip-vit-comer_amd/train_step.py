@@ -106,16 +106,117 @@ class GradBucket:
             self.flat.div_(dist.get_world_size(group))
 
 
-class TrainStep:
-    """forward -> losses -> backward -> (DP: gradient all-reduce) -> AdamW step.
+class _StepBase:
+    """What the training steps of both model variants share: optimizer, gradient bucket and the engines' `direct_grads`,
+    the backward half of a step, the gradient exchange, and the eager -> capture -> replay sequence around a HIP graph.
+    A variant supplies `_fwd_bwd` (its forward and losses, ending in `_backward`) and, for graph mode, `_signature`,
+    `_static_target` and `_refill`."""
+
+    def __init__(self, model, optimizer, bucket, graph, reg):
+        self.model = model
+        self.reg = RegTerm.of(reg)
+        self.opt = optimizer or make_optimizer(model)
+        self.bucket = GradBucket(model.get_param_groups()[3]) if bucket else None
+        self.graph = bool(graph)
+        self._graphs = {}
+        self._pool = None
+        # the HIP head and the insert engine write their gradients straight into the views of THIS bucket (zeroed each step,
+        # each gradient written exactly once per backward; a .grad that lies elsewhere is accumulated through autograd as
+        # usual); a step without a bucket clears the opt-in
+        rng = None
+        if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
+            lo = self.bucket.flat.data_ptr()
+            rng = (lo, lo + 4 * self.bucket.flat.numel())
+        for owner in (getattr(model, "head_engine", None), getattr(model, "comer", None)):
+            if owner is not None:
+                owner.direct_grads = rng
+
+    def _reduce_grads(self):
+        """One exchange per step: mean of the trainable gradients over the data-parallel ranks."""
+        if self.bucket is not None:
+            return self.bucket.all_reduce_mean()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            # no flat bucket: reduce the gradients tensor by tensor (slower, same result) rather than let ranks diverge
+            world = dist.get_world_size()
+            for p in self.model.get_param_groups()[3]:
+                if p.grad is not None:
+                    dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)
+                    p.grad.div_(world)
+
+    def _backward(self, losses, img, seg, label, img_box, reg_active):
+        """The half of a step behind the variant's `losses` (total first): energy term of `seg` against `img` and the `label`
+        map, zeroed gradients, backward.  -> the detached scalars, total first, the energy last when `reg` is set."""
+        loss = losses[0]
+        if self.reg is not None:
+            loss, energy = self.reg.add(loss, img, seg, label, img_box, reg_active)
+            losses = (loss,) + tuple(losses[1:]) + (energy,)
+        if self.bucket is not None:
+            self.bucket.zero()
+        else:
+            self.opt.zero_grad()
+        loss.backward()
+        if img.is_cuda:      # backward nodes of a head that ran beside the CAM chain execute on the model's side stream
+            cur = torch.cuda.current_stream()
+            for s in getattr(self.model, "side_streams", lambda: [])():
+                cur.wait_stream(s)
+        return tuple(l.detach() for l in losses)
+
+    def __call__(self, img, target, img_box=None, names=None):
+        """One step on `img` and the variant's `target`; a step of one scalar returns it bare, any other a tuple."""
+        active = self.reg is not None and self.reg.begin_step()
+        if self.graph and target is not None and img.is_cuda and self.bucket is not None:
+            out = self._graphed(img, target, img_box, active)
+        else:
+            out = self._fwd_bwd(img, target, None, names, img_box, active)
+        self._reduce_grads()
+        self.opt.step()
+        return out[0] if len(out) == 1 else out
+
+    def _graphed(self, img, target, img_box, reg_active):
+        """HIP-graph replay: per batch signature the first step runs eagerly on the static buffers (it warms every lazy
+        initialisation), the second captures, every later one replays.  Whether the energy term is active is part of the
+        signature; `img_box` goes through a static (B, 4) buffer."""
+        m = self.model
+        sig = self._signature(img, target) + ((True,) if reg_active else ())
+        ent = self._graphs.get(sig)
+        first = ent is None
+        if first:
+            ent = self._graphs[sig] = {"graph": None, "img": torch.empty(img.shape, device=img.device, dtype=torch.float32),
+                                       "target": self._static_target(img, target),
+                                       "box": self.reg.box_buffer(img) if reg_active else None}
+        else:
+            self._refill(ent["target"], target)
+        ent["img"].copy_(img)
+        if reg_active:
+            self.reg.fill_box(ent["box"], img_box, img)
+        if first:
+            return self._fwd_bwd(ent["img"], target, ent["target"], None, ent["box"], reg_active)
+        if ent["graph"] is None:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            it = m.iter_num
+            # thread_local: other threads (RCCL's watchdog polling its events, the autograd workers allocating) must not
+            # abort the capture; the kernels the autograd workers launch on the capturing stream are captured all the same
+            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+                ent["out"] = torch.stack(self._fwd_bwd(ent["img"], target, ent["target"], None, ent["box"], reg_active))
+            m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
+            self._pool = self._pool or g.pool()
+            ent["graph"] = g
+        ent["graph"].replay()
+        m.iter_num += 1
+        return tuple(ent["out"].clone())     # the graph's pool memory is rewritten by the next replay
+
+
+class TrainStep(_StepBase):
+    """forward -> losses -> backward -> (DP: gradient all-reduce) -> AdamW step.  This class holds the weakly supervised
+    variant's forward, `losses` (the override point) and PairPlan statics; everything behind the losses is `_StepBase`.
 
     graph=True (CUDA tensors + explicit `labels` only): forward + losses + backward of a batch signature
     (image shape, number of (image, class) pairs, max classes per image, affinity branch) are captured once into a
     HIP graph and replayed from then on -- one graph launch instead of ~420 kernel launches through Python, which is
     what the step costs on the host otherwise (BENCH_r01: 9.8 ms of enqueue per 14.5 ms step).  Inputs are copied
     into static buffers (images; the pair index tensors via PairPlan.update); the gradient all-reduce and the
-    optimizer stay outside the graph (RCCL and the host-computed learning-rate schedule).  The first step of a new
-    signature runs eagerly (it also warms every lazy initialisation), the second captures.
+    optimizer stay outside the graph (RCCL and the host-computed learning-rate schedule).
 
     pad_plans (default on in graph mode): the signature is BUCKETED (clip_tool.PairPlan pad=True: pair count to a multiple
     of 8 with dropped dummy pairs, channel capacity K to the next even number), so batches whose images carry 1..5
@@ -125,30 +226,13 @@ class TrainStep:
     reg (default None: nothing changes): a `RegTerm` description.  The loss becomes seg_loss + 0.1 * attn_loss + coef * energy
     at step numbers > start_iter, energy = the dense energy loss of the up-sampled logits against the step's input image and
     pseudo labels inside `img_box` (an argument of the call: None = the whole image, or (B, 4) rows (y0, y1, x0, x1) on either
-    side); the step then returns a fourth value, the energy before `coef` (zero while the term is inactive).  Whether the term
-    is active is part of the graph signature, and img_box goes through a static buffer."""
+    side); the step then returns a fourth value, the energy before `coef` (zero while the term is inactive)."""
 
     def __init__(self, model, optimizer=None, radius=8, ignore_index=255, bucket=True, graph=False, pad_plans=True, reg=None):
-        self.model = model
-        self.reg = RegTerm.of(reg)
-        self.opt = optimizer or make_optimizer(model)
+        super().__init__(model, optimizer, bucket, graph, reg)
         self.radius, self.ignore = radius, ignore_index
         self._mask = {}
-        self.bucket = GradBucket(model.get_param_groups()[3]) if bucket else None
-        self.graph = bool(graph)
         self.pad_plans = bool(pad_plans)
-        self._graphs = {}
-        self._pool = None
-        # the HIP head and the insert engine write their gradients straight into the views of THIS bucket (zeroed each step,
-        # each gradient written exactly once per backward; a .grad that lies elsewhere is accumulated through autograd as
-        # usual); a TrainStep without a bucket clears the opt-in
-        rng = None
-        if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
-            lo = self.bucket.flat.data_ptr()
-            rng = (lo, lo + 4 * self.bucket.flat.numel())
-        for owner in (getattr(model, "head_engine", None), getattr(model, "comer", None)):
-            if owner is not None:
-                owner.direct_grads = rng
 
     def mask(self, h, w, device):
         key = (h, w, str(device))
@@ -168,93 +252,31 @@ class TrainStep:
             seg_loss = get_seg_loss(segs, cam.long(), ignore_index=self.ignore)
         return seg_loss + 0.1 * attn_loss, seg_loss, attn_loss
 
-    def _reduce_grads(self):
-        """One exchange per step: mean of the trainable gradients over the data-parallel ranks."""
-        if self.bucket is not None:
-            self.bucket.all_reduce_mean()
-            return
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            # no flat bucket: reduce the gradients tensor by tensor (slower, same result) rather than let ranks diverge
-            world = dist.get_world_size()
-            for p in self.model.get_param_groups()[3]:
-                if p.grad is not None:
-                    dist.all_reduce(p.grad, op=dist.ReduceOp.SUM)
-                    p.grad.div_(world)
-
-    def _fwd_bwd(self, img, names, labels, plan=None, img_box=None, reg_active=False):
+    def _fwd_bwd(self, img, labels, plan=None, names=None, img_box=None, reg_active=False):
         kw = {"plan": plan} if plan is not None else {}
         seg, cam, attn_pred = self.model(img, names if names is not None else [""] * img.shape[0], labels=labels, **kw)
-        loss, seg_loss, attn_loss = self.losses(seg, cam, attn_pred)
-        extra = ()
-        if self.reg is not None:
-            loss, energy = self.reg.add(loss, img, seg, cam, img_box, reg_active)
-            extra = (energy,)
-        if self.bucket is not None:
-            self.bucket.zero()
-        else:
-            self.opt.zero_grad()
-        loss.backward()
-        if img.is_cuda:      # backward nodes of a head that ran beside the CAM chain execute on the model's side stream
-            cur = torch.cuda.current_stream()
-            for s in getattr(self.model, "side_streams", lambda: [])():
-                cur.wait_stream(s)
-        return (loss.detach(), seg_loss.detach(), attn_loss.detach()) + extra
+        return self._backward(self.losses(seg, cam, attn_pred), img, seg, cam, img_box, reg_active)
 
     def __call__(self, img, names=None, labels=None, img_box=None):
-        active = self.reg is not None and self.reg.begin_step()
-        if self.graph and labels is not None and img.is_cuda and self.bucket is not None:
-            out = self._graphed(img, labels, img_box, active)
-        else:
-            out = self._fwd_bwd(img, names, labels, img_box=img_box, reg_active=active)
-        self._reduce_grads()
-        self.opt.step()
-        return out
+        return super().__call__(img, labels, img_box, names)
 
-    # ---------------------------------------------------------------------------------- HIP-graph replay
-    def _signature(self, img, labels, reg_active=False):
+    # ------------------------------------------------------------- graph mode: the signature, and a PairPlan as static target
+    def _signature(self, img, labels):
         from .clip.clip_tool import PairPlan
         m = self.model
         seg_trans = (m.iter_num + 1) > m.seg_trans_after
-        sig = (tuple(img.shape), PairPlan.signature(labels, self.pad_plans), bool(seg_trans), bool(m.training))
-        return sig + (True,) if reg_active else sig
+        return tuple(img.shape), PairPlan.signature(labels, self.pad_plans), bool(seg_trans), bool(m.training)
 
-    def _graphed(self, img, labels, img_box=None, reg_active=False):
+    def _static_target(self, img, labels):
         from .clip.clip_tool import PairPlan
         m = self.model
-        sig = self._signature(img, labels, reg_active)
-        ent = self._graphs.get(sig)
-        if ent is None:                      # first step of this signature: eager (warms lazy state), sets up the statics
-            ent = self._graphs[sig] = {"graph": None, "img": torch.empty_like(img, dtype=torch.float32).contiguous(),
-                                       "plan": PairPlan(labels, m.fg_text_features.shape[0], m.bg_text_features.shape[0],
-                                                        img.device, pad=self.pad_plans),
-                                       "box": self.reg.box_buffer(img) if reg_active else None}
-            ent["img"].copy_(img)
-            if reg_active:
-                self.reg.fill_box(ent["box"], img_box, img)
-            return self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"], img_box=ent["box"], reg_active=reg_active)
-        ent["img"].copy_(img)
-        ent["plan"].update(labels)
-        if reg_active:
-            self.reg.fill_box(ent["box"], img_box, img)
-        if ent["graph"] is None:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            it = m.iter_num
-            # thread_local: other threads (RCCL's watchdog polling its events, the autograd workers allocating) must not
-            # abort the capture; the kernels the autograd workers launch on the capturing stream are captured all the same
-            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                out = self._fwd_bwd(ent["img"], None, labels, plan=ent["plan"], img_box=ent["box"], reg_active=reg_active)
-                ent["out"] = torch.stack(out)
-            m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
-            self._pool = self._pool or g.pool()
-            ent["graph"] = g
-        ent["graph"].replay()
-        m.iter_num += 1
-        o = ent["out"].clone()               # the graph's pool memory is rewritten by the next replay
-        return tuple(o[i] for i in range(o.shape[0]))
+        return PairPlan(labels, m.fg_text_features.shape[0], m.bg_text_features.shape[0], img.device, pad=self.pad_plans)
+
+    def _refill(self, plan, labels):
+        plan.update(labels)
 
 
-class SupervisedTrainStep:
+class SupervisedTrainStep(_StepBase):
     """forward -> cross-entropy -> backward -> (DP: gradient all-reduce) -> AdamW step for the fully supervised variant
     (WeCLIP_model/model_attn_aff_voc_seg.py), whose labels are ground-truth masks.  The loss is
     F.cross_entropy(F.interpolate(seg, label.shape[1:], bilinear, align_corners=False), label, ignore_index): the
@@ -264,31 +286,16 @@ class SupervisedTrainStep:
     `step(img, label)`: img (B, 3, H, W) and label (B, Hl, Wl) integer device tensors the caller has prepared (any
     augmentation happens before); returns the detached loss.  graph=True (CUDA tensors, with a bucket): forward + loss +
     backward are captured once per (image shape, label shape, training flag) -- the first step of a signature runs eagerly,
-    the second captures -- and replayed from static input buffers; the all-reduce and the optimizer stay outside the graph,
-    as in TrainStep.
+    the second captures -- and replayed from static input buffers; the all-reduce and the optimizer stay outside the graph.
+    That sequence, like everything else behind `loss`, is `_StepBase`'s, the one TrainStep runs.
 
     reg (default None: nothing changes): a `RegTerm` description, as in TrainStep.  The loss becomes ce + coef * energy at step
     numbers > start_iter, with the ground-truth label and `img_box` (third argument of the call; None = the whole image); the
     step then returns (loss, energy before `coef`), the energy zero while the term is inactive."""
 
     def __init__(self, model, optimizer=None, ignore_index=255, bucket=True, graph=False, reg=None):
-        self.model = model
-        self.reg = RegTerm.of(reg)
-        self.opt = optimizer or make_optimizer(model)
+        super().__init__(model, optimizer, bucket, graph, reg)
         self.ignore = int(ignore_index)
-        self.bucket = GradBucket(model.get_param_groups()[3]) if bucket else None
-        self.graph = bool(graph)
-        self._graphs = {}
-        self._pool = None
-        rng = None
-        if self.bucket is not None and os.environ.get("WECLIP_DIRECT_GRADS", "1") != "0":
-            lo = self.bucket.flat.data_ptr()
-            rng = (lo, lo + 4 * self.bucket.flat.numel())
-        eng = getattr(model, "head_engine", None)
-        if eng is not None:
-            eng.direct_grads = rng
-
-    _reduce_grads = TrainStep._reduce_grads
 
     def loss(self, seg, label):
         if seg.is_cuda:
@@ -296,58 +303,19 @@ class SupervisedTrainStep:
         segs = F.interpolate(seg, size=label.shape[1:], mode="bilinear", align_corners=False)
         return F.cross_entropy(segs, label.long(), ignore_index=self.ignore)
 
-    def _fwd_bwd(self, img, label, img_box=None, reg_active=False):
+    def _fwd_bwd(self, img, label, static=None, names=None, img_box=None, reg_active=False):
+        label = label if static is None else static
         seg = self.model(img, mode="train")
-        loss = self.loss(seg, label)
-        if self.reg is not None:
-            loss, energy = self.reg.add(loss, img, seg, label, img_box, reg_active)
-        if self.bucket is not None:
-            self.bucket.zero()
-        else:
-            self.opt.zero_grad()
-        loss.backward()
-        return loss.detach() if self.reg is None else (loss.detach(), energy)
+        return self._backward((self.loss(seg, label),), img, seg, label, img_box, reg_active)
 
-    def __call__(self, img, label, img_box=None):
-        active = self.reg is not None and self.reg.begin_step()
-        if self.graph and img.is_cuda and self.bucket is not None:
-            out = self._graphed(img, label, img_box, active)
-        else:
-            out = self._fwd_bwd(img, label, img_box, active)
-        self._reduce_grads()
-        self.opt.step()
-        return out
+    step = _StepBase.__call__
 
-    step = __call__
+    # ------------------------------------------------------- graph mode: the signature, and an int64 label buffer as static target
+    def _signature(self, img, label):
+        return tuple(img.shape), tuple(label.shape), bool(self.model.training)
 
-    def _graphed(self, img, label, img_box=None, reg_active=False):
-        m = self.model
-        sig = (tuple(img.shape), tuple(label.shape), bool(m.training)) + ((True,) if reg_active else ())
-        ent = self._graphs.get(sig)
-        if ent is None:                      # first step of this signature: eager (warms lazy state), sets up the statics
-            ent = self._graphs[sig] = {"graph": None, "img": torch.empty(img.shape, device=img.device, dtype=torch.float32),
-                                       "label": torch.empty(label.shape, device=img.device, dtype=torch.int64),
-                                       "box": self.reg.box_buffer(img) if reg_active else None}
-            ent["img"].copy_(img)
-            ent["label"].copy_(label)
-            if reg_active:
-                self.reg.fill_box(ent["box"], img_box, img)
-            return self._fwd_bwd(ent["img"], ent["label"], ent["box"], reg_active)
-        ent["img"].copy_(img)
-        ent["label"].copy_(label)
-        if reg_active:
-            self.reg.fill_box(ent["box"], img_box, img)
-        if ent["graph"] is None:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            it = m.iter_num
-            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                out = self._fwd_bwd(ent["img"], ent["label"], ent["box"], reg_active)
-                ent["out"] = out if self.reg is None else torch.stack(out)
-            m.iter_num = it                  # the capture ran forward()'s counter once without executing a step
-            self._pool = self._pool or g.pool()
-            ent["graph"] = g
-        ent["graph"].replay()
-        m.iter_num += 1
-        o = ent["out"].clone()               # the graph's pool memory is rewritten by the next replay
-        return o if self.reg is None else (o[0], o[1])
+    def _static_target(self, img, label):
+        return torch.empty(label.shape, device=img.device, dtype=torch.int64).copy_(label)
+
+    def _refill(self, buf, label):
+        buf.copy_(label)
