@@ -748,11 +748,20 @@ int wc_cam_resize_f32(const float* cam, const int* sizes, const int64_t* offsets
  * wc_label_match_count: the pseudo_seg_mAcc of :274-277.  seg (B,C,Hs,Ws) f32, label (B,H,W) int64 (255 = ignore, which no
  *   arg-max equals).  counts int64[2] is OVERWRITTEN: counts[0] = #pixels with argmax_c bilinear(seg)[c] == label,
  *   counts[1] = B*H*W.  The entry zeroes counts on `stream` and launches one kernel: no allocation, no host read, so it may
- *   be called while `stream` is being captured into a HIP graph. */
+ *   be called while `stream` is being captured into a HIP graph.
+ * wc_step_pair_hist: the confusion counts of one supervised train step, wc_val_pair_hist's seg leg over a batch.  seg
+ *   (B,C,Hs,Ws) f32 low-resolution logits, label (B,H,W) int64 ground-truth masks.  Over the pixels with 0 <= label < nc:
+ *   hist[label*nc + p] += 1 with p = argmax_c bilinear(seg[b])[c] on the (H,W) grid (the arithmetic above).  Every other label
+ *   value (255, negative, >= nc) is skipped; p >= nc (C > nc) is skipped and sets flag[0].  hist (nc,nc) int64 is ADDED to and
+ *   never zeroed: the caller owns the window.  Integer atomics only (per-workgroup LDS histogram while nc*nc*4 <= 64 KiB,
+ *   global atomics otherwise; the counts of a wave's leading cell are summed across its lanes and added once), so the result
+ *   does not depend on their order.  One launch, no allocation, no host read: capturable into a HIP graph.  nc <= 4096. */
 int wc_val_pair_hist(const float* seg, const long* cam, const long* gt, long* seg_hist, long* cam_hist, int* flag, int C, int Hs,
                      int Ws, int Hl, int Wl, int nc, void* stream);
 int wc_label_match_count(const float* seg, const long* label, long* counts, int B, int C, int Hs, int Ws, int H, int W,
                          void* stream);
+int wc_step_pair_hist(const float* seg, const long* label, long* hist, int* flag, int B, int C, int Hs, int Ws, int H, int W,
+                      int nc, void* stream);
 
 /* ---- evaluation entry point: the per-image tail (csrc/evalfinish.hip) -------------------------- */
 /* wc_eval_finish: one evaluated image of test_msc_flip_voc.py:92-107 in one launch over the (Hl,Wl) label grid.

@@ -29,6 +29,8 @@ def _drop_derived_keys(state_dict, prefix, *args):
 
 class WeCLIP(nn.Module):
     fg_names, bg_names = "new_class_names", "BACKGROUND_CATEGORY"      # clip.clip_text lists of the text rows (:76-79)
+    val_runs_cam = False        # no CAM leg at all, and
+    val_logits_only = True      # forward takes no `labels` and returns the logits tensor alone (validate.Validator reads both)
 
     def __init__(self, num_classes=None, clip_model=None, embedding_dim=256, in_channels=512, dataset_root_path=None,
                  device="cuda", text_features=None):

@@ -371,6 +371,16 @@ class DeviceSegAugment:
         self.sel = sel
         return out, lab, box
 
+    @staticmethod
+    def img_box(draw, crop, start):
+        """`img_box` of random_crop (datasets/transforms.py:162-166) from one draw_one() tuple and the crop origin
+        (H_start, W_start) the device chose for it (`sel[b, :2]`), int32 like the kernel's: a host restatement for checks."""
+        import numpy as np
+        _, _, rh, rw, pad_y, pad_x = draw[:6]
+        cy, cx = int(start[0]), int(start[1])
+        return np.asarray([max(pad_y - cy, 0), min(cy + crop, pad_y + rh), max(pad_x - cx, 0), min(cx + crop, pad_x + rw)],
+                          dtype=np.int32)
+
     def check_ragged(self, rec, cand, sizes):
         """Host-side preconditions for host-resident records and a list of (H, W); -> canvas_max of the batch."""
         cm = self.crop

@@ -131,6 +131,7 @@ class DeviceLoader:
                                         ignore_index=dataset.ignore_index, seed=self.seed + self.rank)
         self.last_draws = None                                                # draw_one() tuples of the batch yielded last
         self.last_cls_labels = None                                           # its cls_labels once more, as a HOST array
+        self.last_img_box = None      # Seg, aug=True: its img_box (B,4) int32 {y0,y1,x0,x1} on the DEVICE; None for the other kinds
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -198,6 +199,7 @@ class DeviceLoader:
             return dev[a:b].view(dtype).view(*(shape or like.shape))
         names = [it[0] for it in items]
         tables = st["tables"]
+        box = None
         cls_labels = view(f"table{len(tables) - 1}", tables[-1]).clone()       # a copy: the slot's buffer will be reused
         src = dev[lay["images"][0]:lay["images"][1]]
         if not self.augment:
@@ -212,10 +214,11 @@ class DeviceLoader:
             out = (names, inputs, cls_labels, view("table1", tables[1]).clone())
         else:
             lab = dev[lay["labels"][0]:lay["labels"][1]]
-            inputs, labels, _ = self.aug.ragged(src, lab, view("offsets", torch.int64, B), view("sizes", torch.int32, B, 2),
+            inputs, labels, box = self.aug.ragged(src, lab, view("offsets", torch.int64, B), view("sizes", torch.int32, B, 2),
                                                 view("table0", torch.int32, B, 16),
                                                 view("table1", torch.int32, B, self.aug.n_cand, 2), st["canvas_max"])
             out = (names, inputs, labels, cls_labels)
+        self.last_img_box = box
         slot.consumed.record(cur)                                             # the reading kernel is enqueued: slot reusable
         self.last_draws, self.last_cls_labels = st["draws"], tables[-1]
         return out

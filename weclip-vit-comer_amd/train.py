@@ -2,7 +2,7 @@
 scripts/dist_clip_coco.py) around this package's graph-replayed step.
 
     python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
-        [--dataset voc|coco] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
+        [--dataset voc|coco|seg] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
         [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>]]
 
 The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
@@ -11,6 +11,11 @@ into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is c
 --reg_loss adds the dense energy (regularised) loss as a fourth scalar of the same accumulator (TrainStep(reg=...)).
 Under `python -m torch.distributed.run` every rank trains on its share of each epoch (DeviceLoader rank / world), gradients
 are averaged through `GradBucket`, every rank validates its share of the images, and rank 0 alone logs and saves.
+
+--dataset seg trains the fully supervised variant (WeCLIP_model/model_attn_aff_voc_seg.py) on VOC's ground-truth masks: the same
+YAML, `VOC12SegDataset(aug=True)` batches whose labels never visit the host, `LoggedSupervisedTrainStep`, and a log line of
+this package's own (the reference ships no training script for the variant): the window's mean cross-entropy and the pAcc /
+mAcc / mIoU of the window's confusion matrix, which `wc_step_pair_hist` (csrc/trainlog.hip) counts inside the captured step.
 
 Two optional keys extend the configuration, both under `clip_init`: `text_features` (a torch file holding {"bg", "fg"}: the
 zero-shot text rows, for a machine without the reference checkout that `--reference_root` names) and `comer` (bool).
@@ -28,12 +33,25 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .train_step import TrainStep, make_optimizer
+from .train_step import SupervisedTrainStep, TrainStep, make_optimizer
 
 LOG = logging.getLogger("weclip.train")
 LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, pseudo_seg_loss: %.4f, attn_loss: %.4f, pseudo_seg_mAcc: %.4f"   # :280
+SEG_LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, seg_loss: %.4f, seg_pAcc: %.4f, seg_mAcc: %.4f, seg_mIoU: %.4f"   # --dataset seg
 REG_FORMAT = ", reg_loss: %.4e"                         # appended with --reg_loss only
-SAVE_AFTER = {"voc": 26000, "coco": 40000}              # dist_clip_voc.py:288, dist_clip_coco.py:287
+
+
+class _SaveAfter(dict):
+    """First iteration past which checkpoints are written, per --dataset.  "seg" runs on VOC's YAML and has no entry of its
+    own: it reads VOC's, so the two cannot drift apart (and the table still lists exactly the reference's two scripts)."""
+
+    def __missing__(self, kind):
+        if kind == "seg":
+            return self["voc"]
+        raise KeyError(kind)
+
+
+SAVE_AFTER = _SaveAfter(voc=26000, coco=40000)          # dist_clip_voc.py:288, dist_clip_coco.py:287
 MODEL_FILE, STATE_FILE = "WeCLIP_model_iter_%d.pth", "train_state_iter_%d.pth"
 _SCI = re.compile(r"^[+-]?(\d+\.?\d*|\.\d+)[eE][+-]?\d+$")
 
@@ -80,15 +98,17 @@ def build_parser():
     p.add_argument("--config", type=str, required=True, help="the reference's YAML (configs/voc_attn_reg.yaml, coco_attn_reg.yaml)")
     p.add_argument("--seg_detach", action="store_true", help="accepted and ignored, as in the reference")
     p.add_argument("--work_dir", default=None, type=str)
-    p.add_argument("--radius", default=8, type=int)
+    p.add_argument("--radius", default=8, type=int, help="affinity radius (unused with --dataset seg)")
     p.add_argument("--crop_size", default=320, type=int)
-    p.add_argument("--dataset", choices=("voc", "coco"), default="voc")
+    p.add_argument("--dataset", choices=("voc", "coco", "seg"), default="voc",
+                   help="seg: the fully supervised variant on VOC's ground-truth masks (the word's meaning in msc_flip_eval)")
     p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
     p.add_argument("--graph", action=argparse.BooleanOptionalAction, default=True, help="HIP-graph replay of the step")
     p.add_argument("--threads", type=int, default=8, help="decode threads of the loaders")
     p.add_argument("--prefetch", type=int, default=2)
     p.add_argument("--max_iters", type=int, default=None, help="overrides train.max_iters")
-    p.add_argument("--save_after", type=int, default=None, help="checkpoints are written past this iteration (voc 26000, coco 40000)")
+    p.add_argument("--save_after", type=int, default=None,
+                   help="checkpoints are written past this iteration (voc and seg 26000, coco 40000)")
     p.add_argument("--resume", type=str, default=None, help="a WeCLIP_model_iter_N.pth; its train_state_iter_N.pth is loaded with it")
     p.add_argument("--reg_loss", action="store_true",
                    help="add the dense energy (regularised) loss to the step; its all-pairs filter costs about four plain steps at "
@@ -138,6 +158,28 @@ def log_record(n_iter, lr, host, steps):
     rec = {"iter": n_iter, "lr": lr, "seg_loss": host[1] / steps, "attn_loss": host[2] / steps, "pseudo_seg_mAcc": host[-2] / host[-1]}
     if len(host) == 6:
         rec["reg_loss"] = host[3] / steps
+    return rec
+
+
+def format_seg_log_line(n_iter, delta, eta, lr, seg_loss, pacc, macc, miou, reg_loss=None):
+    line = SEG_LOG_FORMAT % (n_iter, delta, eta, lr, seg_loss, pacc, macc, miou)
+    return line if reg_loss is None else line + REG_FORMAT % reg_loss
+
+
+def seg_log_record(n_iter, lr, host, steps, num_classes):
+    """The metrics.jsonl record of a window of `steps` supervised steps from the one host read: host = the window sums (loss,
+    seg_loss[, reg_loss with --reg_loss]) followed by the window's (nc, nc) confusion matrix, row-major.  pAcc / mAcc / miou
+    are `evaluate.scores_from_hist` of that matrix: scores of the WHOLE window, not of its last step as `pseudo_seg_mAcc` is."""
+    from .utils.evaluate import scores_from_hist
+    cells = int(num_classes) ** 2
+    sums = len(host) - cells
+    if sums not in (2, 3):
+        raise ValueError(f"seg_log_record: {len(host)} values are not 2 or 3 sums and a {num_classes} x {num_classes} matrix")
+    score = scores_from_hist(np.asarray(host[sums:], dtype=np.float64).reshape(num_classes, num_classes))
+    rec = {"iter": n_iter, "lr": lr, "seg_loss": host[1] / steps, "pAcc": float(score["pAcc"]), "mAcc": float(score["mAcc"]),
+           "miou": float(score["miou"])}
+    if sums == 3:
+        rec["reg_loss"] = host[2] / steps
     return rec
 
 
@@ -216,6 +258,34 @@ class LoggedTrainStep(TrainStep):
         return out
 
 
+class LoggedSupervisedTrainStep(SupervisedTrainStep):
+    """SupervisedTrainStep whose loss() also counts, on the device, the step's confusion matrix: `hist` (nc, nc) int64 gets
+    hist[label, arg-max of the up-sampled logits] += 1 over the pixels with 0 <= label < nc (255 borders and crop padding are
+    NOT in any denominator, unlike LoggedTrainStep's pixel count, which is right for pseudo labels only).  The step ADDS into
+    `hist`; whoever reads it zeroes it.  `ce` (a static scalar) holds the step's cross-entropy, which under `reg` is not
+    among the returned values.  Both launches sit between the parent's loss kernels and the backward, so in graph mode they
+    are part of the captured step; they read `seg.detach()` and `label` only, and the returned loss is the parent's."""
+
+    def __init__(self, model, *args, **kw):
+        super().__init__(model, *args, **kw)
+        dev = next(model.parameters()).device
+        nc = int(model.num_classes)
+        self.hist = torch.zeros(nc, nc, device=dev, dtype=torch.int64)
+        self.ce = torch.zeros((), device=dev, dtype=torch.float32)
+        self._flag = None
+        if dev.type == "cuda":
+            from .validate import _flag
+            self._flag = _flag(dev)                  # created here, not inside a capture
+
+    def loss(self, seg, label):
+        out = super().loss(seg, label)
+        if seg.is_cuda:
+            from .validate import step_pair_hist
+            self.ce.copy_(out.detach())
+            step_pair_hist(seg.detach().float().contiguous(), label.long().contiguous(), self.hist.shape[0], self.hist, self._flag)
+        return out
+
+
 # ---------------------------------------------------------------------------------------------- the driver
 def build_model(cfg, kind="voc", reference_root=None):
     """The WeCLIP of `cfg.clip_init` for `kind` ("voc", "coco", or "seg": the supervised variant) with its text rows.  Shared with
@@ -264,16 +334,21 @@ class Trainer:
         setup_seed(self.seed)
 
         ds = cfg.dataset
-        if self.kind == "voc":
+        if self.kind in ("voc", "seg"):
             from .datasets.voc import VOC12ClsDataset as ClsDataset, VOC12SegDataset as SegDataset
             val_stage = "train"                          # dist_clip_voc.py:162
         else:
             from .datasets.coco import CocoClsDataset as ClsDataset, CocoSegDataset as SegDataset
             val_stage = "val"                            # dist_clip_coco.py:163
-        self.train_dataset = ClsDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.train.split, stage="train",
-                                        aug=True, resize_range=ds.resize_range, rescale_range=ds.rescale_range,
-                                        crop_size=ds.crop_size, img_fliplr=True, ignore_index=ds.ignore_index,
-                                        num_classes=ds.num_classes)
+        if self.kind == "seg":                          # ground-truth masks, label-aware augmentation (DeviceSegAugment)
+            self.train_dataset = SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.train.split,
+                                            stage="train", aug=True, crop_size=ds.crop_size, img_fliplr=True,
+                                            ignore_index=ds.ignore_index, num_classes=ds.num_classes)
+        else:
+            self.train_dataset = ClsDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.train.split,
+                                            stage="train", aug=True, resize_range=ds.resize_range, rescale_range=ds.rescale_range,
+                                            crop_size=ds.crop_size, img_fliplr=True, ignore_index=ds.ignore_index,
+                                            num_classes=ds.num_classes)
         self.val_dataset = SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=cfg.val.split, stage=val_stage,
                                       aug=False, ignore_index=ds.ignore_index, num_classes=ds.num_classes)
         threads, prefetch = getattr(args, "threads", 8), getattr(args, "prefetch", 2)
@@ -292,12 +367,16 @@ class Trainer:
                                   betas=tuple(float(b) for b in opt.betas), warmup_iter=int(sch.warmup_iter),
                                   max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power))
         self.reg = reg_settings(cfg, args)
-        self.step = LoggedTrainStep(self.model, self.opt, radius=getattr(args, "radius", 8), ignore_index=ds.ignore_index,
-                                    graph=bool(getattr(args, "graph", True)), reg=self.reg)
+        if self.kind == "seg":
+            self.step = LoggedSupervisedTrainStep(self.model, self.opt, ignore_index=ds.ignore_index,
+                                                  graph=bool(getattr(args, "graph", True)), reg=self.reg)
+        else:
+            self.step = LoggedTrainStep(self.model, self.opt, radius=getattr(args, "radius", 8), ignore_index=ds.ignore_index,
+                                        graph=bool(getattr(args, "graph", True)), reg=self.reg)
         self.validator = Validator(self.model, ds.num_classes, self.rank, self.world)
         dev = next(self.model.parameters()).device
-        # window sums of (loss, seg_loss, attn_loss[, reg_loss with --reg_loss])
-        self.acc = torch.zeros(3 if self.reg is None else 4, device=dev, dtype=torch.float32)
+        # window sums of (loss, seg_loss, attn_loss[, reg_loss with --reg_loss]); seg: (loss, seg_loss[, reg_loss])
+        self.acc = torch.zeros((2 if self.kind == "seg" else 3) + (self.reg is not None), device=dev, dtype=torch.float32)
         self.window = 0                                                 # steps in the window (host)
         self.n_iter = 0
         self.time0 = datetime.datetime.now().replace(microsecond=0)
@@ -328,6 +407,8 @@ class Trainer:
 
     def step_once(self):
         """One training iteration -> the step's (loss, seg_loss, attn_loss[, reg_loss]) device scalars.  No host read."""
+        if self.kind == "seg":
+            return self._seg_step_once()
         from .datasets import labels_from_onehot
         _, inputs, _, img_box = self._next_batch()
         labels = labels_from_onehot(self.train_loader.last_cls_labels)      # the host copy: graph mode needs explicit labels
@@ -337,11 +418,45 @@ class Trainer:
         self.n_iter += 1
         return out
 
+    def _seg_step_once(self):
+        """--dataset seg: (inputs, labels) of the batch go straight to the step, the labels stay on the device; with
+        --reg_loss the batch's img_box (DeviceLoader.last_img_box, a device tensor) goes with them."""
+        _, inputs, labels, _ = self._next_batch()
+        if self.reg is None:
+            out = (self.step(inputs, labels),)
+        else:
+            out = self.step(inputs, labels, self.train_loader.last_img_box)
+        self.acc.add_(torch.stack((out[0], self.step.ce) + tuple(out[1:])))
+        self.window += 1
+        self.n_iter += 1
+        return out
+
+    def _seg_log(self):
+        """--dataset seg: the window's loss sums and its confusion matrix in ONE device-to-host read; the matrix is then
+        zeroed on the stream.  pAcc / mAcc / mIoU are those of the whole window (seg_log_record)."""
+        hist = self.step.hist
+        host = torch.cat([self.acc.double(), hist.flatten().double()]).cpu().tolist() if self.rank == 0 else None
+        self.acc.zero_()
+        hist.zero_()
+        steps, self.window = self.window, 0
+        if host is None:
+            return None
+        rec = seg_log_record(self.n_iter, self.opt.param_groups[0]["lr"], host, steps, hist.shape[0])
+        delta, eta = cal_eta(self.time0, max(self.n_iter, 1), self.max_iters)
+        LOG.info(format_seg_log_line(rec["iter"], delta, eta, rec["lr"], rec["seg_loss"], rec["pAcc"], rec["mAcc"], rec["miou"],
+                                     rec.get("reg_loss")))
+        append_metrics(self.metrics_path, rec)
+        if self.writer is not None:
+            self.writer.add_scalars("train/loss", {"seg_loss": rec["seg_loss"]}, global_step=self.n_iter)
+        return rec
+
     def log(self):
         """The log line of :269-282 for the window since the last call: ONE device-to-host read (loss sums + counts).
         pseudo_seg_mAcc is the LAST step's, as the reference's.  Needs at least one step since the last call."""
         if self.window == 0:
             raise RuntimeError("Trainer.log: no step since the last log line (there is no window to average)")
+        if self.kind == "seg":
+            return self._seg_log()
         host = torch.cat([self.acc.double(), self.step.counts.double()]).cpu().tolist() if self.rank == 0 else None
         self.acc.zero_()
         steps, self.window = self.window, 0
@@ -364,8 +479,9 @@ class Trainer:
         seg_score, cam_score = self.validator.run(self.val_loader)
         self.model.iter_num = before + len(self.val_dataset)
         if self.rank == 0:
-            LOG.info("cams score:")
-            LOG.info(cam_score)
+            if self.kind != "seg":                       # the supervised variant has no CAM leg: cam_score is None
+                LOG.info("cams score:")
+                LOG.info(cam_score)
             LOG.info("segs score:")
             LOG.info(seg_score)
             brief = lambda s: None if s is None else {k: float(s[k]) for k in ("pAcc", "mAcc", "miou")}      # noqa: E731

@@ -60,9 +60,30 @@ def label_match_count(seg, label, counts=None):
     return counts
 
 
+def step_pair_hist(seg, label, num_classes, hist, flag=None):
+    """seg (B,C,Hs,Ws) f32 logits of a train step, label (B,H,W) int64 ground-truth masks; ADDS into hist (nc,nc) int64:
+    hist[label, argmax_c bilinear(seg[b])[c]] += 1 over the pixels with 0 <= label < nc (255 and any other value are skipped).
+    A prediction outside [0, nc) is skipped and raises `flag` (default: the flag of `evaluate.check_predictions_in_range`).
+    One launch of `wc_step_pair_hist` on the current stream, no host read: it may run inside a graph capture."""
+    L.require_gpu()
+    B, C, Hs, Ws = seg.shape
+    if label.dim() != 3 or label.shape[0] != B:
+        raise RuntimeError("step_pair_hist: label must be (B, H, W) with seg's batch size")
+    if tuple(hist.shape) != (int(num_classes), int(num_classes)):
+        raise RuntimeError("step_pair_hist: hist must be (num_classes, num_classes)")
+    if flag is None:
+        flag = _flag(seg.device)
+    L.lib().wc_step_pair_hist(L.ptr(seg, F32, "seg"), L.ptr(label, torch.int64, "label"), L.ptr(hist, torch.int64, "hist"),
+                              L.ptr(flag, torch.int32, "flag"), B, C, Hs, Ws, label.shape[1], label.shape[2], int(num_classes),
+                              L.stream())
+    return hist
+
+
 class Validator:
-    """model: WeCLIP (VOC or COCO) on the GPU.  rank / world: this process's share of the images under data parallelism
-    (`msc_flip.shard`: images rank, rank + world, ...; replicas only, ONE all-reduce of the histograms at the end)."""
+    """model: WeCLIP (VOC, COCO or the seg-only supervised variant) on the GPU.  rank / world: this process's share of the
+    images under data parallelism (`msc_flip.shard`: images rank, rank + world, ...; replicas only, ONE all-reduce of the
+    histograms at the end).  A model whose class says `val_logits_only = True` (model_attn_aff_voc_seg.py) is called as
+    `model(inputs, mode="val")` and returns the logits alone: no CAM leg, `cam_score` None."""
 
     def __init__(self, model, num_classes, rank=0, world=1):
         L.require_gpu()
@@ -75,15 +96,20 @@ class Validator:
         self.cam_hist = torch.zeros(self.nc, self.nc, device=self.device, dtype=torch.int64)
         # the CAM leg: known from the model where it says so (a rank whose share is empty must agree with the others)
         self.has_cam = bool(getattr(self.model, "val_runs_cam", False))
+        # the seg-only model: `model(inputs, mode="val")` -> the logits alone (a class attribute, so every rank agrees)
+        self.logits_only = bool(getattr(self.model, "val_logits_only", False))
         self.images = 0
         self.seg_hist_host = self.cam_hist_host = None    # the summed histograms on the host, once finish() has read them
 
     @torch.no_grad()
     def add(self, inputs, labels, class_ids):
         """One image: inputs (1,3,H,W) normalised pixels, labels (1,Hl,Wl) integer class map (255 = ignore), class_ids the
-        image's class ids (what the CAM leg of the VOC model builds its channels from)."""
-        out = self.model(inputs, [""], mode="val", labels=[list(class_ids)])
-        seg, cam = out[0], out[1]
+        image's class ids (what the CAM leg of the VOC model builds its channels from; unused by a logits-only model)."""
+        if self.logits_only:
+            seg, cam = self.model(inputs, mode="val"), None
+        else:
+            out = self.model(inputs, [""], mode="val", labels=[list(class_ids)])
+            seg, cam = out[0], out[1]
         gt = labels[0].to(self.device).long().contiguous()
         if cam is not None:
             cam = (cam[0] if isinstance(cam, (list, tuple)) else cam.reshape(cam.shape[-2:])).long().contiguous()
