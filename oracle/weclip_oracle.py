@@ -280,7 +280,7 @@ def par_affinity(img, dilations=PAR_DILATIONS, w1=0.3, w2=0.01):
     std = nb.std(dim=1, keepdim=True)                          # unbiased, :77
     e = -(((nb - img[0][:, None]).abs() / (std + 1e-8) / w1) ** 2)
     e = e.mean(0)                                              # mean over channels :81
-    pos = torch.tensor(pos, dtype=torch.float32)
+    pos = torch.tensor(pos, dtype=img.dtype if img.dtype == torch.float64 else torch.float32)
     pe = -((pos / (pos.std() + 1e-8) / w1) ** 2)               # :78,83
     return torch.softmax(e, 0) + w2 * torch.softmax(pe, 0)[:, None, None]
 
@@ -305,9 +305,10 @@ def par_iterate(aff, masks, num_iter=20, dilations=PAR_DILATIONS):
 
 def par(img, masks, num_iter=20, dilations=PAR_DILATIONS):
     """PAR.forward, WeCLIP_model/PAR.py:64-92.  img (1,3,Hi,Wi), masks (1,C,H,W)."""
-    img = F.interpolate(img.float(), size=masks.shape[-2:], mode="bilinear", align_corners=True)
+    f = (lambda t: t) if img.dtype == masks.dtype == torch.float64 else (lambda t: t.float())   # fp64 in: an fp64 evaluation
+    img = F.interpolate(f(img), size=masks.shape[-2:], mode="bilinear", align_corners=True)
     aff = par_affinity(img, dilations)
-    return par_iterate(aff, masks[0].float(), num_iter, dilations)[None]
+    return par_iterate(aff, f(masks[0]), num_iter, dilations)[None]
 
 
 # ----------------------------------------------------------------------------- A.9

@@ -352,7 +352,7 @@ __global__ __launch_bounds__(256) void par_labels_kernel(const float* __restrict
 }
 
 static int build_taps(ParTaps* tp, const int* dilations, int n_dil, float w1, float w2) {
-    if (n_dil < 1 || n_dil * 8 > PAR_MAX_TAPS) return 1;
+    if (!dilations || n_dil < 1 || n_dil * 8 > PAR_MAX_TAPS) return 1;
     static const int DY[8] = {-1, -1, -1, 0, 0, 1, 1, 1};   // get_kernel() order, PAR.py:10-24
     static const int DX[8] = {-1, 0, 1, -1, 1, -1, 0, 1};
     const int T = n_dil * 8;
@@ -434,7 +434,7 @@ static int launch_iter(const float* aff, const float* src, float* dst, int B, in
 
 extern "C" int wc_par_iterate(const float* aff, const float* masks_in, float* masks_out, int B, int C,
                               int H, int W, const int* dilations, int n_dil, void* stream) {
-    WC_CHECK_ARG(aff && masks_in && masks_out && masks_in != masks_out && B > 0 && C > 0,
+    WC_CHECK_ARG(aff && masks_in && masks_out && masks_in != masks_out && B > 0 && C > 0 && H > 0 && W > 0,
                  "wc_par_iterate: bad argument (in-place not allowed)");
     ParTaps tp;
     WC_CHECK_ARG(build_taps(&tp, dilations, n_dil, 0.3f, 0.01f) == 0, "wc_par_iterate: 1..8 dilations");
@@ -494,7 +494,7 @@ static int par_forward_impl(const float* img, const float* masks, float* out, fl
 
 extern "C" int wc_par_labels(const float* masks, const int64_t* valid_key, const int* nch,
                              int64_t* labels, int B, int C, int H, int W, void* stream) {
-    WC_CHECK_ARG(masks && valid_key && labels && B > 0 && C > 0, "wc_par_labels: bad argument");
+    WC_CHECK_ARG(masks && valid_key && labels && B > 0 && C > 0 && H > 0 && W > 0, "wc_par_labels: bad argument");
     const long HW = (long)H * W;
     dim3 grid(wc_cdiv(HW, 256), B);
     hipLaunchKernelGGL(par_labels_kernel, grid, dim3(256), 0, (hipStream_t)stream, masks,
