@@ -262,14 +262,18 @@ int wc_convert_weights(const int64_t* table, int count, int blocks_per_tensor, v
 /* One AdamW step over many fp32 parameter tensors in one launch (reference utils/optimizer.py:3-33: torch.optim.AdamW
  * with the poly-warm-up lr written per group).  table (device): count rows of 8 int64 {param, grad, exp_avg, exp_avg_sq,
  * numel, 0, 0, 0}.  p *= 1 - lr*wd; m = lerp(m, g, 1-b1); v = v*b2 + (1-b2) g^2; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
- * with bias_correction{1,2} = 1 - beta^step (the update order of torch._multi_tensor_adam). */
+ * with bias_correction{1,2} = 1 - beta^step > 0 (the update order of torch._multi_tensor_adam).  0 < count <= 65535 (also for
+ * wc_convert_weights), blocks_per_tensor > 0.  A tensor with numel % 4 == 0 whose four pointers are 16-byte aligned is walked
+ * with 16-byte accesses, any other one element by element: the arithmetic is the same. */
 int wc_adamw_multi(const int64_t* table, int count, double lr, double beta1, double beta2, double eps,
                    double weight_decay, double bias_correction1, double bias_correction2, int blocks_per_tensor,
                    void* stream);
 
 /* ---- LayerNorm ------------------------------------------------------------------------ */
 /* clip/model.py:177-183 (`LayerNorm.forward`, fp32 math).  x (rows, D) f32 with row stride ldx;
- * outputs (each optional): y32 f32, y16 fp16 hi, y16lo fp16 residual; all dense (rows, D). */
+ * outputs (each optional, at least one of y32 / y16; y16lo only with y16): y32 f32, y16 fp16 hi, y16lo fp16 residual; all dense
+ * (rows, D).  D % 4 == 0, D <= 4096, ldx >= D, ldx % 4 == 0 (WC_ERR_ARG otherwise).  The kernels use 16-byte (fp16: 8-byte)
+ * accesses: keep every buffer aligned to that (not checked). */
 int wc_layernorm(const float* x, long ldx, const float* w, const float* b, float eps, float* y32,
                  void* y16, void* y16lo, long rows, int D, void* stream);
 
@@ -378,10 +382,15 @@ int wc_cam_upsample(const float* R, const int* nk, float* stats, float* cams, in
  * model_attn_aff_voc.py:134-137 (all run by torch.autograd in the reference).
  * wc_transpose_f16:  out[c, b*oR + r] = fp16(scale*src[b,r,c]) (hi[,lo]); src f32 or f16 (src_f32),
  *                    row stride ld, batch stride sSrc; out row stride ldo: operands of dW = dY^T X.
- * wc_colsum:         out[c] = alpha * sum_r src[r,c] (bias gradients); part: ceil(R/256)*C f32.
- * wc_layernorm_bwd:  dx = add + LN_bwd(dy; x, w) as f32 and/or fp16(dx*out_scale);
- *                    dgb (2,D) = alpha*[sum dy*xhat ; sum dy]; part: ceil(rows/16)*2*D f32.
- * wc_sigmoid_gram_bwd: S[b] = scale*(Z + Z^T), Z = dAP*AP*(1-AP) (fp16 hi[,lo], row stride ldo) so dF = S F.
+ *                    ld >= C, oR >= R, ldo >= (batch-1)*oR + R, batch <= 65535; the columns of out that no (b, r) maps to are
+ *                    left untouched (keep them zero).
+ * wc_colsum:         out[c] = alpha * sum_r src[r,c] (bias gradients), rounded through fp16 if round16; src f32 or f16
+ *                    (src_f32), row stride ld >= C; part: ceil(R/256)*C f32; R <= 256*65535.
+ * wc_layernorm_bwd:  dx = add (may be NULL) + LN_bwd(dy; x, w) as f32 and/or fp16(dx*out_scale) (at least one of dx32 / dx16);
+ *                    dgb (2,D) = alpha*[sum dy*xhat ; sum dy]; part: ceil(rows/16)*2*D f32.  D % 4 == 0, D <= 1024; dy, x, w,
+ *                    add, dx32 16-byte aligned, dx16 (and dy16 of wc_layernorm_bwd_h) 8-byte (WC_ERR_ARG otherwise).
+ * wc_sigmoid_gram_bwd: S[b] = scale*(Z + Z^T), Z = dAP*AP*(1-AP) (fp16 hi[,lo], row stride ldo >= n; columns [n, ldo) are left
+ *                    untouched) so dF = S F.  n <= 65535.
  * wc_colscale_split: y = alpha * x * cs[row / rows_per_batch, col] (cs may be NULL) -> f32 (optional), fp16 hi[,lo]. */
 /* wc_attn_bwd: backward of clip/myAtt.py:21-64 without storing L x L tensors: from the packed qkv
  * (q pre-scaled), dO (B*L,E) fp16, o32, lse -> dqkv (B*L,3E) fp16 hi (+lo, may be NULL), gradients
@@ -403,8 +412,9 @@ int wc_layernorm_bwd_h(const void* dy16, const float* x, const float* w, const f
                        long rows, int D, void* stream);
 /* two LayerNorms of ONE input x (the ViT-CoMer CTI normalises c1 once for the values of one deformable attention and once
  * for the queries of the other: this package's own WeCLIP_model/comer.py CTI.forward; no reference code) back-propagated in one
- * pass: dx = LN_bwd_a(dya16) + LN_bwd_b(dyb16) [+ add]; dgba / dgbb (2, D) = alpha * [dgamma; dbeta] of each; D <= 256;
- * part: >= min(ceil(rows / 16), 2048) * 4 * D floats */
+ * pass: dx = LN_bwd_a(dya16) + LN_bwd_b(dyb16) [+ add]; dgba / dgbb (2, D) = alpha * [dgamma; dbeta] of each; D % 4 == 0,
+ * D <= 256; part: >= min(ceil(rows / 16), 2048) * 4 * D floats; alignment as for wc_layernorm_bwd_h (wa, wb 16-byte, dya16,
+ * dyb16 8-byte) */
 int wc_layernorm_bwd2_h(const void* dya16, const float* wa, const void* dyb16, const float* wb, const float* x,
                         const float* add, float eps, float* dx32, void* dx16, float out_scale, float* part, float* dgba,
                         float* dgbb, float alpha, long rows, int D, void* stream);

@@ -339,17 +339,22 @@ def _forward(so, fn, **kw):
                            a["n_dil"], a["num_iter"], a["group"], None)
 
 
+def _kwid(kw):
+    """str(kw) with a ctypes array shown by its values (its repr holds an address: a test id that changes from run to run)."""
+    return str({k: list(v) if isinstance(v, ctypes.Array) else v for k, v in kw.items()})
+
+
 _SIZES = [dict(B=0), dict(B=-1), dict(H=0), dict(W=0), dict(H=-3)]
 _DILS = [dict(n_dil=0), dict(n_dil=9, dil=D9), dict(n_dil=-1), dict(dil=None)]
 
 
-@pytest.mark.parametrize("kw", _SIZES + _DILS + [dict(img=None), dict(aff=None)], ids=str)
+@pytest.mark.parametrize("kw", _SIZES + _DILS + [dict(img=None), dict(aff=None)], ids=_kwid)
 def test_par_affinity_refusals(so, kw):
     assert _affinity(so, **kw) == WC_ERR_ARG
 
 
 @pytest.mark.parametrize("kw", _SIZES + _DILS + [dict(C=0), dict(aff=None), dict(src=None), dict(dst=None),
-                                                 dict(dst=_P(1))], ids=str)
+                                                 dict(dst=_P(1))], ids=_kwid)
 def test_par_iterate_refusals(so, kw):
     assert _iterate(so, **kw) == WC_ERR_ARG
 
@@ -357,7 +362,7 @@ def test_par_iterate_refusals(so, kw):
 @pytest.mark.parametrize("fn", ["wc_par_forward", "wc_par_forward_h"])
 @pytest.mark.parametrize("kw", _SIZES + _DILS + [
     dict(C=0), dict(num_iter=0), dict(num_iter=-1), dict(group=0), dict(group=-2), dict(out=_P(1)), dict(tmp=_P(1)),
-    dict(out=_P(3)), dict(img=None), dict(masks=None), dict(out=None), dict(tmp=None), dict(aff_ws=None)], ids=str)
+    dict(out=_P(3)), dict(img=None), dict(masks=None), dict(out=None), dict(tmp=None), dict(aff_ws=None)], ids=_kwid)
 def test_par_forward_refusals(so, fn, kw):
     assert _forward(so, fn, **kw) == WC_ERR_ARG
 
