@@ -839,6 +839,42 @@ int wc_box_gather(const float* cams, const float* images, const int* meta, float
 int wc_box_scatter(const float* src, const int* meta, float* out, int G, int B, int C, int H, int W, int hb, int wb, int Kg,
                    void* stream);
 
+/* ---- training image panels of utils/imutils.py (csrc/panels.hip) ------------------------------ */
+/* Every entry paints B tiles of (H,W) pixels straight into `out`, a (3,canvas_h,canvas_w) uint8 CHW canvas that the caller has
+ * zeroed: the grid of `torchvision.utils.make_grid(nrow, padding=2, pad_value=0)` (utils/imutils.py:30,38,49,83,131) without a
+ * grid pass.  Tile k0 + i (i = 0..B-1, k = k0 + i) has its first pixel at
+ *   (oy + (k / xmaps) * (H + pad), ox + (k % xmaps) * (W + pad)),   with colmajor != 0 at
+ *   (oy + (k % xmaps) * (H + pad), ox + (k / xmaps) * (W + pad)):   tiles run down the columns first, the net effect of the two
+ * transposes of tensorboard_attn (:79 `permute([0,3,2,1])`, :83 `.permute(0,2,1)`).  Only the tiles' bytes are written.  Each
+ * entry checks that every tile lies inside the canvas and returns WC_ERR_ARG with nothing launched otherwise; no entry
+ * allocates or reads device memory on the host.  A float becomes a uint8 by truncation toward zero (`.type(torch.uint8)`).
+ * mean3 / std3: HOST arrays of 3 floats.
+ * wc_panel_images: utils/imutils.py:11-18 (`denormalize_img`) + :30.  img (B,3,H,W) f32; pixel = uint8(x * std + mean), the
+ *   product and the sum rounded separately in fp32.
+ * wc_panel_labels: utils/imutils.py:7-9 (`encode_cmap`) + :125-133 (`tensorboard_label`).  label (B,H,W) int64 (is_u8 = 0; taken
+ *   modulo 256) or uint8 (is_u8 = 1) -> the PASCAL VOC colour of :136-154, 255 -> (224,224,192).
+ * wc_panel_heat: the heat-map tiles of utils/imutils.py:32-38 (`tensorboard_image`'s overlay), :44-47 (`tensorboard_edge`) and
+ *   :59-79 (`tensorboard_attn`).  Image b's source is C maps of (h,w) f32 at src + b * sB + c * sC (elements).  Per pixel:
+ *   bilinear up-sampling to (H,W) (aligned = 0: align_corners=False, scale = in / out; aligned = 1: align_corners=True), the
+ *   maximum over the C maps (a NaN wins), then with minmax != NULL (device workspace of 3 * B floats, written by a reduction
+ *   launch of this entry) x = (x - min_b) / (max_b - min_b) over image b's up-sampled map (:71-76; a constant map gives 0 / 0),
+ *   then matplotlib's look-up of cmap (0 jet, 1 viridis): entry int(x * 256), x == 1 -> 255, x < 0 -> 0, x > 1 -> 255, NaN ->
+ *   (0,0,0).  img == NULL: pixel = uint8(lut * 255) (fp64).  img (B,3,H,W) f32: pixel = uint8(0.5 * lut * 255 + 0.5 * u), u =
+ *   wc_panel_images' pixel, in fp64 (:37).
+ * wc_panel_snapshot: what a later render of a train step needs, copied out of the step's memory in ONE launch (no allocation,
+ *   no memset, no host read: capturable into a HIP graph).  seg_out[0..n_seg) = seg; label_out[0..n_label) uint8 = the low
+ *   byte of label (int64; torch's cast); with attn (B,hw,hw) f32 != NULL: rows_out (B,4,hw) = attn[b, rows4[q], :], rows4 a
+ *   HOST array of the 4 rows tensorboard_attn reads (:64).  label 16-byte, label_out 4-byte aligned. */
+int wc_panel_images(const float* img, const float* mean3, const float* std3, int B, int H, int W, void* out, int canvas_h,
+                    int canvas_w, int oy, int ox, int xmaps, int pad, int colmajor, int k0, void* stream);
+int wc_panel_labels(const void* label, int is_u8, int B, int H, int W, void* out, int canvas_h, int canvas_w, int oy, int ox,
+                    int xmaps, int pad, int colmajor, int k0, void* stream);
+int wc_panel_heat(const float* src, long sB, long sC, int C, int h, int w, int aligned, float* minmax, int cmap,
+                  const float* img, const float* mean3, const float* std3, int B, int H, int W, void* out, int canvas_h,
+                  int canvas_w, int oy, int ox, int xmaps, int pad, int colmajor, int k0, void* stream);
+int wc_panel_snapshot(const float* seg, long n_seg, const long* label, long n_label, const float* attn, int B, int hw,
+                      const int* rows4, float* seg_out, void* label_out, float* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

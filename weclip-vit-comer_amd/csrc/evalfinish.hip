@@ -9,22 +9,10 @@
 //   label_finish_kernel : the same outputs for a ready int64 arg-max map (the CRF leg)                               (:158-161)
 // Bilinear arithmetic (so each arg-max is resize_argmax_kernel's) and the histogram skeleton: resample.h.  Flag contract =
 // confusion_hist_kernel's.
-// The colour of label v is the PASCAL VOC bit-interleaved map: bit j of v (j = 0..7) goes to bit 7 - j/3 of channel j % 3.
+// The colour of label v is the PASCAL VOC bit-interleaved map, ef_colour of voc_colour.h (shared with panels.hip).
 #include "common.h"
 #include "resample.h"
-
-// (r, g, b) of label v packed as r | g << 8 | b << 16 (utils/imutils.py:142-151)
-__device__ __forceinline__ unsigned int ef_colour(unsigned int v) {
-    unsigned int r = 0, g = 0, b = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        r |= ((v >> 0) & 1u) << (7 - j);
-        g |= ((v >> 1) & 1u) << (7 - j);
-        b |= ((v >> 2) & 1u) << (7 - j);
-        v >>= 3;
-    }
-    return r | (g << 8) | (b << 16);
-}
+#include "voc_colour.h"
 
 // 4 labels -> the uint8 map and the RGB image at pixels [i, i + n) of a row-major grid.  Full groups whose first pixel is
 // 4-byte aligned in the output go out as one 32-bit and three 32-bit vector stores (neighbouring lanes write neighbouring words),

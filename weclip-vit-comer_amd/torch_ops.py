@@ -444,6 +444,56 @@ def _(aff, cams, mask, cls, bkg_score, with_bkg):
     return cams.new_empty((cams.shape[0], cams.shape[1] + (1 if with_bkg else 0), cams.shape[2]), dtype=F32)
 
 
+@torch.library.custom_op(f"{_LIB}::panel_images", mutates_args=(), device_types="cuda")
+def panel_images(imgs: Tensor, cam: Tensor) -> Tuple[Tensor, Tensor]:
+    """tensorboard_image (reference utils/imutils.py:26-40; csrc/panels.hip): imgs (B,3,H,W) normalised, cam (B,C,h,w) -> the
+    nrow=2 grids of the de-normalised images and of their jet overlay with max_c bilinear(cam), uint8 CHW."""
+    from .utils import panels
+    return panels.tensorboard_image(imgs, cam)
+
+
+@panel_images.register_fake
+def _(imgs, cam):
+    from .utils.panels import grid_geometry
+    g = grid_geometry(imgs.shape[0], imgs.shape[2], imgs.shape[3], 2)
+    return (imgs.new_empty((3, g.canvas_h, g.canvas_w), dtype=torch.uint8), imgs.new_empty((3, g.canvas_h, g.canvas_w), dtype=torch.uint8))
+
+
+@torch.library.custom_op(f"{_LIB}::panel_labels", mutates_args=(), device_types="cuda")
+def panel_labels(labels: Tensor) -> Tensor:
+    """tensorboard_label (reference utils/imutils.py:125-133; csrc/panels.hip): labels (B,H,W) int64 / uint8 -> the nrow=2 grid of
+    their PASCAL VOC colours, uint8 CHW (B = 1: the bare (3,H,W) image)."""
+    from .utils import panels
+    if labels.dim() != 3:
+        raise RuntimeError("panel_labels: labels must be (B, H, W)")
+    geo = panels.grid_geometry(labels.shape[0], labels.shape[1], labels.shape[2], 2)
+    lab = labels if labels.dtype in (torch.int64, torch.uint8) else labels.long()
+    return panels.paint_labels(lab.contiguous(), panels._canvas(geo, labels.device), geo)
+
+
+@panel_labels.register_fake
+def _(labels):
+    from .utils.panels import grid_geometry
+    g = grid_geometry(labels.shape[0], labels.shape[1], labels.shape[2], 2)
+    return labels.new_empty((3, g.canvas_h, g.canvas_w), dtype=torch.uint8)
+
+
+@torch.library.custom_op(f"{_LIB}::panel_attn", mutates_args=(), device_types="cuda")
+def panel_attn(attns: List[Tensor], size: List[int], n_pix: float, n_row: int) -> Tensor:
+    """tensorboard_attn (reference utils/imutils.py:54-85; csrc/panels.hip): a list of (b,hw,hw) maps -> the viridis grid of
+    their rows int(h * n_pix) * (w + 1), up-sampled (align_corners=True) to `size` and min-max normalised per image."""
+    from .utils import panels
+    return panels.tensorboard_attn(attns, size=list(size), n_pix=n_pix, n_row=n_row)
+
+
+@panel_attn.register_fake
+def _(attns, size, n_pix, n_row):
+    from .utils.panels import grid_geometry
+    g = grid_geometry(sum(a.shape[0] for a in attns), size[0], size[1], n_row, colmajor=True)
+    return attns[0].new_empty((3, g.canvas_h, g.canvas_w), dtype=torch.uint8)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
-       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate")
+       "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
+       "panel_images", "panel_labels", "panel_attn")

@@ -3,7 +3,7 @@ scripts/dist_clip_coco.py) around this package's graph-replayed step.
 
     python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
         [--dataset voc|coco|seg] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
-        [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>]]
+        [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>]] [--panel_iters N]
 
 The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
 into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is counted by `wc_label_match_count`
@@ -16,6 +16,13 @@ are averaged through `GradBucket`, every rank validates its share of the images,
 YAML, `VOC12SegDataset(aug=True)` batches whose labels never visit the host, `LoggedSupervisedTrainStep`, and a log line of
 this package's own (the reference ships no training script for the variant): the window's mean cross-entropy and the pAcc /
 mAcc / mIoU of the window's confusion matrix, which `wc_step_pair_hist` (csrc/trainlog.hip) counts inside the captured step.
+
+--panel_iters N (default 0: off) makes rank 0 render the reference's tensorboard image panels (utils/imutils.py; here
+utils/panels.py, csrc/panels.hip) after iterations N, 2N, ...: `images`, `pseudo_label` (`gt_label` with --dataset seg),
+`prediction`, `seg_conf` and, for the weakly supervised variants, `attn_pred_0..3`, written as <work_dir>/panels/iter_<n>_<name>.png
+by writer threads (`PanelWriter`) and handed to tensorboard where it imports.  The step then snapshots its logits, label map and
+four attn_pred rows inside the captured graph (`wc_panel_snapshot`); the render runs outside it, on panel iterations only, with
+no forward and no host read.
 
 Two optional keys extend the configuration, both under `clip_init`: `text_features` (a torch file holding {"bg", "fg"}: the
 zero-shot text rows, for a machine without the reference checkout that `--reference_root` names) and `comer` (bool).
@@ -116,6 +123,8 @@ def build_parser():
     p.add_argument("--reg_coef", type=float, default=0.01, help="weight of the energy term in the step's loss")
     p.add_argument("--reg_scale", type=float, default=0.5, choices=(1.0, 0.5, 0.25), help="scale_factor of the DenseEnergyLoss")
     p.add_argument("--reg_start", type=int, default=None, help="the term starts after this iteration (default: train.cam_iters)")
+    p.add_argument("--panel_iters", type=int, default=0,
+                   help="rank 0 writes the image panels (<work_dir>/panels/iter_<n>_<name>.png) every this many iterations; 0: off")
     return p
 
 
@@ -244,17 +253,22 @@ def cal_eta(time0, cur_iter, total_iter):
 class LoggedTrainStep(TrainStep):
     """TrainStep whose losses() also counts, on the device, the pixels where the up-sampled logits' arg-max equals the
     pseudo label (`counts` int64[2] = [matches, pixels], overwritten by every step).  The launch sits between the parent's
-    loss kernels and the backward, so in graph mode it is part of the captured step; the returned losses are the parent's."""
+    loss kernels and the backward, so in graph mode it is part of the captured step; the returned losses are the parent's.
+    panels (default None: nothing about the step changes): a `utils.panels.StepSnapshot`; one more launch beside the counting
+    kernel then copies the logits, the pseudo labels (as uint8) and the four attn_pred rows of the attention panels into it."""
 
-    def __init__(self, model, *args, **kw):
+    def __init__(self, model, *args, panels=None, **kw):
         super().__init__(model, *args, **kw)
         self.counts = torch.zeros(2, device=next(model.parameters()).device, dtype=torch.int64)
+        self.panels = panels
 
     def losses(self, seg, cam, attn_pred):
         out = super().losses(seg, cam, attn_pred)
         if seg.is_cuda:
             from .validate import label_match_count
             label_match_count(seg.detach().float().contiguous(), cam.long().contiguous(), self.counts)
+            if self.panels is not None:
+                self.panels.take(seg.detach().float().contiguous(), cam.long().contiguous(), attn_pred.detach().float().contiguous())
         return out
 
 
@@ -264,10 +278,13 @@ class LoggedSupervisedTrainStep(SupervisedTrainStep):
     NOT in any denominator, unlike LoggedTrainStep's pixel count, which is right for pseudo labels only).  The step ADDS into
     `hist`; whoever reads it zeroes it.  `ce` (a static scalar) holds the step's cross-entropy, which under `reg` is not
     among the returned values.  Both launches sit between the parent's loss kernels and the backward, so in graph mode they
-    are part of the captured step; they read `seg.detach()` and `label` only, and the returned loss is the parent's."""
+    are part of the captured step; they read `seg.detach()` and `label` only, and the returned loss is the parent's.
+    panels (default None: nothing about the step changes): a `utils.panels.StepSnapshot` that one more launch fills with the
+    logits and the ground-truth labels (as uint8)."""
 
-    def __init__(self, model, *args, **kw):
+    def __init__(self, model, *args, panels=None, **kw):
         super().__init__(model, *args, **kw)
+        self.panels = panels
         dev = next(model.parameters()).device
         nc = int(model.num_classes)
         self.hist = torch.zeros(nc, nc, device=dev, dtype=torch.int64)
@@ -283,7 +300,104 @@ class LoggedSupervisedTrainStep(SupervisedTrainStep):
             from .validate import step_pair_hist
             self.ce.copy_(out.detach())
             step_pair_hist(seg.detach().float().contiguous(), label.long().contiguous(), self.hist.shape[0], self.hist, self._flag)
+            if self.panels is not None:
+                self.panels.take(seg.detach().float().contiguous(), label.long().contiguous())
         return out
+
+
+# ---------------------------------------------------------------------------------------------- the panel files
+class PanelWriter:
+    """A ring of `depth` (device, pinned host) buffer pairs and `writers` host threads behind it, after msc_flip_eval.WriterPool:
+
+        slot = pw.acquire({"images": (h, w), ...})   # waits for the slot's writer; slot.views[name]: zeroed (3,h,w) uint8 canvases
+        ... the panel kernels paint the canvases ...
+        pw.commit(slot, n_iter)                      # ONE asynchronous copy device -> host, one event, the job is queued
+
+    A writer waits for the slot's event and saves out_dir/iter_<n_iter>_<name>.png with Pillow; `on_image(name, chw, n_iter)`
+    (tensorboard's add_image, where it imports) is called with the same host array.  The buffers only grow.  The first
+    exception of a writer is kept and raised by `finish()`."""
+
+    def __init__(self, out_dir, writers=2, depth=2, on_image=None):
+        import queue
+        import threading
+        from .msc_flip_eval import _Slot, _cuda_event
+        self.out_dir, self.on_image = out_dir, on_image
+        os.makedirs(out_dir, exist_ok=True)
+        self.depth = max(1, int(depth))
+        self.slots = [_Slot(_cuda_event()) for _ in range(self.depth)]
+        self._next = 0
+        self.jobs = queue.Queue(maxsize=self.depth)
+        self.error = None
+        self.written = 0
+        self._lock = threading.Lock()
+        self.threads = [threading.Thread(target=self._work, name=f"weclip-panel-{i}", daemon=True) for i in range(max(1, int(writers)))]
+        for t in self.threads:
+            t.start()
+
+    def acquire(self, shapes):
+        from .msc_flip_eval import _cuda_alloc
+        slot = self.slots[self._next]
+        slot.free.wait()
+        self._next = (self._next + 1) % self.depth
+        need = sum(3 * h * w for h, w in shapes.values())
+        if slot.dev is None or slot.dev.numel() < need:
+            slot.dev, slot.host = _cuda_alloc(need)
+        slot.dev[:need].zero_()                          # the grids' borders: the kernels write the tiles only
+        slot.views, slot.layout, off = {}, [], 0
+        for name, (h, w) in shapes.items():
+            slot.views[name] = slot.dev[off:off + 3 * h * w].view(3, h, w)
+            slot.layout.append((name, off, h, w))
+            off += 3 * h * w
+        return slot
+
+    def commit(self, slot, n_iter):
+        need = sum(3 * h * w for _, _, h, w in slot.layout)
+        slot.free.clear()
+        slot.host[:need].copy_(slot.dev[:need], non_blocking=True)
+        slot.copied.record()
+        self.jobs.put((slot, int(n_iter)))
+
+    def _write(self, slot, n_iter):
+        from PIL import Image
+        slot.copied.synchronize()
+        host = slot.host.numpy()
+        for name, off, h, w in slot.layout:
+            chw = host[off:off + 3 * h * w].reshape(3, h, w)
+            Image.fromarray(np.ascontiguousarray(chw.transpose(1, 2, 0)), mode="RGB").save(
+                os.path.join(self.out_dir, f"iter_{n_iter}_{name}.png"))
+            if self.on_image is not None:
+                self.on_image(name, chw, n_iter)
+
+    def _work(self):
+        while True:
+            job = self.jobs.get()
+            try:
+                if job is None:
+                    return
+                try:
+                    self._write(*job)
+                    with self._lock:
+                        self.written += 1
+                except BaseException as e:               # kept for finish(); the slot is freed either way
+                    with self._lock:
+                        if self.error is None:
+                            self.error = e
+                finally:
+                    job[0].free.set()
+            finally:
+                self.jobs.task_done()
+
+    def finish(self):
+        """Wait for every queued panel set, end the threads, raise the first writer exception.  -> sets written."""
+        self.jobs.join()
+        for _ in self.threads:
+            self.jobs.put(None)
+        for t in self.threads:
+            t.join()
+        self.threads = []
+        if self.error is not None:
+            raise self.error
+        return self.written
 
 
 # ---------------------------------------------------------------------------------------------- the driver
@@ -367,12 +481,17 @@ class Trainer:
                                   betas=tuple(float(b) for b in opt.betas), warmup_iter=int(sch.warmup_iter),
                                   max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power))
         self.reg = reg_settings(cfg, args)
+        self.panel_iters = max(0, int(getattr(args, "panel_iters", 0) or 0))
+        self.snapshot = self.panel_writer = self._last_inputs = None
+        if self.panel_iters and self.rank == 0:          # without the flag the step is the parent's: same launches, same graph
+            from .utils.panels import StepSnapshot
+            self.snapshot = StepSnapshot()
         if self.kind == "seg":
             self.step = LoggedSupervisedTrainStep(self.model, self.opt, ignore_index=ds.ignore_index,
-                                                  graph=bool(getattr(args, "graph", True)), reg=self.reg)
+                                                  graph=bool(getattr(args, "graph", True)), reg=self.reg, panels=self.snapshot)
         else:
             self.step = LoggedTrainStep(self.model, self.opt, radius=getattr(args, "radius", 8), ignore_index=ds.ignore_index,
-                                        graph=bool(getattr(args, "graph", True)), reg=self.reg)
+                                        graph=bool(getattr(args, "graph", True)), reg=self.reg, panels=self.snapshot)
         self.validator = Validator(self.model, ds.num_classes, self.rank, self.world)
         dev = next(self.model.parameters()).device
         # window sums of (loss, seg_loss, attn_loss[, reg_loss with --reg_loss]); seg: (loss, seg_loss[, reg_loss])
@@ -388,6 +507,11 @@ class Trainer:
                 self.writer = SummaryWriter(cfg.work_dir.tb_logger_dir)
             except ImportError:
                 pass
+        if self.snapshot is not None:
+            on_image = None
+            if self.writer is not None:
+                on_image = lambda name, chw, n: self.writer.add_image("train/" + name, chw, global_step=n)      # noqa: E731
+            self.panel_writer = PanelWriter(os.path.join(cfg.work_dir.dir, "panels"), on_image=on_image)
         if getattr(args, "resume", None):
             self.resume(args.resume)
 
@@ -411,6 +535,7 @@ class Trainer:
             return self._seg_step_once()
         from .datasets import labels_from_onehot
         _, inputs, _, img_box = self._next_batch()
+        self._last_inputs = inputs
         labels = labels_from_onehot(self.train_loader.last_cls_labels)      # the host copy: graph mode needs explicit labels
         out = self.step(inputs, labels=labels) if self.reg is None else self.step(inputs, labels=labels, img_box=img_box)
         self.acc.add_(torch.stack(out))
@@ -422,6 +547,7 @@ class Trainer:
         """--dataset seg: (inputs, labels) of the batch go straight to the step, the labels stay on the device; with
         --reg_loss the batch's img_box (DeviceLoader.last_img_box, a device tensor) goes with them."""
         _, inputs, labels, _ = self._next_batch()
+        self._last_inputs = inputs
         if self.reg is None:
             out = (self.step(inputs, labels),)
         else:
@@ -430,6 +556,35 @@ class Trainer:
         self.window += 1
         self.n_iter += 1
         return out
+
+    def render_panels(self):
+        """Rank 0 with --panel_iters: the panel set of the step that just ran, from the step's snapshot and the batch's input
+        images, painted into a slot of the PanelWriter's ring.  Kernels and one asynchronous copy on the stream: no forward
+        (model.iter_num stays), no host read.  -> the slot (its views are valid until the ring comes round), or None."""
+        if self.panel_writer is None or self.snapshot.seg is None:
+            return None
+        from .msc_flip import resize_argmax
+        from .utils import panels as P
+        snap, imgs = self.snapshot, self._last_inputs.detach().float().contiguous()
+        B, _, H, W = imgs.shape
+        geo = P.grid_geometry(B, H, W, 2)
+        label_name = "gt_label" if self.kind == "seg" else "pseudo_label"
+        shapes = {name: (geo.canvas_h, geo.canvas_w) for name in ("images", label_name, "prediction", "seg_conf")}
+        if snap.rows is not None:
+            ageo = P.grid_geometry(B, 224, 224, 4, colmajor=True)
+            shapes.update({f"attn_pred_{j}": (ageo.canvas_h, ageo.canvas_w) for j in range(4)})
+        slot = self.panel_writer.acquire(shapes)
+        v = slot.views
+        conf = torch.softmax(snap.seg, dim=1)[:, 1:].contiguous()        # the head's confidence without its background channel
+        P.tensorboard_image(imgs, conf, out=(v["images"], v["seg_conf"]))
+        P.paint_labels(snap.label, v[label_name], geo)
+        pred = torch.stack([resize_argmax(snap.seg[b], (H, W)) for b in range(B)])
+        P.paint_labels(pred, v["prediction"], geo)
+        if snap.rows is not None:
+            for j in range(4):
+                P.attn_rows_grid([snap.rows[:, j]], n_row=4, out=v[f"attn_pred_{j}"])
+        self.panel_writer.commit(slot, self.n_iter)
+        return slot
 
     def _seg_log(self):
         """--dataset seg: the window's loss sums and its confusion matrix in ONE device-to-host read; the matrix is then
@@ -536,6 +691,8 @@ class Trainer:
         stop = self.max_iters if until is None else min(int(until), self.max_iters)
         while self.n_iter < stop:
             self.step_once()
+            if self.panel_iters and self.n_iter % self.panel_iters == 0:
+                self.render_panels()
             if self.n_iter % cfg.log_iters == 0:
                 self.log()
             if self.n_iter % cfg.eval_iters == 0:
@@ -554,6 +711,9 @@ class Trainer:
         if self._batches is not None:
             self._batches.close()                        # ends the loader's decode threads
             self._batches = None
+        if self.panel_writer is not None:
+            pw, self.panel_writer = self.panel_writer, None
+            pw.finish()                                  # before the tensorboard writer its threads feed is closed
         if self.writer is not None:
             self.writer.close()
         if self.rank_dump_dir:
