@@ -646,6 +646,43 @@ int wc_dcrf_inference(const void* img, int img_is_u8, const float* unary, float*
 int wc_dcrf_message(const void* img, int img_is_u8, const float* Q, float* msg_pos, float* msg_bil, float* S, void* ws,
                     int C, int H, int W, float pos_xy_std, float bi_xy_std, float bi_rgb_std, void* stream);
 
+/* ---- dense CRF, lattice bilateral term (csrc/dcrf_lattice.hip; DESIGN.md "Dense CRF", "The lattice") --------------- */
+/* utils/dcrf.py wraps pydensecrf, which filters the bilateral term on the permutohedral lattice (Adams, Baek, Davis 2010).
+ * These entries are that filter (d = 5, features (x, y) / bi_xy_std and (R, G, B) / bi_rgb_std) as an OPT-IN second way to the
+ * bilateral message; the wc_dcrf_* entries above stay exact.  The algorithm is the one restated in fp64 by
+ * tests/dcrf_lattice_ref.py: fp64 build (weights stored f32), splat, d + 1 blur passes new = old + (n1 + n2) / 2 over the
+ * vertices the image touches, slice with alpha = 1 / (1 + 2^-d).  Built by sorting packed vertex keys: no hash table, no float
+ * atomics, bit-identical from call to call.
+ * Key bound: a key packs the d stored coordinates at 12 bits each.  With c_max = ((W-1) / bi_xy_std) s_0, ((H-1) / bi_xy_std) s_1,
+ *   (256 / bi_rgb_std) s_2..4 and s_j = sqrt(2/3) (d+1) / sqrt((j+1)(j+2)), the elevated coordinate e_j = sum_{m>=j} c_m - j c_{j-1}
+ *   satisfies |e_j| <= E = max_j max(sum_{m>=j} c_max,m, j c_max,j-1); a vertex or blur-neighbour coordinate is within 20 of it.
+ *   E + 20 <= 2047 is required (WC_ERR_ARG otherwise, nothing launched).  Colours outside [0, 256] (f32 images) are clamped for the
+ *   keys and set flag = 1.
+ * Limits (WC_ERR_ARG, nothing launched): those of wc_dcrf_inference, the key bound, 1 <= M <= 6 H W, non-null pointers.
+ * Error model of a filter or message element against the fp64 restatement: |M - M64| <= eps * M64 + 2^-24, eps = 2^-10
+ *   (f32 weights, f32 splat / blur / slice sums in fixed order, at most 6 * 3^6 terms, all non-negative up to weight rounding).
+ * wc_dcrf_lattice_key_bound:       *h_bound (HOST) = E + 20 for the given shape and stds; WC_ERR_ARG when it exceeds 2047.
+ * wc_dcrf_lattice_workspace_bytes: HOST out-parameters: bytes of the structure `lat` (depends on H W only) and of the f32
+ *                                  workspace `ws` of the three calls below.
+ * wc_dcrf_lattice_build:           img (H,W,3) -> lat.  lat begins with int32 meta[16]: meta[0] = M (unique vertices), meta[1] =
+ *                                  flag.  The host may read these once to size `vals`; nothing else is read back.
+ * vals: 2 * (M + 1) * CP f32, CP = 32 * ceil(C / 32): the value rows and their ping-pong partner.  M is passed back by the host;
+ *                                  a call whose M differs from meta[0] writes nothing.
+ * wc_dcrf_lattice_filter:          out (C,H,W) = the un-normalised filter of in (C,H,W).
+ * wc_dcrf_lattice_message:         the outputs of wc_dcrf_message with M_bil = n filter(n Q), n = (filter(1) + 1e-20)^-1/2,
+ *                                  S[1] = filter(1) (about half the exact S_bil; the symmetric normalisation absorbs it).
+ * wc_dcrf_lattice_inference:       wc_dcrf_inference with that bilateral message; the image and the bilateral stds are in lat. */
+int wc_dcrf_lattice_key_bound(int H, int W, float bi_xy_std, float bi_rgb_std, double* h_bound);
+int wc_dcrf_lattice_workspace_bytes(int C, int H, int W, long* h_lat_bytes, long* h_ws_bytes);
+int wc_dcrf_lattice_build(const void* img, int img_is_u8, void* lat, int H, int W, float bi_xy_std, float bi_rgb_std,
+                          void* stream);
+int wc_dcrf_lattice_filter(const void* lat, const float* in, float* out, float* vals, void* ws, int C, int H, int W, long M,
+                           void* stream);
+int wc_dcrf_lattice_message(const void* lat, const float* Q, float* msg_pos, float* msg_bil, float* S, float* vals, void* ws,
+                            int C, int H, int W, long M, float pos_xy_std, void* stream);
+int wc_dcrf_lattice_inference(const void* lat, const float* unary, float* Q, float* vals, void* ws, int C, int H, int W, long M,
+                              int iter_max, float pos_w, float pos_xy_std, float bi_w, void* stream);
+
 /* ---- dense energy loss (csrc/energy.hip) ------------------------------------------------------ */
 /* utils/losses.py:52-116 (`DenseEnergyLossFunction`, `DenseEnergyLoss`) with the `bilateralfilter_batch` call of :75 as the
  * EXACT all-pairs sum (the extension's permutohedral lattice is not built; parity with it: unpinned).  Pixel i = y * W + x;

@@ -5,6 +5,7 @@ without label files, and the CRF is the 21-class one), scales 1 and 0.75, long s
   (n0) msc_flip_eval.SplitEvaluator, no files            (p0) MscFlipEvaluator.add
   (n1) SplitEvaluator writing prediction/ + _cmap/       (p1) add, .cpu() of both maps, serial Pillow save of the msc map and table[map]
   (n2) SplitEvaluator with the CRF leg and files         (p2) add_with_crf, .cpu() of the maps, serial Pillow save of the CRF map
+  (n3) n2 with DenseCRF(..., bilateral="lattice"): the CRF leg's bilateral message on the permutohedral lattice
   (v)  SplitEvaluator on the VOC model with its CAM leg and files (the parent cannot evaluate a VOC model built without
        dataset_root_path: no counterpart)
 
@@ -169,6 +170,7 @@ def main():
     table = np.load(os.path.join(ROOT, "tests", "golden", "voc_cmap.npz"))["cmap"]
     seg_model, voc_model = make_models(torch)
     crf = DenseCRF(**E.CRF_PARAMS)
+    crf_lattice = DenseCRF(**E.CRF_PARAMS, bilateral="lattice")
     rows = {}
     with tempfile.TemporaryDirectory() as tmp:
         tree = write_tree(os.path.join(tmp, "tree"), args.images)
@@ -183,6 +185,7 @@ def main():
                 ("p1", lambda d: parent_pass(torch, seg_model, d, os.path.join(tmp, "p1"), None, table), ds),
                 ("n2", lambda d: new_pass(torch, seg_model, d, os.path.join(tmp, "n2"), crf, args.writers), few),
                 ("p2", lambda d: parent_pass(torch, seg_model, d, os.path.join(tmp, "p2"), crf, table), few),
+                ("n3", lambda d: new_pass(torch, seg_model, d, os.path.join(tmp, "n3"), crf_lattice, args.writers), few),
                 ("v", lambda d: new_pass(torch, voc_model, d, os.path.join(tmp, "v"), None, args.writers), ds)]
         rates = {k: [] for k, _, _ in plan}
         hists = {}
@@ -206,6 +209,8 @@ def main():
            "n0_split_evaluator_no_files": rows["n0"], "p0_parent_add": rows["p0"],
            "n1_split_evaluator_files": rows["n1"], "p1_parent_add_cpu_serial_save": rows["p1"],
            "n2_split_evaluator_crf_files": rows["n2"], "p2_parent_add_with_crf_cpu_serial_save": rows["p2"],
+           "n3_split_evaluator_crf_lattice_files": rows["n3"],
+           "ratio_n3_over_n2": round(rows["n3"]["images_per_s"] / rows["n2"]["images_per_s"], 3),
            "v_split_evaluator_voc_cam_leg_files": rows["v"],
            "ratio_n0_over_p0": round(rows["n0"]["images_per_s"] / rows["p0"]["images_per_s"], 3),
            "ratio_n1_over_p1": round(rows["n1"]["images_per_s"] / rows["p1"]["images_per_s"], 3),

@@ -542,3 +542,47 @@ extern "C" int wc_dcrf_inference(const void* img, int img_is_u8, const float* un
     }
     return WC_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ shared with dcrf_lattice.hip
+#include "dcrf_shared.h"
+
+namespace dcrf_shared {
+
+int limits(int C, int H, int W, float pos_xy_std, float bi_xy_std, float bi_rgb_std, const char* who) {
+    Plan p;
+    return plan(p, C, H, W, pos_xy_std, bi_xy_std, bi_rgb_std, who);
+}
+
+int pos_norm(int H, int W, float pos_xy_std, float* S, float* nrm, hipStream_t st) {
+    Plan p;
+    if (int rc = plan(p, 1, H, W, pos_xy_std, 1.f, 1.f, "dcrf")) return rc;
+    hipLaunchKernelGGL(dcrf_gauss_norm_kernel, dim3(wc_cdiv(p.N, 256)), dim3(256), 0, st, S, nrm, H, W, p.R, p.a_pos);
+    WC_LAUNCH_CHECK("dcrf_gauss_norm_kernel");
+    return WC_OK;
+}
+
+int gauss_message(int C, int H, int W, float pos_xy_std, const float* in, float* tmp, float* out, hipStream_t st) {
+    Plan p;
+    if (int rc = plan(p, C, H, W, pos_xy_std, 1.f, 1.f, "dcrf")) return rc;
+    return ::gauss_message(p, H, W, in, tmp, out, st);
+}
+
+int init(const float* U, const float* nrm, float* Q, float* Vb, float* Vp, int C, int CP, int N, hipStream_t st) {
+    hipLaunchKernelGGL(dcrf_init_kernel, dim3(wc_cdiv(N, 256)), dim3(256), 0, st, U, nrm, Q, Vb, Vp, C, CP, N);
+    WC_LAUNCH_CHECK("dcrf_init_kernel");
+    return WC_OK;
+}
+
+int operands(const float* Q, const float* nrm, float* Vb, float* Vp, int C, int CP, int N, hipStream_t st) {
+    hipLaunchKernelGGL(dcrf_operands_kernel, dim3(wc_cdiv((long)C * N, 256)), dim3(256), 0, st, Q, nrm, Vb, Vp, C, CP, N);
+    WC_LAUNCH_CHECK("dcrf_operands_kernel");
+    return WC_OK;
+}
+
+int scale(const float* G, const float* nrm, float* msg, int C, int N, hipStream_t st) {
+    hipLaunchKernelGGL(dcrf_scale_kernel, dim3(wc_cdiv((long)C * N, 256)), dim3(256), 0, st, G, nrm, msg, C, N);
+    WC_LAUNCH_CHECK("dcrf_scale_kernel");
+    return WC_OK;
+}
+
+}  // namespace dcrf_shared

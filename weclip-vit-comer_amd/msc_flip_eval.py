@@ -341,6 +341,8 @@ def build_parser():
     p.add_argument("--dataset", choices=("voc", "coco", "seg"), default="voc", help="seg: the supervised variant on VOC")
     p.add_argument("--scales", type=parse_scales, default=[1.0, 0.75])
     p.add_argument("--crf", action=argparse.BooleanOptionalAction, default=False, help="the crf_proc leg (commented out in the reference)")
+    p.add_argument("--crf_bilateral", choices=("exact", "lattice"), default="exact",
+                   help="the CRF leg's bilateral message: the exact all-pairs sum, or the permutohedral lattice (as pydensecrf)")
     p.add_argument("--save_logits", action="store_true", help="logit/NAME.npy as the reference writes it")
     p.add_argument("--threads", type=int, default=8, help="decode threads of the loader")
     p.add_argument("--writers", type=int, default=4, help="host threads that write the PNG files")
@@ -389,7 +391,7 @@ def main(argv=None):
         crf = None
         if args.crf:
             from .utils.dcrf import DenseCRF
-            crf = DenseCRF(**CRF_PARAMS)
+            crf = DenseCRF(**CRF_PARAMS, bilateral=args.crf_bilateral)
         if rank == 0:
             print(cfg)
             print(args)

@@ -329,6 +329,21 @@ def _(image, probs, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
     return probs.new_empty(probs.shape, dtype=F32)
 
 
+@torch.library.custom_op(f"{_LIB}::dense_crf_lattice", mutates_args=(), device_types="cuda")
+def dense_crf_lattice(image: Tensor, probs: Tensor, iter_max: int, pos_w: float, pos_xy_std: float, bi_w: float,
+                      bi_xy_std: float, bi_rgb_std: float) -> Tensor:
+    """dense_crf with the bilateral message filtered on the permutohedral lattice (DenseCRF(..., bilateral="lattice")).
+    No autograd."""
+    from .utils import dcrf
+    return dcrf.inference(image, dcrf.unary_from_prob(probs), iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std,
+                          bilateral="lattice")
+
+
+@dense_crf_lattice.register_fake
+def _(image, probs, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
+    return probs.new_empty(probs.shape, dtype=F32)
+
+
 @torch.library.custom_op(f"{_LIB}::encode_text", mutates_args=(), device_types="cuda")
 def encode_text(text: Tensor, token_embedding: Tensor, positional_embedding: Tensor, blocks: List[Tensor], heads: int,
                 ln_final_weight: Tensor, ln_final_bias: Tensor, text_projection: Tensor) -> Tensor:
@@ -496,4 +511,4 @@ def _(attns, size, n_pix, n_row):
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
        "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
-       "panel_images", "panel_labels", "panel_attn")
+       "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice")
