@@ -685,7 +685,8 @@ int wc_dcrf_lattice_inference(const void* lat, const float* unary, float* Q, flo
 
 /* ---- dense energy loss (csrc/energy.hip) ------------------------------------------------------ */
 /* utils/losses.py:52-116 (`DenseEnergyLossFunction`, `DenseEnergyLoss`) with the `bilateralfilter_batch` call of :75 as the
- * EXACT all-pairs sum (the extension's permutohedral lattice is not built; parity with it: unpinned).  Pixel i = y * W + x;
+ * EXACT all-pairs sum (the extension's permutohedral lattice is not built by these entries -- the opt-in lattice entries
+ * follow below --; parity with the extension: unpinned).  Pixel i = y * W + x;
  * images (N,3,H,W) f32 on the 0..255 scale, segs P (N,K,H,W) f32, rois (N,H,W) f32 in {0,1}, unlabel_u8 (N,H,W) bytes
  * (non-zero = unlabelled).  k_n(i,j) = exp(-|p_i - p_j|^2 / (2 sigma_xy^2) - |I_n,i - I_n,j|^2 / (2 sigma_rgb^2)), j = i
  * included; S = P * ROI; AS(n,k,i) = sum_j k_n(i,j) S(n,k,j); Gate = ROI - max_k P, then 1 where unlabelled, then 0 where
@@ -707,6 +708,44 @@ int wc_dense_energy_fwd(const float* images, const float* segs, const float* roi
                         float* loss, void* ws, int N, int K, int H, int W, float sigma_rgb, float sigma_xy, void* stream);
 int wc_dense_energy_bwd(const float* A, const float* rois, const float* grad_out, float* grad_segs, int N, int K, int H, int W,
                         void* stream);
+
+/* ---- dense energy loss, lattice filter (csrc/energy_lattice.hip) ----------------------------- */
+/* (Added to the paragraph above: "the extension's permutohedral lattice is not built" was true of the exact entries and still
+ * is; these entries are the opt-in second way.  Parity with the extension itself stays unpinned: it is not shipped.)
+ * utils/losses.py:75 with the filter as the permutohedral lattice (Adams, Baek, Davis 2010; d = 5), un-normalised, as the
+ * lineage's `bilateralfilter` extension uses it: per image n, AS(n) = filter(build(image_n, H, W, sigma_xy, sigma_rgb), S(n))
+ * of tests/dcrf_lattice_ref.py (forward blur order 0..d, alpha = 1 / (1 + 2^-d)), composed with the loss, Gate and gradient of
+ * tests/energy_ref.py in tests/energy_lattice_ref.py.  Shapes, S, Gate, A and loss as for the exact entries above; the backward
+ * is the unchanged wc_dense_energy_bwd / wc_energy_prep_bwd (the factor 2 is an approximation here: the lattice filter is not a
+ * symmetric matrix).  The lattice AS is about half the exact AS: a weight tuned for one does not carry
+ * over to the other.
+ * The images are read as NCHW f32 (no HWC copy); every build decision is made in fp64; colours outside [0, 256] are clamped
+ * for the key and reported by OR-ing 1 into int32 meta[1] of `lat`, which the caller may read whenever it likes (the entries
+ * never do).  `lat` begins with int32 meta[16 + N]: meta[0] = M of the last image, meta[1] = the flag, meta[16 + n] = M (the
+ * number of lattice vertices) of image n.  M never crosses to the host: the kernels read it on the device, their grids cover
+ * the worst case M <= 6 H W (every pixel touches d + 1 = 6 vertices) and workgroups beyond M exit at once.  The images go one
+ * after another through one shared structure.  No allocation, no host synchronisation, every launch and every rocPRIM call
+ * on `stream`: an entry can be captured into a graph and replayed on other contents.  No floating-point atomics, fixed-order
+ * sums: bit-identical from run to run.
+ * Limits (WC_ERR_ARG, nothing launched): those of the exact entries (non-null pointers, 1 <= N <= 65535: N is looped over
+ * inside the entry, but the shared operand kernel keeps the image index in its grid; 1 <= K <= 128, 1 <= H*W <= 640*640,
+ * sigmas finite and > 0), lat and ws 256-byte aligned, and wc_dcrf_lattice_key_bound(H, W, sigma_xy, sigma_rgb) <= 2047,
+ * checked on the host before any launch.
+ * Error model of an element of AS against the fp64 restatement: |AS - AS64| <= eps * filter64(|S|) + 2^-24, eps = 2^-10.
+ * wc_energy_lattice_workspace_bytes: HOST out-parameters, the only source of sizes.  With HW = H*W, NE = 6*HW, CP = 32*ceil(K/32),
+ *     XC = NE/256 + 2 (integer division) and every piece rounded up to 256 bytes:
+ *     lat_bytes = 4*(16 + N) + 4*NE*6 + 8*NE*2 + 8*(NE+1) + 4*(NE+2) + 4*XC*2 + 48*(NE+1) + rocPRIM's temporary storage
+ *                 (the larger of a 60-bit pair sort and a scan of NE entries);
+ *     ws_bytes  = 4 * (8*N*HW + N*HW*CP + N*ceil(HW/32) + 2*(NE+1)*CP + XC*CP): features, operand, loss partials, the two value
+ *                 row sets of ONE image (the worst case, 100 MB at 256x256 and CP = 32) and the long-segment partial rows.
+ * wc_bilateral_filter_batch_lattice: wc_bilateral_filter_batch with that filter (segs may be signed).
+ * wc_dense_energy_fwd_lattice: wc_dense_energy_fwd with that filter: A = Gate * AS, gate, loss. */
+int wc_energy_lattice_workspace_bytes(int N, int K, int H, int W, long* h_lat_bytes, long* h_ws_bytes);
+int wc_bilateral_filter_batch_lattice(const float* images, const float* segs, float* AS, void* lat, void* ws, int N, int K, int H,
+                                      int W, float sigma_rgb, float sigma_xy, void* stream);
+int wc_dense_energy_fwd_lattice(const float* images, const float* segs, const float* rois, const void* unlabel_u8, float* A,
+                                float* gate, float* loss, void* lat, void* ws, int N, int K, int H, int W, float sigma_rgb,
+                                float sigma_xy, void* stream);
 
 /* ---- dense energy loss as a term of the training step (csrc/energy_prep.hip) ------------------ */
 /* get_energy_loss (utils/losses.py:35-50) on F.interpolate(seg, (H,W), bilinear, align_corners=False) followed by

@@ -1,14 +1,20 @@
 """HIP-event time of one forward + backward of the dense energy loss (utils.losses.DenseEnergyLossFunction) against the same loss
 written with stock torch ops on the same card.
 
-    python tools/energy_bench.py [--windows 5] [--out profiles/energy_bench.json] [--small-only]
+    python tools/energy_bench.py [--windows 5] [--out profiles/energy_bench.json] [--key NAME] [--small-only]
 
 Sizes: N = 4, K = 21, 160 x 160 (the reference's default: crop 320, batch 4, scale 0.5) and N = 16, K = 21, 256 x 256.
 Method: a warm-up call of both, then --windows windows of each, alternating (ours, stock, ours, ...); a window is `iters`
 forward + backward calls between two events; reported: median (min .. max) of the windows' ms per call.  The stock form computes
 the pairwise exponent in row chunks (a matmul of the centred features, exp) and contracts it with a matmul; it is the comparison, the parent commit has no
 implementation.  `filter_ms`: the library's own event pair around energy_filter_kernel in a separate call.  `estimate_ms`: the
-dense CRF's measured 29.101 ms per 3.515625e10 pairs at CP = 32 (profiles/dcrf_bench.json) scaled to this size's pairs."""
+dense CRF's measured 29.101 ms per 3.515625e10 pairs at CP = 32 (profiles/dcrf_bench.json) scaled to this size's pairs.
+The `lattice` row is the same call with bilateral="lattice" (csrc/energy_lattice.hip), timed in the same
+process in windows that alternate with the exact ones; `lattice_split_ms`: the library's event pairs around the per-image build
+(key kernel, sort, scans, neighbours) and filter (splat, blur, slice), summed over the images of one call, and the rest of a
+forward + backward; `lattice_M_per_pixel`: lattice vertices per pixel of every image.  The lattice AS is about half the exact
+AS, so `lattice_vs_exact` is recorded as a description of the two filters, not as an error.  --key NAME stores the result under
+that key of the JSON file --out, keeping the file's other keys."""
 import argparse
 import json
 import os
@@ -62,6 +68,16 @@ def ours_fwd_bwd(img, P, roi, unl, g):
     return loss.detach(), p.grad
 
 
+LATTICE_WS = {}
+
+
+def lattice_fwd_bwd(img, P, roi, unl, g):
+    p = P.detach().requires_grad_(True)
+    loss, A, _ = losses.dense_energy_forward(img, p, SIGMA_RGB, SIGMA_XY, roi, unl, "lattice",
+                                             losses._lattice_workspace(*P.shape, P.device, LATTICE_WS))
+    return loss, losses.dense_energy_backward(g, A, roi)
+
+
 def window(fn, args, iters):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -91,17 +107,31 @@ def run_case(N, K, H, W, iters, windows):
     l2, g2 = stock_fwd_bwd(*args)
     torch.cuda.synchronize()
     agree = dict(loss_rel=abs(l1.item() - l2.item()) / abs(l2.item()), grad_rel_of_max=((g1 - g2).abs().max() / g2.abs().max()).item())
-    ours, stock = [], []
+    l3, g3 = lattice_fwd_bwd(*args)
+    torch.cuda.synchronize()
+    flag, M = losses.lattice_vertex_counts(losses._lattice_workspace(N, K, H, W, P.device, LATTICE_WS)[0], N)
+    lat_vs_exact = dict(loss_ratio=l3.item() / l1.item(), grad_max_ratio=(g3.abs().max() / g1.abs().max()).item(), clamp_flag=flag.item())
+    ours, stock, lat = [], [], []
     for _ in range(windows):
         ours.append(window(ours_fwd_bwd, args, iters[0]))
+        lat.append(window(lattice_fwd_bwd, args, iters[0]))
         stock.append(window(stock_fwd_bwd, args, iters[1]))
+    KernelTimer.enable(1)
+    lattice_fwd_bwd(*args)
+    rec = KernelTimer.summary()
+    KernelTimer.enable(0)
+    build_ms, filt_ms = (rec.get(k, {}).get("ms", float("nan")) for k in ("energy_lattice_build", "energy_lattice_filter"))
+    lat_med = statistics.median(lat)
+    split = dict(build=round(build_ms, 3), filter=round(filt_ms, 3), rest=round(lat_med - build_ms - filt_ms, 3))
     KernelTimer.enable(1)
     ours_fwd_bwd(*args)
     rec = KernelTimer.summary().get("energy_filter_kernel", {})
     KernelTimer.enable(0)
     pairs = N * (H * W) ** 2
     return dict(N=N, K=K, H=H, W=W, CP=32 * ((K + 31) // 32), pairs=pairs, iters_per_window=list(iters), windows=windows,
-                ours=stats(ours), stock_torch=stats(stock), filter_ms=round(rec.get("ms", float("nan")), 3),
+                ours=stats(ours), lattice=stats(lat), lattice_split_ms=split, lattice_M_per_pixel=[round(m / (H * W), 3) for m in M.tolist()],
+                exact_over_lattice=round(statistics.median(ours) / lat_med, 2), lattice_all_ms=[round(t, 3) for t in lat],
+                lattice_vs_exact=lat_vs_exact, stock_torch=stats(stock), filter_ms=round(rec.get("ms", float("nan")), 3),
                 estimate_ms=round(29.101 * pairs / 3.515625e10, 3), ours_all_ms=[round(t, 3) for t in ours],
                 stock_all_ms=[round(t, 3) for t in stock], ours_vs_stock=agree, sigma_rgb=SIGMA_RGB, sigma_xy=SIGMA_XY)
 
@@ -110,14 +140,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--key", default=None, help="store the result under this key of the JSON file --out, keeping its other keys")
     ap.add_argument("--small-only", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("energy_bench: needs the GPU; there is nothing to time without one")
     res = [run_case(**c, windows=a.windows) for c in (CASES[:1] if a.small_only else CASES)]
     res = dict(device=torch.cuda.get_device_name(0), cases=res)
+    print(json.dumps(res, indent=1))
+    if a.out and a.key:
+        old = json.load(open(a.out)) if os.path.exists(a.out) else {}
+        res = dict(old, **{a.key: res})
     txt = json.dumps(res, indent=1)
-    print(txt)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:

@@ -24,76 +24,12 @@
 // Error model: include/weclip_hip.h (wc_dcrf_lattice_*).
 #include "common.h"
 #include "dcrf_shared.h"
+#include "lattice_shared.h"       // the layout, the per-pixel build and the chunk sum: shared with csrc/energy_lattice.hip
 
 #include <string.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-
-#define LAT_D 5
-#define LAT_D1 6
-#define LAT_BITS 12
-#define LAT_BIAS 2048
-#define LAT_MARGIN 20            // nearest point 3 + rank wrap 6 + canonical offset 5 + blur neighbour 5, rounded up
-#define LAT_CHUNK 256
-#define LAT_CMAX 256.0           // colours lie in [0, 256): 8-bit values, or 8-bit values plus a fraction
-#define LAT_NBR (2 * LAT_D1)
-#define LAT_MAX_C 128
-#define LAT_MAX_N (640 * 640)
-#define LAT_ALPHA (1.0f / (1.0f + 0.03125f))
-#define LAT_LOG2E 1.4426950408889634f
-
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
-// ------------------------------------------------------------------------------------------------ structure layout
-// meta[0] = M, meta[1] = flag (1: a colour outside 0..256 was clamped, 2: a key coordinate left the packing), meta[2] = X, the
-// number of extra chunks
-struct Lat {
-    int* meta;
-    float* bary;        // (N, 6) f32 weights, by slot
-    u32* pixvert;       // (N, 6) vertex index of every slot
-    u64* keys[2];       // sort double buffer
-    u32* slots[2];
-    u32* vid;           // vertex index of every sorted entry
-    u32* xid;           // inclusive count of extra-chunk starts
-    u64* ukeys;         // [1..M] sorted unique keys
-    u32* segstart;      // [1..M+1]
-    u32* xstart;        // [X] first entry of an extra chunk
-    u32* xvert;         // [X] its vertex
-    u32* nbr;           // (NE + 1, 12)
-    void* temp;         // rocPRIM
-    size_t temp_bytes;
-    long total;
-};
-
-static inline long lat_align(long b) { return (b + 255) & ~255L; }
-
-static Lat lat_carve(void* base, long N, size_t temp_bytes) {
-    Lat L;
-    const long NE = N * LAT_D1, XC = NE / LAT_CHUNK + 2;
-    char* p = (char*)base;
-    long o = 0;
-    auto take = [&](long bytes) { char* r = p + o; o += lat_align(bytes); return r; };
-    L.meta = (int*)take(64);
-    L.bary = (float*)take(4 * NE);
-    L.pixvert = (u32*)take(4 * NE);
-    L.keys[0] = (u64*)take(8 * NE);
-    L.keys[1] = (u64*)take(8 * NE);
-    L.slots[0] = (u32*)take(4 * NE);
-    L.slots[1] = (u32*)take(4 * NE);
-    L.vid = (u32*)take(4 * NE);
-    L.xid = (u32*)take(4 * NE);
-    L.ukeys = (u64*)take(8 * (NE + 1));
-    L.segstart = (u32*)take(4 * (NE + 2));
-    L.xstart = (u32*)take(4 * XC);
-    L.xvert = (u32*)take(4 * XC);
-    L.nbr = (u32*)take(4L * LAT_NBR * (NE + 1));
-    L.temp = take((long)temp_bytes);
-    L.temp_bytes = temp_bytes;
-    L.total = o;
-    return L;
-}
 
 // f32 workspace of the filter / message / inference entries: nrm 2N | Vb N CP | Vp, tmp, G 3 C N | partial (NE / 256 + 2) CP
 struct LatWs {
@@ -118,21 +54,9 @@ static LatWs ws_carve(void* base, long N, int C) {
 }
 
 // ------------------------------------------------------------------------------------------------ build
-struct BuildArgs {
-    const void* img;
-    int is_u8, H, W;
-    double xy_std, rgb_std;
-    double s[LAT_D];
-    u64* keys;
-    u32* slots;
-    float* bary;
-    int* meta;
-};
-
 __global__ __launch_bounds__(256) void lat_build_kernel(BuildArgs A) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= A.H * A.W) return;
-    const int y = i / A.W, x = i - y * A.W;
     double col[3];
     if (A.is_u8) {
         const uint8_t* p = (const uint8_t*)A.img + 3L * i;
@@ -141,95 +65,7 @@ __global__ __launch_bounds__(256) void lat_build_kernel(BuildArgs A) {
         const float* p = (const float*)A.img + 3L * i;
         col[0] = p[0], col[1] = p[1], col[2] = p[2];
     }
-    int flag = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        if (!(col[k] >= 0.0 && col[k] <= LAT_CMAX)) {
-            col[k] = col[k] > LAT_CMAX ? LAT_CMAX : 0.0;          // NaN -> 0
-            flag = 1;
-        }
-    double c[LAT_D];
-    c[0] = ((double)x / A.xy_std) * A.s[0];
-    c[1] = ((double)y / A.xy_std) * A.s[1];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[2 + k] = (col[k] / A.rgb_std) * A.s[2 + k];
-    // elevate
-    double e[LAT_D1], sm = 0.0;
-#pragma unroll
-    for (int j = LAT_D; j >= 1; --j) {
-        e[j] = sm - (double)j * c[j - 1];
-        sm = sm + c[j - 1];
-    }
-    e[0] = sm;
-    // nearest zero-remainder point
-    double rem0[LAT_D1], sumd = 0.0;
-#pragma unroll
-    for (int k = 0; k < LAT_D1; ++k) {
-        const double v = e[k] / (double)LAT_D1;
-        const double up = ceil(v) * (double)LAT_D1, dn = floor(v) * (double)LAT_D1;
-        rem0[k] = (up - e[k] < e[k] - dn) ? up : dn;
-        sumd += rem0[k] / (double)LAT_D1;
-    }
-    const int sum = (int)rint(sumd);
-    // rank
-    int rank[LAT_D1];
-    double delta[LAT_D1];
-#pragma unroll
-    for (int k = 0; k < LAT_D1; ++k) rank[k] = 0, delta[k] = e[k] - rem0[k];
-#pragma unroll
-    for (int a = 0; a < LAT_D1; ++a)
-#pragma unroll
-        for (int b = a + 1; b < LAT_D1; ++b) {
-            const bool lt = delta[a] < delta[b];
-            rank[a] += lt ? 1 : 0;
-            rank[b] += lt ? 0 : 1;
-        }
-#pragma unroll
-    for (int k = 0; k < LAT_D1; ++k) {
-        rank[k] += sum;
-        if (rank[k] < 0) {
-            rank[k] += LAT_D1;
-            rem0[k] += (double)LAT_D1;
-        } else if (rank[k] > LAT_D) {
-            rank[k] -= LAT_D1;
-            rem0[k] -= (double)LAT_D1;
-        }
-    }
-    // barycentric weights (the additions in the restatement's order; adding 0.0 to the other entries changes nothing)
-    double b[LAT_D1 + 1];
-#pragma unroll
-    for (int m = 0; m <= LAT_D1; ++m) b[m] = 0.0;
-#pragma unroll
-    for (int k = 0; k < LAT_D1; ++k) {
-        const double t = (e[k] - rem0[k]) / (double)LAT_D1;
-#pragma unroll
-        for (int m = 0; m <= LAT_D1; ++m) {
-            if (m == LAT_D - rank[k]) b[m] += t;
-            if (m == LAT_D1 - rank[k]) b[m] -= t;
-        }
-    }
-    b[0] += 1.0 + b[LAT_D1];
-    // keys
-    int r0[LAT_D];
-#pragma unroll
-    for (int k = 0; k < LAT_D; ++k) r0[k] = (int)rem0[k];
-#pragma unroll
-    for (int r = 0; r < LAT_D1; ++r) {
-        u64 key = 0;
-#pragma unroll
-        for (int k = 0; k < LAT_D; ++k) {
-            int f = r0[k] + (rank[k] <= LAT_D - r ? r : r - LAT_D1) + LAT_BIAS;
-            if (f < LAT_D1 || f > 2 * LAT_BIAS - 1 - LAT_D1) {          // cannot happen inside the host's bound
-                f = min(max(f, LAT_D1), 2 * LAT_BIAS - 1 - LAT_D1);
-                flag = 2;
-            }
-            key |= (u64)f << (LAT_BITS * (LAT_D - 1 - k));
-        }
-        const long s = (long)i * LAT_D1 + r;
-        A.keys[s] = key;
-        A.slots[s] = (u32)s;
-        A.bary[s] = (float)b[r];
-    }
+    const int flag = lat_point(A, i, col);
     if (flag) A.meta[1] = flag;
 }
 
@@ -331,42 +167,6 @@ __global__ __launch_bounds__(256) void lat_ones_kernel(float* __restrict__ V, lo
 }
 
 // ------------------------------------------------------------------------------------------------ splat
-struct SplatArgs {
-    const float4* V;          // (N, q) float4
-    float4* val;              // (M + 1, q)
-    float4* partial;          // (X, q)
-    const u32* slots;         // sorted
-    const float* bary;
-    const u32* segstart;
-    const u32* xid;
-    const u32* xstart;
-    const u32* xvert;
-    const int* meta;
-    int q, M;
-};
-
-// sum of entries [start, end) of the sorted list, in order, four loads in flight
-__device__ __forceinline__ float4 lat_chunk_sum(const SplatArgs& A, u32 start, u32 end, int c4) {
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (u32 e = start; e < end; e += 4) {
-        float w[4];
-        float4 x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const u32 s = A.slots[min(e + u, end - 1)];
-            w[u] = e + u < end ? A.bary[s] : 0.f;
-            x[u] = A.V[(long)(s / LAT_D1) * A.q + c4];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            acc.x = fmaf(w[u], x[u].x, acc.x);
-            acc.y = fmaf(w[u], x[u].y, acc.y);
-            acc.z = fmaf(w[u], x[u].z, acc.z);
-            acc.w = fmaf(w[u], x[u].w, acc.w);
-        }
-    }
-    return acc;
-}
 
 // the chunks of long segments after their first -> partial rows; grid covers the a-priori bound on X
 __global__ __launch_bounds__(256) void lat_splat_extra_kernel(SplatArgs A, long cap) {
@@ -668,21 +468,32 @@ extern "C" int wc_dcrf_lattice_build(const void* img, int img_is_u8, void* lat, 
     }
     b.img = img, b.is_u8 = img_is_u8, b.H = H, b.W = W, b.xy_std = bi_xy_std, b.rgb_std = bi_rgb_std;
     b.keys = L.keys[1], b.slots = L.slots[1], b.bary = L.bary, b.meta = L.meta;
-    const dim3 ge(wc_cdiv(NE, 256)), blk(256);
-    hipLaunchKernelGGL(lat_build_kernel, dim3(wc_cdiv(N, 256)), blk, 0, st, b);
+    hipLaunchKernelGGL(lat_build_kernel, dim3(wc_cdiv(N, 256)), dim3(256), 0, st, b);
     WC_LAUNCH_CHECK("lat_build_kernel");
+    return lattice_shared::structure(L, NE, st, "wc_dcrf_lattice_build");
+}
+
+// ---- what csrc/energy_lattice.hip shares (lattice_shared.h)
+int lattice_shared::check_bound(int H, int W, float bi_xy_std, float bi_rgb_std, double* s_out, const char* who) {
+    return ::check_bound(H, W, bi_xy_std, bi_rgb_std, s_out, who);
+}
+
+int lattice_shared::temp_bytes(long NE, size_t* bytes, const char* who) { return ::temp_bytes(NE, bytes, who); }
+
+int lattice_shared::structure(const Lat& L, int NE, hipStream_t st, const char* who) {
+    const dim3 ge(wc_cdiv(NE, 256)), blk(256);
     // sort into keys[0] / slots[0], whichever buffer rocPRIM finishes in
     rocprim::double_buffer<u64> dk(L.keys[1], L.keys[0]);
     rocprim::double_buffer<u32> dv(L.slots[1], L.slots[0]);
     size_t tbytes = L.temp_bytes;
     if (rocprim::radix_sort_pairs(L.temp, tbytes, dk, dv, (size_t)NE, 0, LAT_BITS * LAT_D, st) != hipSuccess) {
-        wc_set_error("wc_dcrf_lattice_build: rocPRIM radix sort failed");
+        wc_set_error("%s: rocPRIM radix sort failed", who);
         return WC_ERR_HIP;
     }
     if (dk.current() != L.keys[0]) {
         if (hipMemcpyAsync(L.keys[0], dk.current(), 8L * NE, hipMemcpyDeviceToDevice, st) != hipSuccess ||
             hipMemcpyAsync(L.slots[0], dv.current(), 4L * NE, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-            wc_set_error("wc_dcrf_lattice_build: hipMemcpyAsync failed");
+            wc_set_error("%s: hipMemcpyAsync failed", who);
             return WC_ERR_HIP;
         }
     }
@@ -691,7 +502,7 @@ extern "C" int wc_dcrf_lattice_build(const void* img, int img_is_u8, void* lat, 
     WC_LAUNCH_CHECK("lat_head_kernel");
     tbytes = L.temp_bytes;
     if (rocprim::inclusive_scan(L.temp, tbytes, flags, L.vid, (size_t)NE, rocprim::plus<u32>(), st) != hipSuccess) {
-        wc_set_error("wc_dcrf_lattice_build: rocPRIM scan failed");
+        wc_set_error("%s: rocPRIM scan failed", who);
         return WC_ERR_HIP;
     }
     hipLaunchKernelGGL(lat_vertex_kernel, ge, blk, 0, st, L.keys[0], L.slots[0], L.vid, L.pixvert, L.ukeys, L.segstart, L.meta, NE);
@@ -700,7 +511,7 @@ extern "C" int wc_dcrf_lattice_build(const void* img, int img_is_u8, void* lat, 
     WC_LAUNCH_CHECK("lat_xflag_kernel");
     tbytes = L.temp_bytes;
     if (rocprim::inclusive_scan(L.temp, tbytes, flags, L.xid, (size_t)NE, rocprim::plus<u32>(), st) != hipSuccess) {
-        wc_set_error("wc_dcrf_lattice_build: rocPRIM scan failed");
+        wc_set_error("%s: rocPRIM scan failed", who);
         return WC_ERR_HIP;
     }
     hipLaunchKernelGGL(lat_xchunk_kernel, ge, blk, 0, st, L.vid, L.segstart, L.xid, L.xstart, L.xvert, L.meta, NE);

@@ -21,6 +21,7 @@
 // No atomics anywhere: every output is a fixed-order sum, bit-identical from run to run.
 // Error model (per element of AS, relative to sum_j k |V_j|): dcrf.hip's, for the same arithmetic: eps = 2^-10.
 #include "common.h"
+#include "energy_shared.h"        // what csrc/energy_lattice.hip (the opt-in lattice form of the filter) runs of this file
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -337,5 +338,26 @@ extern "C" int wc_dense_energy_bwd(const float* A, const float* rois, const floa
     hipLaunchKernelGGL(energy_bwd_kernel, dim3(wc_cdiv(p.HW, 256), p.K, p.N), dim3(256), 0, (hipStream_t)stream, A, rois, grad_out,
                        grad_segs, (float)(-2.0 / p.N), p.HW);
     WC_LAUNCH_CHECK("energy_bwd_kernel");
+    return WC_OK;
+}
+
+// ---- what csrc/energy_lattice.hip shares (energy_shared.h)
+int energy_shared::limits(int N, int K, int H, int W, float sigma_rgb, float sigma_xy, const char* who) {
+    EPlan p;
+    return eplan(p, N, K, H, W, sigma_rgb, sigma_xy, who);
+}
+
+int energy_shared::prep(const float* images, const float* segs, const float* rois, const void* unlabel_u8, float* feat, float* V,
+                        float* gate, int N, int K, int H, int W, hipStream_t st) {
+    const int HW = H * W, CP = 32 * ((K + 31) / 32);
+    hipLaunchKernelGGL(energy_prep_kernel, dim3(wc_cdiv(HW, EN_PP), N), dim3(256), 0, st, images, segs, rois,
+                       (const uint8_t*)unlabel_u8, feat, V, gate, K, CP, HW, W);
+    WC_LAUNCH_CHECK("energy_prep_kernel");
+    return WC_OK;
+}
+
+int energy_shared::finish(const float* part, long n, double scale, float* loss, hipStream_t st) {
+    hipLaunchKernelGGL(energy_finish_kernel, dim3(1), dim3(256), 0, st, part, n, scale, loss);
+    WC_LAUNCH_CHECK("energy_finish_kernel");
     return WC_OK;
 }

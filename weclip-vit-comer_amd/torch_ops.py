@@ -444,6 +444,42 @@ def _energy_term_backward(ctx, grad_loss, grad_grad):
 torch.library.register_autograd(f"{_LIB}::energy_term", _energy_term_backward, setup_context=_energy_term_setup)
 
 
+@torch.library.custom_op(f"{_LIB}::dense_energy_lattice", mutates_args=(), device_types="cuda")
+def dense_energy_lattice(images: Tensor, segmentations: Tensor, rois: Tensor, unlabel_region: Tensor, sigma_rgb: float,
+                         sigma_xy: float) -> Tuple[Tensor, Tensor]:
+    """weclip::dense_energy with the permutohedral lattice as the bilateral filter (csrc/energy_lattice.hip, DESIGN.md section
+    15.3; opt-in, about half the exact AS) -> (loss (1,), A (N,K,H,W) = Gate * AS).  Differentiable in `segmentations` through the
+    same weclip::dense_energy_bwd."""
+    from .utils.losses import dense_energy_forward
+    loss, A, _ = dense_energy_forward(images, segmentations, sigma_rgb, sigma_xy, rois, unlabel_region, "lattice")
+    return loss, A
+
+
+@dense_energy_lattice.register_fake
+def _(images, segmentations, rois, unlabel_region, sigma_rgb, sigma_xy):
+    return segmentations.new_empty((1,), dtype=F32), segmentations.new_empty(segmentations.shape, dtype=F32)
+
+
+torch.library.register_autograd(f"{_LIB}::dense_energy_lattice", _energy_backward, setup_context=_energy_setup)
+
+
+@torch.library.custom_op(f"{_LIB}::energy_term_lattice", mutates_args=(), device_types="cuda")
+def energy_term_lattice(img: Tensor, seg_lowres: Tensor, label: Tensor, img_box: Optional[Tensor], weight: float, sigma_rgb: float,
+                        sigma_xy: float, scale_factor: float, mean: List[float], std: List[float]) -> Tuple[Tensor, Tensor]:
+    """weclip::energy_term with the permutohedral lattice as the bilateral filter (csrc/energy_lattice.hip): same arguments, same
+    outputs, same autograd."""
+    from .utils.losses import energy_term as term
+    return term(img, seg_lowres, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, list(mean), list(std), bilateral="lattice")
+
+
+@energy_term_lattice.register_fake
+def _(img, seg_lowres, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std):
+    return seg_lowres.new_empty((1,), dtype=F32), seg_lowres.new_empty(seg_lowres.shape, dtype=F32)
+
+
+torch.library.register_autograd(f"{_LIB}::energy_term_lattice", _energy_term_backward, setup_context=_energy_term_setup)
+
+
 @torch.library.custom_op(f"{_LIB}::aff_propagate", mutates_args=(), device_types="cuda")
 def aff_propagate(aff: Tensor, cams: Tensor, mask: Optional[Tensor], cls: Optional[Tensor], bkg_score: float,
                   with_bkg: bool) -> Tensor:
@@ -511,4 +547,4 @@ def _(attns, size, n_pix, n_row):
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
        "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
-       "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice")
+       "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice", "dense_energy_lattice", "energy_term_lattice")

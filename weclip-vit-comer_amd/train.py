@@ -3,7 +3,7 @@ scripts/dist_clip_coco.py) around this package's graph-replayed step.
 
     python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
         [--dataset voc|coco|seg] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
-        [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>]] [--panel_iters N]
+        [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>] [--reg_bilateral exact|lattice]] [--panel_iters N]
 
 The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
 into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is counted by `wc_label_match_count`
@@ -119,10 +119,13 @@ def build_parser():
     p.add_argument("--resume", type=str, default=None, help="a WeCLIP_model_iter_N.pth; its train_state_iter_N.pth is loaded with it")
     p.add_argument("--reg_loss", action="store_true",
                    help="add the dense energy (regularised) loss to the step; its all-pairs filter costs about four plain steps at "
-                        "batch 16 / crop 512 (DESIGN.md section 15.2)")
+                        "batch 16 / crop 512 (DESIGN.md section 15.2; --reg_bilateral lattice: half a step, section 15.3)")
     p.add_argument("--reg_coef", type=float, default=0.01, help="weight of the energy term in the step's loss")
     p.add_argument("--reg_scale", type=float, default=0.5, choices=(1.0, 0.5, 0.25), help="scale_factor of the DenseEnergyLoss")
     p.add_argument("--reg_start", type=int, default=None, help="the term starts after this iteration (default: train.cam_iters)")
+    p.add_argument("--reg_bilateral", type=str, default="exact", choices=("exact", "lattice"),
+                   help="the term's bilateral filter: the exact all-pairs sum, or the permutohedral lattice (much cheaper; about half "
+                        "the exact value, so --reg_coef does not carry over; DESIGN.md section 15.3)")
     p.add_argument("--panel_iters", type=int, default=0,
                    help="rank 0 writes the image panels (<work_dir>/panels/iter_<n>_<name>.png) every this many iterations; 0: off")
     return p
@@ -197,8 +200,11 @@ def reg_settings(cfg, args):
     if not getattr(args, "reg_loss", False):
         return None
     start = getattr(args, "reg_start", None)
-    return {"coef": float(getattr(args, "reg_coef", 0.01)), "scale_factor": float(getattr(args, "reg_scale", 0.5)),
-            "start_iter": int(cfg.train.cam_iters if start is None else start)}
+    reg = {"coef": float(getattr(args, "reg_coef", 0.01)), "scale_factor": float(getattr(args, "reg_scale", 0.5)),
+           "start_iter": int(cfg.train.cam_iters if start is None else start)}
+    if getattr(args, "reg_bilateral", "exact") != "exact":      # without the flag the settings are what they were
+        reg["bilateral"] = str(args.reg_bilateral)
+    return reg
 
 
 def strict_json(v):

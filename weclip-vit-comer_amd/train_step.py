@@ -36,10 +36,12 @@ class RegTerm:
     or an object with any of
         coef (0.01): the term's weight in the step's loss;  start_iter (0): the term is active at 1-based step numbers > start_iter;
         weight (1e-7), sigma_rgb (15), sigma_xy (100), scale_factor (0.5): the DenseEnergyLoss, the lineage's parameters.
+        bilateral ("exact"): the term's filter, "exact" or "lattice" (utils.losses).  The lattice's
+        workspaces are allocated once per (batch, classes, scaled size) and kept; the filter is part of the graph signature.
     `coef` and `start_iter` are this package's choice (the reference checkout never calls its get_energy_loss; DESIGN.md
     section 15.2).  scale_factor must be 1, 0.5 or 0.25 (utils.losses.get_energy_loss_fused)."""
 
-    DEFAULTS = dict(coef=0.01, weight=1e-7, sigma_rgb=15, sigma_xy=100, scale_factor=0.5, start_iter=0)
+    DEFAULTS = dict(coef=0.01, weight=1e-7, sigma_rgb=15, sigma_xy=100, scale_factor=0.5, start_iter=0, bilateral="exact")
 
     @classmethod
     def of(cls, reg):
@@ -56,7 +58,9 @@ class RegTerm:
         if float(self.scale_factor) not in (1.0, 0.5, 0.25):
             raise ValueError(f"reg: scale_factor must be 1, 0.5 or 0.25, got {self.scale_factor}")
         self.start_iter = int(self.start_iter)
-        self.layer = DenseEnergyLoss(self.weight, self.sigma_rgb, self.sigma_xy, self.scale_factor)
+        self.layer = DenseEnergyLoss(self.weight, self.sigma_rgb, self.sigma_xy, self.scale_factor, self.bilateral)   # ValueError
+        if self.bilateral != "exact":
+            self.layer.workspace_cache = {}
         self.step_num = 0                    # steps begun (1-based number of the current one)
 
     def begin_step(self):
@@ -178,6 +182,8 @@ class _StepBase:
         signature; `img_box` goes through a static (B, 4) buffer."""
         m = self.model
         sig = self._signature(img, target) + ((True,) if reg_active else ())
+        if reg_active and self.reg.bilateral != "exact":
+            sig += (self.reg.bilateral,)
         ent = self._graphs.get(sig)
         first = ent is None
         if first:

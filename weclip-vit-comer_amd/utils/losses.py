@@ -178,6 +178,7 @@ def get_aff_loss_fused(attn_pred, cam_label, radius=8, ignore_index=255):
 # Dense energy (regularised CRF) loss: reference utils/losses.py:35-116 with the `bilateralfilter_batch` call as the exact
 # all-pairs sum on the GPU (csrc/energy.hip, C ABI `wc_energy_*` / `wc_dense_energy_*`).  The
 # reference's extension (a permutohedral lattice) is not shipped with it; parity with the lattice is unpinned.
+# bilateral="lattice" (opt-in, csrc/energy_lattice.hip) is our own lattice in the filter's place.
 def _energy_workspace(N, K, H, W, device):
     import ctypes
     from .. import _lib as L
@@ -194,26 +195,70 @@ def _energy_shapes(images, segs, who):
     return segs.shape
 
 
-def bilateral_filter_batch(images, segs, sigma_rgb, sigma_xy):
+BILATERAL_MODES = ("exact", "lattice")
+
+
+def _bilateral_mode(bilateral, who):
+    """Checks the filter's name before anything is allocated: "exact" (the all-pairs sum, the default everywhere) or "lattice"
+    (the permutohedral lattice, csrc/energy_lattice.hip)."""
+    if bilateral not in BILATERAL_MODES:
+        raise ValueError(f"{who}: bilateral must be 'exact' or 'lattice', got {bilateral!r}")
+    return bilateral
+
+
+def _lattice_workspace(N, K, H, W, device, cache=None):
+    """(lat, ws) byte tensors of the wc_*_lattice energy entries, sized by wc_energy_lattice_workspace_bytes alone.  `cache`
+    (a dict, or None): one pair per (N, K, H, W, device), allocated on the first request and reused from then on."""
+    import ctypes
+    from .. import _lib as L
+    key = (N, K, H, W, str(device))
+    if cache is not None and key in cache:
+        return cache[key]
+    a, b = ctypes.c_long(), ctypes.c_long()
+    L.lib().wc_energy_lattice_workspace_bytes(N, K, H, W, ctypes.byref(a), ctypes.byref(b))
+    pair = tuple(torch.empty(n.value, device=device, dtype=torch.uint8) for n in (a, b))
+    if cache is not None:
+        cache[key] = pair
+    return pair
+
+
+def lattice_vertex_counts(lat, N):
+    """(flag, M (N,)) of the last lattice call on the structure `lat`: flag != 0 when a colour lay outside [0, 256] and was
+    clamped for the key; M the number of lattice vertices of every image.  Reading them synchronises; the entries never do."""
+    meta = lat[:4 * (16 + N)].view(torch.int32)
+    return meta[1], meta[16:16 + N]
+
+
+def bilateral_filter_batch(images, segs, sigma_rgb, sigma_xy, bilateral="exact", workspace=None):
     """AS (N, K, H, W) f32 on the device: AS(n, k, i) = sum_j exp(-|p_i - p_j|^2 / (2 sigma_xy^2) - |I_n,i - I_n,j|^2 /
     (2 sigma_rgb^2)) segs(n, k, j) over every pixel j of image n (j = i included): what the reference's
     `bilateralfilter_batch(images, segs, AS, N, K, H, W, sigma_rgb, sigma_xy)` (losses.py:75) approximates.  images
-    (N, 3, H, W) on the 0..255 scale; segs may be signed.  No autograd."""
+    (N, 3, H, W) on the 0..255 scale; segs may be signed.  No autograd.
+    bilateral="lattice": the same call with the permutohedral lattice as the filter (un-normalised, what the reference's extension
+    is; about half the exact AS); workspace: a (lat, ws) pair of `_lattice_workspace` to use instead of allocating one."""
     from .. import _lib as L
+    _bilateral_mode(bilateral, "bilateral_filter_batch")
     L.require_gpu()
     N, K, H, W = _energy_shapes(images, segs, "bilateral_filter_batch")
     img = images.detach().float().contiguous()
     seg = segs.detach().float().contiguous()
     AS = torch.empty_like(seg)
+    if bilateral == "lattice":
+        lat, ws = workspace or _lattice_workspace(N, K, H, W, seg.device)
+        L.lib().wc_bilateral_filter_batch_lattice(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segs"), L.ptr(AS),
+                                                  L.ptr(lat), L.ptr(ws), N, K, H, W, float(sigma_rgb), float(sigma_xy), L.stream())
+        return AS
     ws = _energy_workspace(N, K, H, W, seg.device)
     L.lib().wc_bilateral_filter_batch(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segs"), L.ptr(AS), L.ptr(ws),
                                       N, K, H, W, float(sigma_rgb), float(sigma_xy), L.stream())
     return AS
 
 
-def dense_energy_forward(images, segs, sigma_rgb, sigma_xy, rois, unlabel_region):
-    """(loss (1,), A (N, K, H, W) = Gate * AS, Gate (N, H, W)) of DenseEnergyLossFunction.forward, all on the device."""
+def dense_energy_forward(images, segs, sigma_rgb, sigma_xy, rois, unlabel_region, bilateral="exact", workspace=None):
+    """(loss (1,), A (N, K, H, W) = Gate * AS, Gate (N, H, W)) of DenseEnergyLossFunction.forward, all on the device.
+    bilateral, workspace: as in `bilateral_filter_batch`."""
     from .. import _lib as L
+    _bilateral_mode(bilateral, "DenseEnergyLossFunction")
     L.require_gpu()
     N, K, H, W = _energy_shapes(images, segs, "DenseEnergyLossFunction")
     if tuple(rois.shape) != (N, H, W) or tuple(unlabel_region.shape) != (N, H, W):
@@ -226,6 +271,13 @@ def dense_energy_forward(images, segs, sigma_rgb, sigma_xy, rois, unlabel_region
     A = torch.empty_like(seg)
     gate = torch.empty_like(roi)
     loss = torch.empty(1, device=seg.device, dtype=torch.float32)
+    if bilateral == "lattice":
+        lat, ws = workspace or _lattice_workspace(N, K, H, W, seg.device)
+        L.lib().wc_dense_energy_fwd_lattice(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segmentations"),
+                                            L.ptr(roi, torch.float32, "ROIs"), L.ptr(unl, torch.uint8, "unlabel_region"), L.ptr(A),
+                                            L.ptr(gate), L.ptr(loss), L.ptr(lat), L.ptr(ws), N, K, H, W, float(sigma_rgb),
+                                            float(sigma_xy), L.stream())
+        return loss, A, gate
     ws = _energy_workspace(N, K, H, W, seg.device)
     L.lib().wc_dense_energy_fwd(L.ptr(img, torch.float32, "images"), L.ptr(seg, torch.float32, "segmentations"),
                                 L.ptr(roi, torch.float32, "ROIs"), L.ptr(unl, torch.uint8, "unlabel_region"), L.ptr(A), L.ptr(gate),
@@ -255,29 +307,37 @@ class DenseEnergyLossFunction(torch.autograd.Function):
     """loss (1,) = -(1/N) sum S * Gate * AS with S = segmentations * ROIs, AS the bilateral filter of S and
     Gate = ROIs - max_k segmentations, 1 where unlabelled, 0 where negative (reference losses.py:52-91; argument order as
     there).  backward gives -2 * grad * Gate * AS * ROIs / N to `segmentations` and nothing else: the Gate is held constant
-    and the factor 2 stands for the kernel's symmetry, as in the reference -- not the true derivative where the Gate varies."""
+    and the factor 2 stands for the kernel's symmetry, as in the reference -- not the true derivative where the Gate varies.
+    An optional seventh argument, bilateral ("exact", the default, or "lattice"), chooses the filter; with the lattice the
+    factor 2 is an approximation in a second sense, because that filter is not a symmetric matrix."""
 
     @staticmethod
-    def forward(ctx, images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region):
-        loss, A, _ = dense_energy_forward(images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region)
+    def forward(ctx, images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region, *bilateral):
+        if len(bilateral) > 1:
+            raise TypeError("DenseEnergyLossFunction: at most one argument (bilateral) after unlabel_region")
+        loss, A, _ = dense_energy_forward(images, segmentations, sigma_rgb, sigma_xy, ROIs, unlabel_region, *bilateral)
         ctx.save_for_backward(A, ROIs)
+        ctx.n_extra = len(bilateral)
         return loss
 
     @staticmethod
     def backward(ctx, grad_output):
         A, rois = ctx.saved_tensors
-        return None, dense_energy_backward(grad_output, A, rois), None, None, None, None
+        return (None, dense_energy_backward(grad_output, A, rois), None, None, None, None) + (None,) * ctx.n_extra
 
 
 class DenseEnergyLoss(torch.nn.Module):
     """reference losses.py:94-116: the loss at `scale_factor` of the input size, times `weight`.  Images, ROIs and the label
     map are resampled nearest, the segmentations bilinear (align_corners=False); a label of 255 marks a pixel unlabelled;
-    sigma_xy shrinks with the image."""
+    sigma_xy shrinks with the image.  bilateral="lattice" (ours; default "exact"): the permutohedral-lattice filter; its AS is
+    about half the exact one, so a `weight` tuned for one mode does not carry over to the other."""
 
-    def __init__(self, weight, sigma_rgb, sigma_xy, scale_factor):
+    def __init__(self, weight, sigma_rgb, sigma_xy, scale_factor, bilateral="exact"):
         super().__init__()
+        self.bilateral = _bilateral_mode(bilateral, "DenseEnergyLoss")
         self.weight, self.scale_factor = weight, scale_factor
         self.sigma_rgb, self.sigma_xy = sigma_rgb, sigma_xy
+        self.workspace_cache = None          # a dict here makes get_energy_loss_fused keep its lattice workspaces
 
     def _resample(self, x, mode="nearest"):
         kw = dict(align_corners=False) if mode == "bilinear" else {}
@@ -286,13 +346,16 @@ class DenseEnergyLoss(torch.nn.Module):
     def forward(self, images, segmentations, ROIs, seg_label):
         unlabelled = self._resample(seg_label).long().eq(255)[:, 0]
         rois = self._resample(ROIs[:, None])[:, 0]
+        extra = () if self.bilateral == "exact" else (self.bilateral,)
         energy = DenseEnergyLossFunction.apply(self._resample(images), self._resample(segmentations, "bilinear"), self.sigma_rgb,
-                                               self.sigma_xy * self.scale_factor, rois, unlabelled)
+                                               self.sigma_xy * self.scale_factor, rois, unlabelled, *extra)
         return self.weight * energy
 
     def extra_repr(self):
         # nn.Module prints this between the brackets: the order and names are the reference's
         fields = ("sigma_rgb", "sigma_xy", "weight", "scale_factor")
+        if self.bilateral != "exact":
+            fields += ("bilateral",)
         return ", ".join(f"{k}={getattr(self, k)}" for k in fields)
 
 
@@ -402,10 +465,13 @@ def energy_prep_backward(A, rois_s, seg, coef, size, e):
     return grad
 
 
-def energy_term(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std, need_grad=True):
+def energy_term(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std, need_grad=True, bilateral="exact",
+                workspace_cache=None):
     """(weight * loss (1,), d(weight * loss) / d seg for an upstream gradient of 1, or None) of get_energy_loss_fused:
-    wc_energy_prep_fwd, the filter (wc_dense_energy_fwd, unchanged), wc_energy_prep_bwd.  No host synchronisation."""
+    wc_energy_prep_fwd, the filter (wc_dense_energy_fwd, unchanged, or wc_dense_energy_fwd_lattice when bilateral="lattice"),
+    wc_energy_prep_bwd.  No host synchronisation.  workspace_cache: a dict that keeps the lattice's workspaces between calls."""
     from .. import _lib as L
+    _bilateral_mode(bilateral, "get_energy_loss_fused")
     e = _energy_term_check(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_factor, mean, std)
     L.require_gpu()
     dev = seg.device
@@ -421,9 +487,15 @@ def energy_term(img, seg, label, img_box, weight, sigma_rgb, sigma_xy, scale_fac
     images_s, P_s, rois_s, unl = energy_prep_forward(img, seg, label, box, e, mean, std)
     Hs, Ws = rois_s.shape[1:]
     A, gate, loss = torch.empty_like(P_s), torch.empty_like(rois_s), torch.empty(1, device=dev, dtype=torch.float32)
-    L.lib().wc_dense_energy_fwd(L.ptr(images_s), L.ptr(P_s), L.ptr(rois_s), L.ptr(unl), L.ptr(A), L.ptr(gate), L.ptr(loss),
-                                L.ptr(_energy_workspace(N, K, Hs, Ws, dev)), N, K, Hs, Ws, float(sigma_rgb),
-                                float(sigma_xy * scale_factor), L.stream())
+    if bilateral == "lattice":
+        lat, ws = _lattice_workspace(N, K, Hs, Ws, dev, workspace_cache)
+        L.lib().wc_dense_energy_fwd_lattice(L.ptr(images_s), L.ptr(P_s), L.ptr(rois_s), L.ptr(unl), L.ptr(A), L.ptr(gate), L.ptr(loss),
+                                            L.ptr(lat), L.ptr(ws), N, K, Hs, Ws, float(sigma_rgb), float(sigma_xy * scale_factor),
+                                            L.stream())
+    else:
+        L.lib().wc_dense_energy_fwd(L.ptr(images_s), L.ptr(P_s), L.ptr(rois_s), L.ptr(unl), L.ptr(A), L.ptr(gate), L.ptr(loss),
+                                    L.ptr(_energy_workspace(N, K, Hs, Ws, dev)), N, K, Hs, Ws, float(sigma_rgb),
+                                    float(sigma_xy * scale_factor), L.stream())
     grad = energy_prep_backward(A, rois_s, seg, -2.0 * float(weight) / N, label.shape[1:], e) if need_grad else None
     return weight * loss, grad
 
@@ -433,8 +505,12 @@ class _EnergyTermFn(torch.autograd.Function):
     backward only scales it."""
 
     @staticmethod
-    def forward(ctx, seg, img, label, img_box, params, mean, std):
-        loss, grad = energy_term(img, seg, label, img_box, *params, mean, std, need_grad=ctx.needs_input_grad[0])
+    def forward(ctx, seg, img, label, img_box, params, mean, std, *opt):
+        bilateral = opt[0] if opt else "exact"                 # optional: the filter, then a workspace cache
+        workspace_cache = opt[1] if len(opt) > 1 else None
+        loss, grad = energy_term(img, seg, label, img_box, *params, mean, std, need_grad=ctx.needs_input_grad[0], bilateral=bilateral,
+                                 workspace_cache=workspace_cache)
+        ctx.n_in = 7 + len(opt)
         if grad is not None:
             ctx.save_for_backward(grad)
         return loss
@@ -442,7 +518,7 @@ class _EnergyTermFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return (grad * g,) + (None,) * 6
+        return (grad * g,) + (None,) * (ctx.n_in - 1)
 
 
 def get_energy_loss_fused(img, seg_lowres, label, img_box, loss_layer, mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375]):
@@ -451,9 +527,13 @@ def get_energy_loss_fused(img, seg_lowres, label, img_box, loss_layer, mean=[123
     those), without the up-sampled logits, their soft-max or a full-resolution gradient.  img (N, 3, H, W) normalised,
     seg_lowres (N, K, h, w), 1 <= K <= 128, label (N, H, W) integer; img_box: None (the whole image), rows (y0, y1, x0, x1), or
     an integer tensor (N, 4) on the host or on the device -- a device tensor is never read on the host (rows with 0 <= y0, x0;
-    Python's negative slice indices are not emulated).  Returns weight * loss, shape (1,); the Gate is a constant in backward."""
+    Python's negative slice indices are not emulated).  Returns weight * loss, shape (1,); the Gate is a constant in backward.
+    The filter follows loss_layer.bilateral ("exact" when the layer has none)."""
     try:
         params = tuple(getattr(loss_layer, k) for k in ("weight", "sigma_rgb", "sigma_xy", "scale_factor"))
     except AttributeError:
         raise TypeError("get_energy_loss_fused: loss_layer must be a DenseEnergyLoss (weight, sigma_rgb, sigma_xy, scale_factor)") from None
-    return _EnergyTermFn.apply(seg_lowres, img, label, img_box, params, mean, std)
+    bilateral = _bilateral_mode(getattr(loss_layer, "bilateral", "exact"), "get_energy_loss_fused")
+    if bilateral == "exact":
+        return _EnergyTermFn.apply(seg_lowres, img, label, img_box, params, mean, std)
+    return _EnergyTermFn.apply(seg_lowres, img, label, img_box, params, mean, std, bilateral, getattr(loss_layer, "workspace_cache", None))
