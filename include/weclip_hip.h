@@ -951,6 +951,40 @@ int wc_panel_heat(const float* src, long sB, long sC, int C, int h, int w, int a
 int wc_panel_snapshot(const float* seg, long n_seg, const long* label, long n_label, const float* attn, int B, int hw,
                       const int* rows4, float* seg_out, void* label_out, float* rows_out, void* stream);
 
+/* ---- multi-bandwidth RBF MMD loss of utils/mmdloss.py (csrc/mmd.hip) ---------------------------- */
+/* source, target (B, d) row-major, both f32 (is_half = 0) or both fp16 (is_half = 1); X = cat(source, target), N = 2 B rows.
+ * All arithmetic in f32 (sums that cross rows in f64).  With L2_ij = |x_i - x_j|^2:
+ *   bandwidth = fix_sigma, or sum_ij L2_ij / (N^2 - N) when fix_sigma == 0 (utils/mmdloss.py:25-28; formed as
+ *   2 sum_i |x_i - mean|^2 / (N - 1), no N x N pass), then / kernel_mul^(kernel_num / 2) (:30); bw_b = bandwidth * kernel_mul^b
+ *   (:31); K_ij = sum_b exp(-L2_ij / bw_b) (:33-35); W_ij = sum_b exp(-L2_ij / bw_b) / bw_b.
+ * The bandwidth is a device scalar and never read on the host.  With a_i = x_i minus the mean of its own block (source or
+ * target) and delta = source mean - target mean, L2 is formed on the f32-input MFMA as |a_i|^2 + |a_j|^2 - 2 a_i.a_j inside a
+ * block and (|a_i|^2 + 2 s_i delta.a_i) + (|a_j|^2 + 2 s_j delta.a_j) + |delta|^2 - 2 a_i.a_j across the blocks, clamped at 0,
+ * and is exactly 0 on the diagonal (K_ii = kernel_num exactly): neither a common offset of the data nor the distance between
+ * the two sets enters a cancellation.  kernel_mul == 2
+ * takes one exponential and kernel_num - 1 squarings, every other kernel_mul kernel_num exponentials.
+ * Limits (WC_ERR_ARG "bad argument", nothing launched): non-null pointers (grad may be NULL), 1 <= B <= 2^20, 1 <= d <= 8192,
+ * 1 <= kernel_num <= 8, kernel_mul finite and > 0, fix_sigma finite, ws 256-byte aligned.  No allocation, no host
+ * synchronisation, every launch on `stream`; no atomics, fixed-order sums: bit-identical from run to run.  All rows identical
+ * with fix_sigma == 0: bandwidth 0 and a NaN loss, as in the reference.
+ * Error model against fp64 on the same inputs, eps = 2^-16: |loss - loss64| <= eps * A + 2^-24, A = (1/B^2) sum_ij K_ij;
+ * |K_ij - K64_ij| <= eps * K64_ij + 2^-24; |g_ic - g64_ic| <= eps * G_ic + 2^-24,
+ * G_ic = (4/B^2) (sum_j W_ij |x_ic| + sum_j W_ij |x_jc|).
+ * wc_mmd_workspace_bytes: *n_bytes (HOST out-parameter), with dp = 32 ceil(d/32), nt = ceil(N/64), js = min(nt, max(1, 1024/nt))
+ *                    and every piece rounded up to 256 bytes: 8*64*dp + 8*nt*js + 8*dp + 4*N + 4*N + 68 + 4*N*dp: O(N d + tiles).
+ * wc_mmd_rbf:        utils/mmdloss.py:38-59 for n == m == B: loss (1) f32 = (1/B^2) sum_ij s_i s_j K_ij, s = +1 on source rows,
+ *                    -1 on target rows.  grad (N, d) f32 or NULL: rows 0..B-1 = d loss / d source, rows B..N-1 = d loss / d target,
+ *                    with the bandwidth a constant as in the reference (:28 `.data`):
+ *                    grad_i = -(4/B^2) s_i ((sum_j s_j W_ij) x_i - sum_j s_j W_ij x_j).  With grad the d columns are processed in
+ *                    chunks of 128, S = X X^T recomputed per chunk; without it the second product is skipped and only the upper
+ *                    triangle of tiles is visited.
+ * wc_mmd_rbf_kernel: utils/mmdloss.py:4-35: K (N, N) f32, symmetric bit for bit. */
+int wc_mmd_workspace_bytes(int B, int d, long* n_bytes);
+int wc_mmd_rbf(const void* source, const void* target, int is_half, float* loss, float* grad, void* ws, int B, int d,
+               int kernel_num, double kernel_mul, double fix_sigma, void* stream);
+int wc_mmd_rbf_kernel(const void* source, const void* target, int is_half, float* K, void* ws, int B, int d, int kernel_num,
+                      double kernel_mul, double fix_sigma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,7 +82,8 @@ def install_dropin(reference_root=None, datasets=False):
     `utils` resolves to this package's `utils` (losses, camutils, optimizer, evaluate, AverageMeter: the
     modules on the hot path or imported next to it by the training script, `utils.losses` with every name of the
     reference's, `DenseEnergyLoss` / `get_energy_loss` included; dcrf: the GPU dense CRF behind the eval scripts'
-    `from utils.dcrf import DenseCRF`).  `reference_root`, if given, is a checkout of the reference
+    `from utils.dcrf import DenseCRF`; mmdloss: `from utils.mmdloss import mmd_rbf, rbf_kernel`, the multi-bandwidth RBF MMD as
+    a tile-streamed kernel pair that never forms the (N, N, d) tensor, equal row counts only).  `reference_root`, if given, is a checkout of the reference
     whose `utils/` directory is appended to that package's search path, so the helper modules this package does
     not provide (imutils, ...) still import from the user's tree; its `clip/` directory is appended to the `clip`
     package's path the same way (`from clip.clip_text import new_class_names, BACKGROUND_CATEGORY`, and the BPE merges

@@ -440,3 +440,85 @@ class WeightCache:
     def wT(self, name):
         """(Split (C, ldT), ldT): the backward's W^T operand (K = R contiguous, zero padded to ldT)."""
         return self.views[name][1], self.views[name][2]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Multi-bandwidth RBF MMD (reference utils/mmdloss.py; csrc/mmd.hip, C ABI `wc_mmd_*`; DESIGN.md section 18)
+MMD_MAX_D = 8192
+MMD_MAX_KERNELS = 8
+_mmd_ws = {}
+
+
+def mmd_check(source, target, kernel_mul, kernel_num, fix_sigma, who):
+    """Argument errors of utils.mmdloss, raised on the host before anything touches a device: -> (B, d, fix) with fix the
+    bandwidth as a float, 0.0 when it comes from the data (`fix_sigma` falsy, reference utils/mmdloss.py:25)."""
+    for name, t in (("source", source), ("target", target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{who}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be 2-D (rows, features), got {tuple(t.shape)}")
+    if source.shape[1] != target.shape[1]:
+        raise ValueError(f"{who}: feature widths differ: source {tuple(source.shape)}, target {tuple(target.shape)}")
+    if source.shape[0] != target.shape[0]:
+        raise ValueError(f"{who}: source has {source.shape[0]} rows and target {target.shape[0]}: the four blocks of the kernel "
+                         "matrix add only for equal row counts (the reference raises or broadcasts there)")
+    B, d = source.shape
+    if B < 1 or d < 1:
+        raise ValueError(f"{who}: empty input {tuple(source.shape)}")
+    if d > MMD_MAX_D:
+        raise ValueError(f"{who}: bad argument: d = {d} above the supported {MMD_MAX_D}")
+    if source.dtype != target.dtype or source.dtype not in (F32, F16):
+        raise ValueError(f"{who}: source and target must both be float32 or both float16, got {source.dtype} and {target.dtype}")
+    if source.device != target.device:
+        raise ValueError(f"{who}: source is on {source.device}, target on {target.device}")
+    if int(kernel_num) != kernel_num or not 1 <= int(kernel_num) <= MMD_MAX_KERNELS:
+        raise ValueError(f"{who}: kernel_num must be an integer in [1, {MMD_MAX_KERNELS}], got {kernel_num!r}")
+    if not (float(kernel_mul) > 0.0 and math.isfinite(float(kernel_mul))):
+        raise ValueError(f"{who}: kernel_mul must be finite and > 0, got {kernel_mul!r}")
+    fix = float(fix_sigma) if fix_sigma else 0.0
+    if not math.isfinite(fix):
+        raise ValueError(f"{who}: fix_sigma must be finite, got {fix_sigma!r}")
+    return B, d, fix
+
+
+def mmd_device(source, who):
+    L.require_gpu()
+    if not source.is_cuda:
+        raise RuntimeError(f"{who}: needs its tensors on an AMD GPU, got device {source.device}; there is no CPU path")
+
+
+def mmd_workspace(B, d, device):
+    """The byte workspace of the wc_mmd_* entries, one per (N, d, device), kept between calls."""
+    key = (2 * B, d, str(device))
+    ws = _mmd_ws.get(key)
+    if ws is None:
+        n = ctypes.c_long()
+        L.lib().wc_mmd_workspace_bytes(B, d, ctypes.byref(n))
+        ws = _mmd_ws[key] = torch.empty(n.value, device=device, dtype=torch.uint8)
+    return ws
+
+
+def mmd_rbf(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None, need_grad=False):
+    """-> (loss () f32, grad (2B, d) f32 or None): reference utils/mmdloss.py:38-59 and, with need_grad, d loss / d cat(source,
+    target) for an upstream gradient of 1 (the bandwidth a constant, as :28).  No host synchronisation."""
+    B, d, fix = mmd_check(source, target, kernel_mul, kernel_num, fix_sigma, "mmd_rbf")
+    mmd_device(source, "mmd_rbf")
+    src, tgt = source.detach().contiguous(), target.detach().contiguous()
+    dev = src.device
+    loss = torch.empty((), device=dev, dtype=F32)
+    grad = torch.empty(2 * B, d, device=dev, dtype=F32) if need_grad else None
+    L.lib().wc_mmd_rbf(L.ptr(src), L.ptr(tgt), int(src.dtype == F16), L.ptr(loss), L.ptr(grad), L.ptr(mmd_workspace(B, d, dev)),
+                       B, d, int(kernel_num), float(kernel_mul), fix, L.stream())
+    return loss, grad
+
+
+def mmd_rbf_kernel(source, target, kernel_mul=2.0, kernel_num=5, fix_sigma=None):
+    """-> K (2B, 2B) f32: reference utils/mmdloss.py:4-35, symmetric bit for bit, diagonal exactly kernel_num."""
+    B, d, fix = mmd_check(source, target, kernel_mul, kernel_num, fix_sigma, "rbf_kernel")
+    mmd_device(source, "rbf_kernel")
+    src, tgt = source.detach().contiguous(), target.detach().contiguous()
+    dev = src.device
+    K = torch.empty(2 * B, 2 * B, device=dev, dtype=F32)
+    L.lib().wc_mmd_rbf_kernel(L.ptr(src), L.ptr(tgt), int(src.dtype == F16), L.ptr(K), L.ptr(mmd_workspace(B, d, dev)), B, d,
+                              int(kernel_num), float(kernel_mul), fix, L.stream())
+    return K

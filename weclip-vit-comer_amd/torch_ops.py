@@ -544,7 +544,59 @@ def _(attns, size, n_pix, n_row):
     return attns[0].new_empty((3, g.canvas_h, g.canvas_w), dtype=torch.uint8)
 
 
+
+@torch.library.custom_op(f"{_LIB}::mmd_rbf", mutates_args=(), device_types="cuda")
+def mmd_rbf(source: Tensor, target: Tensor, kernel_mul: float, kernel_num: int, fix_sigma: float,
+            need_grad: bool) -> Tuple[Tensor, Tensor]:
+    """utils.mmdloss.mmd_rbf (reference utils/mmdloss.py:38-59; csrc/mmd.hip): source, target (B, d) f32 or fp16 ->
+    (loss () f32, d loss / d cat(source, target) (2B, d) f32 for an upstream gradient of 1; (0, d) without need_grad).
+    fix_sigma 0.0: bandwidth from the data, on the device.  Differentiable in both inputs (register_autograd scales the second
+    output and casts it to the inputs' dtype; the gradient arriving at it is ignored)."""
+    from . import ops
+    loss, grad = ops.mmd_rbf(source, target, kernel_mul, kernel_num, fix_sigma, need_grad)
+    return loss, grad if grad is not None else source.new_empty((0, source.shape[1]), dtype=F32)
+
+
+@mmd_rbf.register_fake
+def _(source, target, kernel_mul, kernel_num, fix_sigma, need_grad):
+    B, d = source.shape
+    return source.new_empty((), dtype=F32), source.new_empty((2 * B if need_grad else 0, d), dtype=F32)
+
+
+def _mmd_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+    ctx.rows, ctx.dtype = inputs[0].shape[0], inputs[0].dtype
+
+
+def _mmd_backward(ctx, grad_loss, grad_grad):
+    (grad,) = ctx.saved_tensors
+    if grad.shape[0] != 2 * ctx.rows:
+        raise RuntimeError("weclip::mmd_rbf was called with need_grad=False: it kept no gradient")
+    B = ctx.rows
+    gs = (grad[:B] * grad_loss).to(ctx.dtype) if ctx.needs_input_grad[0] else None
+    gt = (grad[B:] * grad_loss).to(ctx.dtype) if ctx.needs_input_grad[1] else None
+    return gs, gt, None, None, None, None
+
+
+torch.library.register_autograd(f"{_LIB}::mmd_rbf", _mmd_backward, setup_context=_mmd_setup)
+
+
+@torch.library.custom_op(f"{_LIB}::rbf_kernel", mutates_args=(), device_types="cuda")
+def rbf_kernel(source: Tensor, target: Tensor, kernel_mul: float, kernel_num: int, fix_sigma: float) -> Tensor:
+    """utils.mmdloss.rbf_kernel (reference utils/mmdloss.py:4-35; csrc/mmd.hip): the (2B, 2B) f32 multi-bandwidth kernel matrix
+    of cat(source, target), symmetric bit for bit.  No autograd."""
+    from . import ops
+    return ops.mmd_rbf_kernel(source, target, kernel_mul, kernel_num, fix_sigma)
+
+
+@rbf_kernel.register_fake
+def _(source, target, kernel_mul, kernel_num, fix_sigma):
+    N = 2 * source.shape[0]
+    return source.new_empty((N, N), dtype=F32)
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
        "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
-       "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice", "dense_energy_lattice", "energy_term_lattice")
+       "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice", "dense_energy_lattice", "energy_term_lattice",
+       "mmd_rbf", "rbf_kernel")
