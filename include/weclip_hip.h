@@ -269,6 +269,17 @@ int wc_adamw_multi(const int64_t* table, int count, double lr, double beta1, dou
                    double weight_decay, double bias_correction1, double bias_correction2, int blocks_per_tensor,
                    void* stream);
 
+/* One SGD-with-momentum step over many fp32 parameter tensors in one launch (reference utils/optimizer.py:35-65:
+ * torch.optim.SGD with momentum 0.9 and the poly-warm-up lr written per group).  table (device): count rows of 8 int64
+ * {param, grad, momentum_buffer, numel, 0, 0, 0, 0}.  g' = g + weight_decay*p; buf = momentum*buf + g'; p -= lr*buf (the order
+ * of torch.optim.SGD with dampening 0, no Nesterov, no maximize); grad is only read.  A first step is a zero momentum_buffer:
+ * momentum*0 + g' = g' exactly, which is torch's clone(g').  lr, momentum and weight_decay are each rounded once to fp32.
+ * 0 < count <= 65535, blocks_per_tensor > 0, 0 <= momentum < 1, lr and weight_decay finite and >= 0 (WC_ERR_ARG otherwise).
+ * A tensor with numel % 4 == 0 whose three pointers are 16-byte aligned is walked with 16-byte accesses, any other one
+ * element by element: the arithmetic is the same. */
+int wc_sgd_multi(const int64_t* table, int count, double lr, double momentum, double weight_decay, int blocks_per_tensor,
+                 void* stream);
+
 /* ---- LayerNorm ------------------------------------------------------------------------ */
 /* clip/model.py:177-183 (`LayerNorm.forward`, fp32 math).  x (rows, D) f32 with row stride ldx;
  * outputs (each optional, at least one of y32 / y16; y16lo only with y16): y32 f32, y16 fp16 hi, y16lo fp16 residual; all dense

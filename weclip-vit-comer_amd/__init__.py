@@ -76,7 +76,7 @@ def install_dropin(reference_root=None, datasets=False):
     package from a fresh interpreter:
 
         from WeCLIP_model.model_attn_aff_voc import WeCLIP;  from utils.losses import get_aff_loss
-        from utils.camutils import cams_to_affinity_label;   from utils.optimizer import PolyWarmupAdamW
+        from utils.camutils import cams_to_affinity_label;   from utils.optimizer import PolyWarmupAdamW, PolyWarmupSGD
         from utils import evaluate;  import clip;  from pytorch_grad_cam import GradCAM
 
     `utils` resolves to this package's `utils` (losses, camutils, optimizer, evaluate, AverageMeter: the

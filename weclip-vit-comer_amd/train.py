@@ -4,6 +4,11 @@ scripts/dist_clip_coco.py) around this package's graph-replayed step.
     python -m weclip_vit_comer_amd.train --config configs/voc_attn_reg.yaml --work_dir work_dir_voc --crop_size 320 \
         [--dataset voc|coco|seg] [--reference_root <reference checkout>] [--no-graph] [--max_iters N] [--resume <model .pth>]
         [--reg_loss [--reg_coef 0.01] [--reg_scale 0.5] [--reg_start <train.cam_iters>] [--reg_bilateral exact|lattice]] [--panel_iters N]
+        [--optimizer AdamW|SGD]
+
+`optimizer.type` of the YAML (AdamW when the key is missing; --optimizer overrides it) chooses between `PolyWarmupAdamW` and
+`PolyWarmupSGD` (utils/optimizer.py), each one HIP launch per parameter group.  The choice is the first line of the log and
+is stored in train_state_iter_N.pth; --resume refuses a state written by the other one.
 
 The configuration is the reference's YAML file, unchanged.  Per step nothing leaves the GPU: the three loss scalars are added
 into a device accumulator, and the reference's `pseudo_seg_mAcc` (:274-277) is counted by `wc_label_match_count`
@@ -40,7 +45,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .train_step import SupervisedTrainStep, TrainStep, make_optimizer
+from .train_step import OPTIMIZER_TYPES, SupervisedTrainStep, TrainStep, make_optimizer
 
 LOG = logging.getLogger("weclip.train")
 LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, pseudo_seg_loss: %.4f, attn_loss: %.4f, pseudo_seg_mAcc: %.4f"   # :280
@@ -117,6 +122,8 @@ def build_parser():
     p.add_argument("--save_after", type=int, default=None,
                    help="checkpoints are written past this iteration (voc and seg 26000, coco 40000)")
     p.add_argument("--resume", type=str, default=None, help="a WeCLIP_model_iter_N.pth; its train_state_iter_N.pth is loaded with it")
+    p.add_argument("--optimizer", type=str, default=None, choices=OPTIMIZER_TYPES,
+                   help="overrides optimizer.type of the YAML (a YAML without the key means AdamW)")
     p.add_argument("--reg_loss", action="store_true",
                    help="add the dense energy (regularised) loss to the step; its all-pairs filter costs about four plain steps at "
                         "batch 16 / crop 512 (DESIGN.md section 15.2; --reg_bilateral lattice: half a step, section 15.3)")
@@ -193,6 +200,25 @@ def seg_log_record(n_iter, lr, host, steps, num_classes):
     if sums == 3:
         rec["reg_loss"] = host[2] / steps
     return rec
+
+
+def optimizer_type(cfg, args=None):
+    """The optimizer the run uses, as make_optimizer spells it: --optimizer if given, else the YAML's optimizer.type (any
+    letter case), else AdamW."""
+    name = getattr(args, "optimizer", None) or cfg.optimizer.get("type") or "AdamW"
+    for known in OPTIMIZER_TYPES:
+        if str(name).lower() == known.lower():
+            return known
+    raise ValueError(f"optimizer.type must be one of {', '.join(OPTIMIZER_TYPES)}, got {name!r}")
+
+
+def check_state_optimizer(state, configured, path="the training state"):
+    """--resume: the optimizer a train_state file was written by (files from before the key existed: AdamW) must be the
+    configured one; its tensors would not load into the other."""
+    saved = state.get("optimizer_type", "AdamW")
+    if saved != configured:
+        raise RuntimeError(f"{path} was written by a run with optimizer {saved}, but this run is configured for {configured} "
+                           "(optimizer.type of the YAML, or --optimizer): resume with the same optimizer")
 
 
 def reg_settings(cfg, args):
@@ -483,9 +509,14 @@ class Trainer:
         self.model = model if model is not None else self.build_model()
         self.model.train()
         opt, sch = cfg.optimizer, cfg.scheduler
+        self.optimizer_type = optimizer_type(cfg, args)
+        betas = opt.get("betas", (0.9, 0.999) if self.optimizer_type == "SGD" else None)      # SGD ignores them
+        if betas is None:
+            raise KeyError("optimizer.betas is missing from the config (only optimizer.type SGD does without it)")
         self.opt = make_optimizer(self.model, lr=float(opt.learning_rate), weight_decay=float(opt.weight_decay),
-                                  betas=tuple(float(b) for b in opt.betas), warmup_iter=int(sch.warmup_iter),
-                                  max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power))
+                                  betas=tuple(float(b) for b in betas), warmup_iter=int(sch.warmup_iter),
+                                  max_iter=self.max_iters, warmup_ratio=float(sch.warmup_ratio), power=float(sch.power),
+                                  type=self.optimizer_type)
         self.reg = reg_settings(cfg, args)
         self.panel_iters = max(0, int(getattr(args, "panel_iters", 0) or 0))
         self.snapshot = self.panel_writer = self._last_inputs = None
@@ -666,7 +697,8 @@ class Trainer:
         if self.rank != 0:
             return None
         path = checkpoint_paths(self.cfg.work_dir.ckpt_dir, self.n_iter)[1]
-        torch.save({"optimizer": self.opt.state_dict(), "global_step": self.opt.global_step, "iter": self.n_iter,
+        torch.save({"optimizer": self.opt.state_dict(), "optimizer_type": self.optimizer_type,
+                    "global_step": self.opt.global_step, "iter": self.n_iter,
                     "model_iter_num": self.model.iter_num, "loader_epoch": self.train_loader.epoch}, path)
         return path
 
@@ -679,6 +711,7 @@ class Trainer:
         and the seg-trans switch continue where they stopped.  The dropout and augmentation streams restart, and the loader
         starts a fresh epoch, so the continuation is not bit-equal to the uninterrupted run."""
         state = torch.load(state_path_of(model_path), map_location="cpu", weights_only=False)
+        check_state_optimizer(state, self.optimizer_type, state_path_of(model_path))
         self.model.load_state_dict(torch.load(model_path, map_location="cpu"), strict=True)
         self.opt.load_state_dict(state["optimizer"])
         self.opt.global_step = int(state["global_step"])
@@ -756,7 +789,7 @@ def main(argv=None):
         trainer = Trainer(cfg, args, rank_dump_dir=os.environ.get("WECLIP_TRAIN_RANK_DUMP") or None)
         if trainer.rank == 0:
             setup_logger(trainer.log_path)
-            LOG.info("\nargs: %s", args)
+            LOG.info("\noptimizer: %s\nargs: %s", trainer.optimizer_type, args)
             LOG.info("\nconfigs: %s", cfg)
         trainer.fit()
         trainer.close()

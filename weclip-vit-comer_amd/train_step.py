@@ -13,13 +13,19 @@ import torch.nn.functional as F
 from .utils.camutils import cams_to_affinity_label, get_mask_by_radius
 from .utils.losses import (DenseEnergyLoss, get_aff_loss, get_aff_loss_fused, get_ce_loss_fused, get_energy_loss_fused,
                            get_seg_loss, get_seg_loss_fused)
-from .utils.optimizer import PolyWarmupAdamW
+from .utils.optimizer import PolyWarmupAdamW, PolyWarmupSGD
+
+OPTIMIZER_TYPES = ("AdamW", "SGD")                  # optimizer.type of the YAML, compared without letter case
 
 
 def make_optimizer(model, lr=2e-4, weight_decay=0.01, betas=(0.9, 0.999), warmup_iter=50, max_iter=30000,
-                   warmup_ratio=1e-6, power=1.0):
+                   warmup_ratio=1e-6, power=1.0, type="AdamW"):
     """configs/voc_attn_reg.yaml:29-38 + scripts/dist_clip_voc.py:196-234: only group 3 is non-empty
-    and runs at 10x the base lr."""
+    and runs at 10x the base lr.  type: "AdamW" (PolyWarmupAdamW) or "SGD" (PolyWarmupSGD, the reference's second optimizer,
+    over the same groups; it ignores betas), in any letter case."""
+    cls = {"adamw": PolyWarmupAdamW, "sgd": PolyWarmupSGD}.get(str(type).lower())
+    if cls is None:
+        raise ValueError(f"make_optimizer: type must be one of {', '.join(OPTIMIZER_TYPES)}, got {type!r}")
     g = model.get_param_groups()
     groups = [
         {"params": g[0], "lr": lr, "weight_decay": weight_decay},
@@ -27,8 +33,8 @@ def make_optimizer(model, lr=2e-4, weight_decay=0.01, betas=(0.9, 0.999), warmup
         {"params": g[2], "lr": lr * 10, "weight_decay": weight_decay},
         {"params": g[3], "lr": lr * 10, "weight_decay": weight_decay},
     ]
-    return PolyWarmupAdamW(groups, lr=lr, weight_decay=weight_decay, betas=list(betas),
-                           warmup_iter=warmup_iter, max_iter=max_iter, warmup_ratio=warmup_ratio, power=power)
+    return cls(groups, lr=lr, weight_decay=weight_decay, betas=list(betas),
+               warmup_iter=warmup_iter, max_iter=max_iter, warmup_ratio=warmup_ratio, power=power)
 
 
 class RegTerm:
@@ -90,7 +96,7 @@ class GradBucket:
 
     def __init__(self, params):
         self.params = [p for p in params if p.requires_grad]
-        # every gradient starts on a 16-byte boundary (the fused AdamW and the split-K reductions use 16-byte accesses):
+        # every gradient starts on a 16-byte boundary (the fused AdamW and SGD steps and the split-K reductions use 16-byte accesses):
         # an odd-sized tensor (the 21-class bias) is followed by <= 3 padding elements, which stay zero
         offs, off = [], 0
         for p in self.params:
@@ -214,8 +220,8 @@ class _StepBase:
 
 
 class TrainStep(_StepBase):
-    """forward -> losses -> backward -> (DP: gradient all-reduce) -> AdamW step.  This class holds the weakly supervised
-    variant's forward, `losses` (the override point) and PairPlan statics; everything behind the losses is `_StepBase`.
+    """forward -> losses -> backward -> (DP: gradient all-reduce) -> optimizer step (PolyWarmupAdamW, or PolyWarmupSGD from
+    make_optimizer(type="SGD")).  This class holds the weakly supervised variant's forward, `losses` (the override point) and PairPlan statics; everything behind the losses is `_StepBase`.
 
     graph=True (CUDA tensors + explicit `labels` only): forward + losses + backward of a batch signature
     (image shape, number of (image, class) pairs, max classes per image, affinity branch) are captured once into a
@@ -283,7 +289,7 @@ class TrainStep(_StepBase):
 
 
 class SupervisedTrainStep(_StepBase):
-    """forward -> cross-entropy -> backward -> (DP: gradient all-reduce) -> AdamW step for the fully supervised variant
+    """forward -> cross-entropy -> backward -> (DP: gradient all-reduce) -> optimizer step (AdamW or SGD) for the fully supervised variant
     (WeCLIP_model/model_attn_aff_voc_seg.py), whose labels are ground-truth masks.  The loss is
     F.cross_entropy(F.interpolate(seg, label.shape[1:], bilinear, align_corners=False), label, ignore_index): the
     reference ships no training script for this variant, so the loss is this package's choice; on the GPU
