@@ -350,8 +350,8 @@ int wc_cam_map(const float* a32, const float* w, const int* pair_img, float* cam
  * generate_cam_label :202-216, WeCLIP_model/model_attn_aff_voc.py:158-163.  hw = L-1 patch tokens.
  * wc_aff_weight:      W (B,hw,hw) = sum_l wgt[b,l] * maps[l][b,1:,1:] (* seg[b] if seg != NULL);
  *                     h_maps: HOST array of nmaps (<=12) device pointers to (B,L,L) head-mean maps.
- * wc_aff_seg_weights: seg-trans layer selection (:158-167): diff (B,nmaps) workspace,
- *                     wgt[b,l] = [diff <= mean diff] / (count + 1e-5).
+ * wc_aff_seg_weights: seg-trans layer selection (:158-167): rowsum (B,nmaps,hw) workspace (the row sums of maps[l][b,1:,1:]),
+ *                     diff (B,nmaps) = -sum of them, wgt[b,l] = [diff <= mean diff] / (count + 1e-5).
  * wc_matvec:          out (B,hw,K) = f(W x) (transpose=0) or f(W^T x) (transpose=1),
  *                     x = X * sin[:,None]; f = 1/v if recip else alpha*v*sout[:,None] + add.
  *                     Sinkhorn (:64-75) as scale vectors: c = 1/(W^T r), r = 1/(W c), 3 rounds;
@@ -363,10 +363,11 @@ int wc_cam_map(const float* a32, const float* w, const int* pair_img, float* cam
  *                     optional mask_out (P,hw) f32, boxes (P,maxbox,4) i32 + nbox (P).
  * wc_cam_upsample:    R (B,hw,K) refined maps -> cams (B,C,H,W): channel 1+k = bilinear(half-pixel)
  *                     of min-max(R_k) for k < nk[b] (0 beyond), channel 0 = 1 - max_k.
+ *                     2 <= C <= K + 1; nk is read on the device, unchecked: 1 <= nk[b] <= C - 1 is the caller's duty.
  *                     stats: workspace B*K*2 f32. */
 int wc_aff_weight(const float* const* h_maps, int nmaps, const float* wgt, const float* seg, float* W,
                   int B, int L, void* stream);
-int wc_aff_seg_weights(const float* const* h_maps, int nmaps, const float* seg, float* diff, float* wgt,
+int wc_aff_seg_weights(const float* const* h_maps, int nmaps, float* rowsum, float* diff, float* wgt,
                        int B, int L, void* stream);
 int wc_matvec(const float* W, const float* X, const float* sin, const float* sout, const float* add,
               float* out, int B, int hw, int K, int transpose, int recip, float alpha, void* stream);

@@ -39,7 +39,13 @@ def fused_ok(hw):
 
 
 def _nblk(hw):
+    """Row blocks of the sweeps: their column partials take B * _nblk(hw) * hw (* K) floats."""
     return (hw + 31) // 32
+
+
+def _nblk_weight(hw):
+    """Row blocks of wc_aff_weight_c1: its column partials take B * _nblk_weight(hw) * hw floats."""
+    return (hw + 7) // 8
 
 
 def affinity_weight(maps, seg=None, seg_trans=False, n_last=6, keep=None, return_c1=False):
@@ -60,7 +66,7 @@ def affinity_weight(maps, seg=None, seg_trans=False, n_last=6, keep=None, return
         """W (and, on the fused path, the first Sinkhorn column scale c1 = 1 / colsum(W) from the same pass)."""
         if return_c1 and fused_ok(hw):
             c1 = torch.empty(B, hw, device=dev, dtype=F32)
-            ws = torch.empty(B * ((hw + 7) // 8) * hw, device=dev, dtype=F32)
+            ws = torch.empty(B * _nblk_weight(hw) * hw, device=dev, dtype=F32)
             lib.wc_aff_weight_c1(_map_array(sel), len(sel), L.ptr(wgt), L.ptr(segp), L.ptr(W), L.ptr(c1), L.ptr(ws), B, Lq,
                                  L.stream())
             return W, c1
@@ -176,7 +182,9 @@ def refine(W, cams, pair_img, pair_slot, K, h, w, thr, c1=None):
 
 def upsample_with_bg(R, nk, h, w, H, Wd, C=None):
     """generate_cam_label + bg score (clip_tool.py:202-216, model_attn_aff_voc.py:160-163):
-    cams (B, C, H, W): channel 0 = 1 - max_k, channels 1.. = bilinear(min-max(R_k))."""
+    cams (B, C, H, W): channel 0 = 1 - max_k, channels 1.. = bilinear(min-max(R_k)) for k < nk[b], zero from there on.
+    Precondition: 1 <= nk[b] <= C - 1 for every image.  nk is device memory and the kernel takes it unchecked: nk[b] == 0 gives
+    bg = +inf, nk[b] > C - 1 writes into the next image's channels (behind the buffer for the last image)."""
     B, hw, K = R.shape
     C = K + 1 if C is None else C
     stats = torch.empty(B, K, 2, device=R.device, dtype=F32)

@@ -535,6 +535,8 @@ __global__ __launch_bounds__(256) void refined_minmax_kernel(const float* __rest
 }
 
 // cams[b, 1+k, y, x] = bilinear((R_k - min)/(1e-7 + max)), cams[b, 0] = 1 - max_k   (k < nk[b])
+// PRECONDITION (not checked: nk is device memory): 1 <= nk[b] <= C - 1.  nk[b] == 0 leaves best = -inf, so bg = +inf; nk[b] > C - 1
+// writes class channels past image b's C, i.e. into image b + 1 (behind the buffer for the last image).
 __global__ __launch_bounds__(256) void cam_upsample_kernel(const float* __restrict__ R, const float* __restrict__ stats,
                                                             const int* __restrict__ nk, float* __restrict__ cams,
                                                             int h, int w, int K, int C, int H, int W, float sy, float sx) {
