@@ -379,6 +379,14 @@ int wc_matvec(const float* W, const float* X, const float* sin, const float* sou
 int wc_aff_fused_supported(int hw);
 int wc_aff_weight_c1(const float* const* h_maps, int nmaps, const float* wgt, const float* seg, float* W, float* c1,
                      float* ws, int B, int L, void* stream);
+/* wc_attn_aff_weight: clip/clip_tool.py:169-173 (the branch without seg-trans) straight from the layers' attention operands:
+ *   W (B,hw,hw) = sum_l wgt[b,l] * ((1/H) sum_h softmax_h(Q_l K_l^T))[1:,1:] and c1 = 1 / colsum(W), bit-identical to
+ *   wc_attn_mean per layer followed by wc_aff_weight_c1 (seg == NULL), in one launch that writes no (B,L,L) map.
+ *   h_qkv / h_lse: HOST arrays of nmaps (<=12) device pointers to the layers' packed qkv (B*L, 3E) fp16 (as wc_attn_fwd takes it,
+ *   16-byte aligned) and lse (B,H,L) f32 (as wc_attn_fwd wrote it), in layer order; wgt (B,nmaps) f32; DH in {32, 64};
+ *   hw = L-1 with wc_aff_fused_supported(hw).  ws: B*ceil(hw/8)*hw f32. */
+int wc_attn_aff_weight(const void* const* h_qkv, const float* const* h_lse, int nmaps, const float* wgt, float* W, float* c1,
+                       float* ws, int B, int L, int H, int DH, void* stream);
 int wc_aff_sinkhorn_step(const float* W, const float* c, float* r, float* c_next, float* ws, int B, int hw, int last,
                          void* stream);
 int wc_aff_tsym_apply(const float* W, const float* r, const float* c, const float* X, float* out, float* y1, float* ws,

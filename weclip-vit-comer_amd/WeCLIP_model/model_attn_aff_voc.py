@@ -122,12 +122,18 @@ class WeCLIP(nn.Module):
         first = 12 - n                      # index into the 12 maps (11 encoder + last block)
         return [i >= first for i in range(11)]
 
-    def encode(self, img, seg_trans, x16=None, want_maps=True):
+    def encode(self, img, seg_trans, x16=None, want_maps=True, defer_maps=False):
         """Frozen encoder: token rows of blocks 1..11 and the head-mean maps the affinity needs (none when the
         caller returns before the CAM stage: the COCO model in 'val', model_attn_aff_coco.py:131-132).
-        `x16` (a list) additionally receives fp16 copies of the block outputs (adapter operands)."""
+        `x16` (a list) additionally receives fp16 copies of the block outputs (adapter operands).
+        `defer_maps` (forward, outside the seg-trans branch): the needed layers hand back their attention operands instead of
+        maps where cam_pipeline.qk_weight_ok holds; the affinity weight is then built from them in one launch."""
         need = self._maps_needed(seg_trans) if want_maps else [False] * 11
-        return VE.encode_blocks(self.encoder.visual, img, need, x16)
+        vis = self.encoder.visual
+        at = vis.transformer.resblocks[0].attn
+        hw = (img.shape[-2] // 16) * (img.shape[-1] // 16)
+        defer = defer_maps and want_maps and not seg_trans and CP.qk_weight_ok(hw, at.embed_dim // at.num_heads)
+        return VE.encode_blocks(vis, img, need, x16, defer_maps=defer)
 
     def forward(self, img, img_names="2007_000032", mode="train", labels=None, plan=None, sizes=None):
         """-> (seg (B,nc,h,w), cam_labels (B,H,W) int64 [list of per-image maps in 'val' when the
@@ -147,7 +153,7 @@ class WeCLIP(nn.Module):
         x16 = VE.X16Stack(self.encoder.visual.transformer.layers - 1) if (hip_head or comer_tokens) else None
         with torch.no_grad():
             want_cam = not (mode == "val" and not self.val_runs_cam)
-            xs, maps, _, Lq = self.encode(img, seg_trans, x16, want_maps=want_cam)
+            xs, maps, _, Lq = self.encode(img, seg_trans, x16, want_maps=want_cam, defer_maps=True)
         if hip_head:
             # adapters + decoder + attn_pred, forward and backward as HIP launches (head_engine.py)
             drop = self.head_engine.draw_dropout(B, img.device) if self.training else None

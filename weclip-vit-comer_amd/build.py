@@ -22,6 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=o
 # kernels whose hand-counted `s_waitcnt vmcnt(n)` waits are only correct without register spills (a spill's scratch access is
 # one more entry in the in-order vmcnt queue): the build fails if the compiler reports scratch use for them
 NO_SCRATCH = ("gemm_row.hip", "gemm_km.hip")
+# single kernels (by name, any template instance) that must not spill: attn_affw_kernel holds two 128x128 fp32 tiles per workgroup
+# in registers at exactly the 256 its two-workgroups-per-CU launch bound allows; a spill would sit in its (layer, head) loop
+NO_SCRATCH_KERNELS = {"attention.hip": ("attn_affw_kernel",)}
 
 
 def _sources():
@@ -59,7 +62,7 @@ def _compile(src):
     if os.path.exists(obj) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
         return obj, False
     cmd = [HIPCC] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
-    if src in NO_SCRATCH:
+    if src in NO_SCRATCH or src in NO_SCRATCH_KERNELS:
         cmd.append("-Rpass-analysis=kernel-resource-usage")
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
@@ -70,6 +73,13 @@ def _compile(src):
         if not spills or any(spills):
             raise RuntimeError(f"{src}: a kernel spills registers (scratch bytes per lane: {spills}); its counted "
                                "`s_waitcnt vmcnt(n)` waits assume that no scratch load / store is in the vmcnt queue")
+    if src in NO_SCRATCH_KERNELS:
+        import re
+        found = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S)
+        for kern in NO_SCRATCH_KERNELS[src]:
+            sizes = [int(v) for name, v in found if kern in name]
+            if not sizes or any(sizes):
+                raise RuntimeError(f"{src}: {kern} spills registers (scratch bytes per lane: {sizes})")
     with open(stamp_file, "w") as fh:
         fh.write(stamp)
     return obj, True

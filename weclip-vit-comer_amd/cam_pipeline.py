@@ -6,9 +6,13 @@ import ctypes
 import torch
 
 from . import _lib as L
-from .ops import F32
+from .ops import F16, F32, AttnOperands, KernelTimer
 
 I32 = torch.int32
+
+# A/B switch: build the affinity weight of the branch without seg-trans straight from the layers' Q / K (affinity_weight_qk, one
+# wc_attn_aff_weight launch) instead of from per-layer head-mean maps.  The results are bit-identical either way.
+FUSED_QK_WEIGHT = True
 
 
 def _map_array(maps):
@@ -48,12 +52,61 @@ def _nblk_weight(hw):
     return (hw + 7) // 8
 
 
+def qk_weight_ok(hw, DH, dtype=F16):
+    """Shapes wc_attn_aff_weight serves: the fused sweeps' token counts, fp16 operands, head dim 32 or 64."""
+    return FUSED_QK_WEIGHT and fused_ok(hw) and dtype == F16 and DH in (32, 64)
+
+
+_UNIFORM_WGT = {}
+
+
+def _uniform_wgt(B, n, dev):
+    """(B, n) f32 of 1/n, kept per (B, n, device): the normal branch's layer weights never change."""
+    key = (B, n, dev.type, dev.index)
+    if key not in _UNIFORM_WGT and torch.cuda.is_current_stream_capturing():
+        return torch.full((B, n), 1.0 / n, device=dev, dtype=F32)      # a graph's pool must not own the kept tensor
+    if key not in _UNIFORM_WGT:
+        _UNIFORM_WGT[key] = torch.full((B, n), 1.0 / n, device=dev, dtype=F32)
+    return _UNIFORM_WGT[key]
+
+
+def affinity_weight_qk(layers, wgt=None):
+    """The normal branch's affinity weight (clip_tool.py:169-173) from the attention operands of the selected layers instead of
+    their head-mean maps: layers = list of ops.AttnOperands in layer order (at most 12), wgt (B, len(layers)) f32, default the
+    mean.  -> (W (B,hw,hw), c1 (B,hw)), bit-identical to affinity_weight(maps, return_c1=True) on those layers' maps."""
+    a = layers[0]
+    B, Lq, H, DH = a.B, a.L, a.H, a.DH
+    hw = Lq - 1
+    dev = a.qkv.device
+    if not (fused_ok(hw) and DH in (32, 64)):
+        raise RuntimeError(f"affinity_weight_qk: hw = {hw}, head dim {DH} are not served (see qk_weight_ok)")
+    for x in layers:
+        if (x.B, x.L, x.H, x.DH) != (B, Lq, H, DH):
+            raise RuntimeError("affinity_weight_qk: the layers' shapes differ")
+    wgt = _uniform_wgt(B, len(layers), dev) if wgt is None else wgt
+    W = torch.empty(B, hw, hw, device=dev, dtype=F32)
+    c1 = torch.empty(B, hw, device=dev, dtype=F32)
+    ws = torch.empty(B * _nblk_weight(hw) * hw, device=dev, dtype=F32)
+    qkv = (ctypes.c_void_p * len(layers))(*[L.ptr(x.qkv, F16, "qkv").value for x in layers])
+    lse = (ctypes.c_void_p * len(layers))(*[L.ptr(x.lse, F32, "lse").value for x in layers])
+    KernelTimer.tag(b"@vit_attn")         # the head-mean work of the ViT blocks, now done here (bench.py's attention group)
+    L.lib().wc_attn_aff_weight(qkv, lse, len(layers), L.ptr(wgt, F32, "wgt"), L.ptr(W), L.ptr(c1), L.ptr(ws), B, Lq, H, DH,
+                               L.stream())
+    KernelTimer.tag(None)
+    return W, c1
+
+
 def affinity_weight(maps, seg=None, seg_trans=False, n_last=6, keep=None, return_c1=False):
     """maps: list of head-mean attention maps (B,L,L) f32 in layer order (11 encoder + last block).
     Normal branch (clip_tool.py:169-173): mean of the last 8 [1:,1:].  Seg-trans branch
     (:152-168, n_last 6 VOC / 10 COCO): masked mean of the last n_last times seg (B,hw,hw).
     keep (B, n_last) 0/1, optional: a caller-supplied layer selection instead of seg_layer_keep's."""
     sel = maps[-n_last:] if seg_trans else maps[-8:]      # entries outside the selection may be None
+    if not seg_trans and keep is None and return_c1 and all(isinstance(m, AttnOperands) for m in sel):
+        return affinity_weight_qk(sel)                    # the layers deferred their maps (vit_engine.run_block)
+    if any(isinstance(m, AttnOperands) for m in sel):
+        raise RuntimeError("affinity_weight: deferred attention operands serve only the normal branch with return_c1 and no "
+                           "`keep` selection, and only when all selected layers deferred their maps")
     B, Lq, _ = sel[0].shape
     hw = Lq - 1
     dev = sel[0].device

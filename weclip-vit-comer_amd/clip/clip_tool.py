@@ -154,7 +154,10 @@ def batch_refined_cams(clip_model, last_rows, maps11, seg_attn, plan, text_hat, 
     maps11: list of that many head-mean maps (entries may be None where unused).
     Returns (R (B, hw, K) refined CAMs, cams (P, hw), probs (P, Tmax), state)."""
     B, Lq = plan.B, h * w + 1
-    st = last_layer_forward(clip_model, last_rows, B, Lq)
+    # the encoder deferred its maps (WeCLIP.encode, normal branch only): the last block does the same and the affinity weight
+    # comes from the eight layers' Q / K in one launch (CP.affinity_weight_qk)
+    defer = not seg_trans and keep is None and len(maps11) >= 7 and all(isinstance(m, CP.AttnOperands) for m in maps11[-7:])
+    st = last_layer_forward(clip_model, last_rows, B, Lq, defer_mean=defer)
     maps = list(maps11) + [st.mean]
     need = maps[-n_last:] if seg_trans else maps[-8:]
     if any(m is None for m in need):

@@ -58,8 +58,10 @@ class X16Stack(list):
         return Split(self.big[i], self.big_lo[i] if self.big_lo is not None else None)
 
 
-def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, causal=False):
+def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, causal=False, defer_mean=False):
     """x (B*L, E) fp32 -> (x_out fp32, head-mean map (B,L,L) or None).
+    `defer_mean`: skip the head-mean launch and hand back the layer's ops.AttnOperands (qkv, lse) in the map's place; they stay
+    alive until the affinity stage turns all layers' into W at once (cam_pipeline.affinity_weight_qk).
     `causal`: the text tower's masked attention (ops.attention_causal; L <= 128, DH = 64); the map is then the causal one.
     `keep`, if a dict, receives intermediates needed by the analytic backward.
     `tag`: bench.py's roofline group of the attention half (in-projection, attention, head-mean, out-projection)."""
@@ -73,10 +75,11 @@ def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, ca
     ops.gemm(a, pk.in_w, M, 3 * E, E, bias=pk.in_b, out16=qkv, scale=ops.q_scale(DH), scale_cols=E)
     o32 = None
     attn = ops.attention_causal if causal else ops.attention
+    kw = {"defer_mean": True} if (defer_mean and not causal) else {}
     if keep is not None:
-        o16, lse, mean, o32 = attn(qkv, B, L, H, DH, want_mean=want_mean, want_o32=True)
+        o16, lse, mean, o32 = attn(qkv, B, L, H, DH, want_mean=want_mean, want_o32=True, **kw)
     else:
-        o16, lse, mean = attn(qkv, B, L, H, DH, want_mean=want_mean)
+        o16, lse, mean = attn(qkv, B, L, H, DH, want_mean=want_mean, **kw)
     x1 = torch.empty(M, E, device=dev, dtype=F32)
     ops.gemm(o16, pk.out_w, M, E, E, bias=pk.out_b, resid=x, out32=x1, round16=True)
     if tag:
@@ -100,13 +103,15 @@ def run_block(pk, x, B, L, want_mean=True, keep=None, x16_out=None, tag=None, ca
     return x2, mean
 
 
-def encode_blocks(vis, img, need, x16=None):
+def encode_blocks(vis, img, need, x16=None, defer_maps=False):
     """The frozen visual tower `vis` up to its last block but one: -> (token rows of blocks 1..11, their head-mean maps
-    [None where `need[i]` is false], B, Lq).  `x16` (a list) additionally receives fp16 copies of the block outputs."""
+    [None where `need[i]` is false], B, Lq).  `x16` (a list) additionally receives fp16 copies of the block outputs.
+    `defer_maps`: the needed layers hand back ops.AttnOperands instead of maps (run_block's defer_mean)."""
     rows, B, Lq = vis.embed(img)
     xs, maps = [], []
     for i in range(vis.transformer.layers - 1):
-        rows, m = run_block(vis.transformer.resblocks[i].pack(), rows, B, Lq, want_mean=need[i], x16_out=x16, tag=b"@vit_attn")
+        rows, m = run_block(vis.transformer.resblocks[i].pack(), rows, B, Lq, want_mean=need[i], x16_out=x16, tag=b"@vit_attn",
+                            defer_mean=defer_maps)
         xs.append(rows)
         maps.append(m)
     return xs, maps, B, Lq

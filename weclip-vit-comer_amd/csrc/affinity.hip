@@ -611,6 +611,14 @@ static bool aff_fused_ok(int hw) { return hw % 4 == 0 && hw <= 1024 * AF_MAXCH &
 // Whether the fused sweeps apply to this token count (hw % 4 == 0: 16-byte row pieces); else use wc_aff_weight / wc_matvec.
 extern "C" int wc_aff_fused_supported(int hw) { return aff_fused_ok(hw) ? 1 : 0; }
 
+// The first Sinkhorn column scale from 8-row column partials (wc_aff_weight_c1 below; wc_attn_aff_weight in attention.hip).
+int wc_aff_colreduce_c1(const float* colpart, float* c1, int B, int hw, int nblk, void* stream) {
+    hipLaunchKernelGGL(aff_colreduce_kernel, dim3(wc_cdiv(hw, 256), B), dim3(256), 0, (hipStream_t)stream, colpart, nullptr, nullptr,
+                       c1, hw, 1, nblk, 0);
+    WC_LAUNCH_CHECK("aff_colreduce_kernel");
+    return WC_OK;
+}
+
 // W (B,hw,hw) as wc_aff_weight, plus the first Sinkhorn column scale c1 = 1 / colsum(W) (B,hw).
 // ws: B * ceil(hw/8) * hw floats.
 extern "C" int wc_aff_weight_c1(const float* const* h_maps, int nmaps, const float* wgt, const float* seg, float* W, float* c1,

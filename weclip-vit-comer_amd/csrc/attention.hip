@@ -1,4 +1,4 @@
-// Multi-head self-attention forward for gfx950 (MFMA fp16, fp32 softmax), in two kernels.
+// Multi-head self-attention forward for gfx950 (MFMA fp16, fp32 softmax), in two kernels, plus the affinity weight from Q / K.
 //
 // Replaces reference clip/myAtt.py:21-64 (`_scaled_dot_product_attention`: q/sqrt(d), bmm,
 // softmax, bmm -- two materialised (B*H, L, L) fp32 tensors) and :325-326 (head-mean of the
@@ -14,6 +14,9 @@
 //                      rows (and key columns) when that remainder is tiny (the CLS token of a 1 + 32*32 sequence): a
 //                      129th row must not cost a whole 128-row tile, so the tiled work starts at row L % 128; the mean
 //                      kernel's first tile row / column take the edge entries from the tiles they hold in LDS.
+//   attn_affw_kernel : reference clip/clip_tool.py:169-173 outside the seg-trans branch: W = sum over the last 8 layers of
+//                      (1/8) * head-mean map [1:, 1:], one launch after the encoder that keeps a 128x128 tile of W in registers
+//                      across all (layer, head) pairs -- no per-layer map is written (see the kernel's comment).
 // V stays row-major [key][dh] (as the in-projection wrote it); the O^T = V^T P^T fragments (8 consecutive keys
 // of one dh column) come from gfx950's transposing LDS read ds_read_b64_tr_b16 -- no V^T copy in HBM.
 //
@@ -622,6 +625,194 @@ __global__ __launch_bounds__(256, 2) void attn_mean_kernel(const __half* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// Affinity weight straight from the layers' Q / K (clip_tool.py:169-173 outside the seg-trans branch):
+//   W[b, i, j] = sum_l wgt[b, l] * ((1/H) sum_h exp2(Q_lh K_lh^T - LSE_lh))[1 + i, 1 + j]
+// One launch after the encoder instead of attn_mean_kernel once per layer + aff_weight_colpart_kernel: a workgroup keeps its
+// 128x128 tile of W in registers across all nmaps x H (layer, head) pairs and writes it once, so the per-layer (B, L, L) maps
+// are neither written nor read back, and the CLS row / column / corner they carry (cropped by W) is never computed.
+// The tile body is attn_mean_kernel's (register-staged Q / K tiles double-buffered in LDS, -LSE through the extra MFMA k-step,
+// XCD-aware (image, tile) order); tiles cover patch tokens only: W index 128 t + x is token 1 + 128 t + x.
+// Bit-identical to the two-kernel path: `accl` is attn_mean_kernel's accumulator (acc += exp2(s), heads ascending), and after
+// a layer's last head wacc = fmaf(wgt, accl * (1/H), wacc) is aff_weight_colpart_kernel's fmaf(wl[l], map, sacc), l ascending
+// from 0.  The column partials of the first Sinkhorn scale keep that kernel's layout and order too (8-row blocks, rows
+// ascending from 0): in the 32x32 accumulator layout an 8-row block of a column is registers 4g..4g+3 of lane l31 (rows 0-3)
+// followed by the same registers of lane 32 + l31 (rows 4-7), so one cross-lane move continues the chain (0 + v is exact).
+struct AttnLayerPtrs {
+    const __half* qkv[12];
+    const float* lse[12];
+};
+
+template <int DH>
+__global__ __launch_bounds__(256, 2) void attn_affw_kernel(AttnLayerPtrs ops, int nmaps, const float* __restrict__ wgt,
+                                                         float* __restrict__ W, float* __restrict__ colpart, int L, int H,
+                                                         int E, int nt, int Bn) {
+    constexpr int KS = DH / 16;
+    constexpr int ROW = DH * 2 + 16;
+    constexpr int TB = 128 * ROW;        // bytes of one 128-row operand tile
+    constexpr int CH = DH / 8;           // 16-B chunks per row
+    constexpr int NC = 128 * CH / 256;   // chunks per thread per operand (4 for DH=64, 2 for 32)
+    constexpr int BUF = 2 * TB + 512;    // [2][Q tile | K tile | lse 128 f32]
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hh = lane >> 5, l31 = lane & 31;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int slot = blockIdx.x >> 3;                    // XCD-aware order, as attn_mean_kernel
+    const int b = (slot / (nt * nt)) * 8 + (blockIdx.x & 7);
+    if (b >= Bn) return;
+    const int rem = slot - (slot / (nt * nt)) * (nt * nt);
+    const int hw = L - 1;
+    const int j0 = (rem % nt) * 128, i0 = (rem / nt) * 128;      // W indices of the tile; token = 1 + index
+    const long ldq = 3L * E;
+    const long boff = (long)b * L * ldq;
+
+    // Staging addresses: chunk i of a thread is row tid / CH + (256 / CH) * i of the tile, so its byte offset inside the image is
+    // min(row 0's + i * (256 / CH) rows, last row's) + column bytes (rows past the sequence clamped to the last token), added to a
+    // wave-uniform (layer, image, head) base.  The offsets are rebuilt per pair from 32-bit registers (the empty asm keeps the
+    // compiler from hoisting 2 * NC + 1 64-bit addresses out of the loop, which it then spills).
+    const unsigned rowb = (unsigned)ldq * 2u, lastb = (unsigned)(L - 1) * rowb;
+    unsigned qrow0 = (unsigned)(1 + i0 + tid / CH) * rowb, krow0 = (unsigned)(1 + j0 + tid / CH) * rowb;
+    const unsigned colb = (unsigned)(tid % CH) * 16u;
+    unsigned lo_ = (unsigned)min(1 + i0 + (tid & 127), L - 1) * 4u;      // the query row's LSE (threads 0..127)
+    u32x4 rq[NC], rk[NC];
+    float rl = 0.f;
+#undef GLOAD
+#define GLOAD(l_, h_) \
+    { \
+        const int h__ = (h_); \
+        const char* base = reinterpret_cast<const char*>(ops.qkv[l_] + boff + h__ * DH); \
+        asm volatile("" : "+v"(qrow0), "+v"(krow0), "+v"(lo_)); \
+        _Pragma("unroll") \
+        for (int i = 0; i < NC; ++i) { \
+            const unsigned step = (unsigned)i * (256 / CH) * rowb; \
+            rq[i] = *reinterpret_cast<const u32x4*>(base + (min(qrow0 + step, lastb) + colb)); \
+            rk[i] = *reinterpret_cast<const u32x4*>(base + E * 2 + (min(krow0 + step, lastb) + colb)); \
+        } \
+        if (tid < 128) \
+            rl = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(ops.lse[l_] + ((long)b * H + h__) * L) + lo_); \
+    }
+#undef LSTORE
+#define LSTORE(buf_) \
+    { \
+        char* qb = smem + (buf_) * BUF + lrow; \
+        _Pragma("unroll") \
+        for (int i = 0; i < NC; ++i) { \
+            *reinterpret_cast<u32x4*>(qb + i * (256 / CH) * ROW) = rq[i]; \
+            *reinterpret_cast<u32x4*>(qb + TB + i * (256 / CH) * ROW) = rk[i]; \
+        } \
+        if (tid < 128) reinterpret_cast<float*>(smem + (buf_) * BUF + 2 * TB)[tid] = rl; \
+    }
+    const int lrow = (tid / CH) * ROW + (tid % CH) * 16;     // chunk i lands (256 / CH) * i rows further down
+
+    f32x16 accl[2][2], wacc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) accl[i][j][r] = wacc[i][j][r] = 0.f;
+    f16x8 b_aug;                         // K side of the -LSE k-step (see attn_mean_kernel)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) b_aug[j] = (_Float16)((hh == 0 && j < 2) ? 1.0f : 0.0f);
+    const float invh = 1.0f / H;
+
+    GLOAD(0, 0);
+    LSTORE(0);
+    __syncthreads();
+    int l = 0, h = 0;                    // the (layer, head) pair in LDS; layer-major, heads ascending
+    for (int p = 0, np = nmaps * H; p < np; ++p) {
+        const int buf = p & 1;
+        const bool last_h = h + 1 == H;
+        const int nl = last_h ? l + 1 : l, nh = last_h ? 0 : h + 1;
+        if (p + 1 < np) GLOAD(nl, nh);   // the prefetch crosses layer boundaries
+        const char* qb = smem + buf * BUF;
+        const float* ls = reinterpret_cast<const float*>(qb + 2 * TB);
+        // one 32-row half of the wave's 64x64 quarter at a time: 32 score registers live beside accl and wacc (64 + 64) and the
+        // staged tiles of the next pair, which keeps the kernel at two workgroups per CU without scratch
+        const char* As = qb + (wr * 64 + l31) * ROW + hh * 16;
+        const char* Bs = qb + TB + (wc * 64 + l31) * ROW + hh * 16;
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const float ng = -ls[wr * 64 + mi * 32 + l31];
+            const _Float16 hi = (_Float16)ng;
+            const _Float16 lo = (_Float16)(ng - (float)hi);
+            f16x8 a_aug;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) a_aug[j] = (_Float16)0.0f;
+            if (hh == 0) { a_aug[0] = hi; a_aug[1] = lo; }
+            f32x16 zero, s[2];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+            s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_aug, b_aug, zero, 0, 0, 0);
+            s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_aug, b_aug, zero, 0, 0, 0);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const f16x8 a = *reinterpret_cast<const f16x8*>(As + mi * 32 * ROW + ks * 32);
+                const f16x8 b0 = *reinterpret_cast<const f16x8*>(Bs + ks * 32);
+                const f16x8 b1 = *reinterpret_cast<const f16x8*>(Bs + 32 * ROW + ks * 32);
+                s[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b0, s[0], 0, 0, 0);
+                s[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b1, s[1], 0, 0, 0);
+            }
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) accl[mi][ni][r] += __builtin_amdgcn_exp2f(s[ni][r]);
+        }
+        if (last_h) {                    // the layer's head mean joins W: wacc = wgt[b, l] * (accl / H) + wacc
+            const float wl = wgt[b * nmaps + l];
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        wacc[mi][ni][r] = fmaf(wl, accl[mi][ni][r] * invh, wacc[mi][ni][r]);
+                        accl[mi][ni][r] = 0.f;
+                    }
+        }
+        if (p + 1 < np) LSTORE(buf ^ 1);
+        __syncthreads();
+        l = nl;
+        h = nh;
+    }
+    float* Wb = W + (long)b * hw * hw;
+    const int nblk = (hw + 7) >> 3;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int j = j0 + wc * 64 + ni * 32 + l31;
+            const int ib = i0 + wr * 64 + mi * 32;
+            if (j < hw) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int i = ib + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                    if (i < hw) Wb[(long)i * hw + j] = wacc[mi][ni][r];
+                }
+            }
+            // column partials: rows ib + 8g .. + 3 on lane l31, then rows + 4 .. + 7 on lane 32 + l31 continue the same chain
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float cs = 0.f;
+                if (hh == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (ib + 8 * g + k < hw) cs += wacc[mi][ni][4 * g + k];
+                }
+                cs = __shfl(cs, l31, 64);
+                if (hh == 1) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (ib + 8 * g + 4 + k < hw) cs += wacc[mi][ni][4 * g + k];
+                    if (j < hw && ib + 8 * g < hw) colpart[((long)b * nblk + (ib >> 3) + g) * hw + j] = cs;
+                }
+            }
+        }
+#undef GLOAD
+#undef LSTORE
+}
+
+// ------------------------------------------------------------------------------------------------
 // A remainder of at most ATT_EDGE_MAX rows (L % 128) is finished by the row / edge paths; the tiles then start at it.
 static int attn_origin(int L) {
     const int r = L % 128;
@@ -698,4 +889,42 @@ extern "C" int wc_attn_mean(const void* qkv, const float* lse, float* mean, int 
     wc_prof_end(pr, mean_names[DH == 64 ? 0 : 1][r == 0 ? 0 : (r == 1 ? 1 : 2)], 2.0 * B * H * (double)L * L * DH, stream);
     WC_LAUNCH_CHECK("attn_mean_kernel");
     return WC_OK;
+}
+
+// W (B,hw,hw) and c1 = 1 / colsum(W) as wc_aff_weight_c1 gives them from the nmaps head-mean maps, computed from the layers'
+// packed qkv and lse instead (no seg factor: the seg-trans branch keeps the map path).  ws: B * ceil(hw/8) * hw floats.
+extern "C" int wc_attn_aff_weight(const void* const* h_qkv, const float* const* h_lse, int nmaps, const float* wgt, float* W,
+                                  float* c1, float* ws, int B, int L, int H, int DH, void* stream) {
+    WC_CHECK_ARG(h_qkv && h_lse && nmaps >= 1 && nmaps <= 12 && wgt && W && c1 && ws && B > 0 && B <= 65535 && L > 1 && H > 0 &&
+                 H <= 65535, "wc_attn_aff_weight: bad argument");
+    WC_CHECK_ARG(DH == 64 || DH == 32, "wc_attn_aff_weight: head dim must be 32 or 64 (got %d)", DH);
+    WC_CHECK_ARG(wc_aff_fused_supported(L - 1), "wc_attn_aff_weight: %d patch tokens are not served by the fused sweeps", L - 1);
+    AttnLayerPtrs ops;
+    for (int i = 0; i < 12; ++i) {
+        ops.qkv[i] = i < nmaps ? (const __half*)h_qkv[i] : nullptr;
+        ops.lse[i] = i < nmaps ? h_lse[i] : nullptr;
+        WC_CHECK_ARG(i >= nmaps || (ops.qkv[i] && ops.lse[i]), "wc_attn_aff_weight: layer %d has no operands", i);
+        WC_CHECK_ARG((uintptr_t)ops.qkv[i] % 16 == 0, "wc_attn_aff_weight: qkv must be 16-byte aligned");
+    }
+    const int E = H * DH, hw = L - 1, nt = wc_cdiv(hw, 128);
+    // (the kernel addresses an image's qkv rows with 32-bit byte offsets)
+    WC_CHECK_ARG((long)nt * nt * (B + 7) < (1L << 30) && (long)L * 6 * E < (1L << 31), "wc_attn_aff_weight: bad shape");
+    dim3 grid((unsigned)(nt * nt * ((B + 7) / 8 * 8)));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = 2 * ((size_t)2 * 128 * (DH * 2 + 16) + 512);       // 2 x BUF of the kernel
+    static bool lds_attr_set = false;
+    if (!lds_attr_set) {         // more than 64 KiB of dynamic LDS
+        WC_CHECK_ARG(hipFuncSetAttribute((const void*)attn_affw_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess &&
+                     hipFuncSetAttribute((const void*)attn_affw_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) == hipSuccess,
+                     "wc_attn_aff_weight: cannot reserve 80 KiB of LDS");
+        lds_attr_set = true;
+    }
+    const int pr = wc_prof_begin(stream);
+    if (DH == 64)
+        hipLaunchKernelGGL((attn_affw_kernel<64>), grid, dim3(256), lds, st, ops, nmaps, wgt, W, ws, L, H, E, nt, B);
+    else
+        hipLaunchKernelGGL((attn_affw_kernel<32>), grid, dim3(256), lds, st, ops, nmaps, wgt, W, ws, L, H, E, nt, B);
+    wc_prof_end(pr, DH == 64 ? "attn_affw_kernel<64>" : "attn_affw_kernel<32>", 2.0 * B * (double)hw * hw * DH * H * nmaps, stream);
+    WC_LAUNCH_CHECK("attn_affw_kernel");
+    return wc_aff_colreduce_c1(ws, c1, B, hw, wc_cdiv(hw, 8), stream);
 }

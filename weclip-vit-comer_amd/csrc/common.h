@@ -41,6 +41,11 @@ void wc_prof_end2(int idx, const char* name, double work, double bytes, void* st
 int wc_prof_begin_always(void* stream);            // records whenever profiling is on (brackets around many launches)
 void wc_prof_end_n(int idx, const char* name, double work, void* stream, int n);   // one event pair around n launches
 
+// affinity.hip, for the affinity weight built in attention.hip: whether the fused sweeps serve `hw` patch tokens, and
+// c1[b, j] = 1 / sum_blk colpart[(b * nblk + blk) * hw + j] (aff_colreduce_kernel, the first Sinkhorn column scale)
+extern "C" int wc_aff_fused_supported(int hw);
+int wc_aff_colreduce_c1(const float* colpart, float* c1, int B, int hw, int nblk, void* stream);
+
 // 64-lane wavefront reductions (DPP/shuffle based).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

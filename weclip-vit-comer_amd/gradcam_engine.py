@@ -131,10 +131,10 @@ class LastLayerState:
         return cams, probs, w
 
 
-def last_layer_forward(clip_model, rows, B, Lq, want_mean=True):
+def last_layer_forward(clip_model, rows, B, Lq, want_mean=True, defer_mean=False):
     """rows (B*L, E) fp32 = output of block layers-1.  Runs the last block keeping what the
-    analytic backward needs."""
+    analytic backward needs.  `defer_mean`: the state's `mean` is the block's ops.AttnOperands (run_block)."""
     blk = clip_model.visual.transformer.resblocks[-1]
     keep = {}
-    x2, mean = VE.run_block(blk.pack(), rows, B, Lq, want_mean=want_mean, keep=keep, tag=b"@vit_attn")
+    x2, mean = VE.run_block(blk.pack(), rows, B, Lq, want_mean=want_mean, keep=keep, tag=b"@vit_attn", defer_mean=defer_mean)
     return LastLayerState(clip_model, x2, mean, keep, B, Lq)

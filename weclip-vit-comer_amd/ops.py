@@ -149,9 +149,20 @@ def layernorm(x, weight, bias, *, eps=1e-5, want32=False, want16=True, with_lo=F
     return y32, (Split(hi, lo) if want16 else None)
 
 
-def attention(qkv16, B, Lq, H, DH, want_mean=True, want_o32=False):
+class AttnOperands:
+    """What a layer's head-mean map is computed from, handed on in the map's place: the packed qkv (B*L, 3E) fp16 and lse (B,H,L)
+    f32 of `attention`.  cam_pipeline.affinity_weight_qk builds the affinity weight from eight of them in one launch
+    (wc_attn_aff_weight) without any (B,L,L) map."""
+    __slots__ = ("qkv", "lse", "B", "L", "H", "DH")
+
+    def __init__(self, qkv, lse, B, Lq, H, DH):
+        self.qkv, self.lse, self.B, self.L, self.H, self.DH = qkv, lse, B, Lq, H, DH
+
+
+def attention(qkv16, B, Lq, H, DH, want_mean=True, want_o32=False, defer_mean=False):
     """qkv16 (B*L, 3E) fp16 with q pre-scaled by log2(e)/sqrt(DH).
-    Returns (o16 (B*L, E) fp16, lse (B,H,L) f32, mean (B,L,L) f32 or None)."""
+    Returns (o16 (B*L, E) fp16, lse (B,H,L) f32, mean (B,L,L) f32 or None).
+    `defer_mean` (with want_mean): no wc_attn_mean launch; `mean` is the layer's AttnOperands instead."""
     E = H * DH
     dev = qkv16.device
     lib = L.lib()
@@ -160,7 +171,9 @@ def attention(qkv16, B, Lq, H, DH, want_mean=True, want_o32=False):
     o32 = torch.empty(B * Lq, E, device=dev, dtype=F32) if want_o32 else None
     lib.wc_attn_fwd(L.ptr(qkv16, F16, "qkv"), L.ptr(o16), L.ptr(o32), L.ptr(lse), B, Lq, H, DH, L.stream())
     mean = None
-    if want_mean:
+    if want_mean and defer_mean:
+        mean = AttnOperands(qkv16, lse, B, Lq, H, DH)
+    elif want_mean:
         mean = torch.empty(B, Lq, Lq, device=dev, dtype=F32)
         lib.wc_attn_mean(L.ptr(qkv16), L.ptr(lse), L.ptr(mean), B, Lq, H, DH, L.stream())
     if want_o32:
