@@ -1005,6 +1005,43 @@ int wc_mmd_rbf(const void* source, const void* target, int is_half, float* loss,
 int wc_mmd_rbf_kernel(const void* source, const void* target, int is_half, float* K, void* ws, int B, int d, int kernel_num,
                       double kernel_mul, double fix_sigma, void* stream);
 
+/* ---- CAM seeds: threshold sweep, seed label maps and their scores (csrc/camseed.hip) ----------- */
+/* Common inputs: cam_f16 (P, HW) fp16, the bucket buffer of clip/generate_cams.py (the (image, class) pairs of an image
+ * consecutive; 16-byte aligned base, a pair itself only 2-byte aligned when HW is odd); first (B+1) int32 = first pair of every
+ * image; keys (P) int32 = 0-based foreground class id of every pair, distinct within an image, in any order; gt_u8 (B, HW)
+ * uint8 (4-byte aligned base).  All device memory.  Per pixel v = max_k cam[k] and c = 1 + the class id attaining it, the
+ * smallest class id on a tie: the arg-max over the class axis of the dense `cls_label * cam` of utils/camutils.py:11-14 (equal
+ * to it for maps >= 0, which scale_cam_image's are).  fp16 widens to f32 exactly; every comparison is f32.
+ * Every entry: integer atomics only, no allocation, no host read, limits checked before anything is launched (WC_ERR_ARG);
+ * flag (int32, caller-zeroed) is set by a pair table that leaves [0, P) or gives an image no pair or more than Kmax, by a
+ * class id outside [0, nc - 1) and by a slot outside the table; such pixels are not counted.
+ * wc_cam_seed_sweep: utils/camutils.py:13-15 (`cam_value <= bkg_score` -> 0: a value equal to the threshold is background) +
+ *   utils/evaluate.py:9-16 (`_fast_hist`; gt >= nc skipped) for T thresholds in one pass.  thresholds: HOST array of T floats,
+ *   finite and strictly ascending, 1 <= T <= 64; 2 <= nc <= 256; Kmax >= the largest number of pairs of an image.  With
+ *   j* = #{j : t_j < v}: bins[gt][c][j*] += 1, bins (nc, nc, T+1) int64, ADDED to and never zeroed.  Per-workgroup 32-bit LDS
+ *   cells over (gt, the image's slot, j*) while they and the thresholds fit 64 KiB (nc * Kmax * (T+1) * 4 + 256 bytes), flushed by
+ *   64-bit global atomics; global
+ *   atomics per pixel otherwise or with force_global != 0 (same counts).  1 <= HW <= 2^28, 1 <= B <= 65535.
+ * wc_cam_seed_sweep_path: *use_lds (HOST out-parameter) = 1 when the sweep stages in LDS for (nc, Kmax, T).
+ *   The per-threshold confusion matrices follow from bins by two cumulative sums (clip/cam_seeds.py confusion_from_bins).
+ * wc_cam_seed_labels: the two slot maps of the per-image body of utils/camutils.py:55-79 at the image's own size:
+ *   lab_low / lab_high (B, HW) int64 (what wc_dcrf_unary_label reads) = 1 + rank of c's class id among the image's ids
+ *   ascending (:56 `nonzero`) where v > low_thre / high_thre, else 0 (:61-65: the threshold plane is channel 0 and wins a tie).
+ *   At most 255 pairs per image.
+ * wc_cam_seed_merge: utils/camutils.py:77-79 for B images in one launch: label_u8 (B, HW) = slot_class[b][high], then 255
+ *   where high == 0, then 0 where high == 0 and low == 0; slot_class (B, S) int32, entry 0 = 0, entry s = 1 + the s-th smallest
+ *   class id.  On un-refined slot maps this is cam_to_label(..., ignore_mid=True) of :20-22.  cmap_rgb (B, HW, 3) uint8 or NULL:
+ *   the VOC colour (utils/imutils.py:136-154).  gt_u8 or NULL; with it `pseudo_scores` (utils/evaluate.py:38-45): hist (nc, nc)
+ *   int64 += (gt, label) over gt < nc and label != 255, cover[0] += those pixels, cover[1] += the pixels with gt < nc (int64[2]).
+ */
+int wc_cam_seed_sweep_path(int nc, int Kmax, int T, int* use_lds);
+int wc_cam_seed_sweep(const void* cam_f16, const int* first, const int* keys, const void* gt_u8, const float* thresholds, long* bins,
+                      int* flag, int B, int P, long HW, int nc, int T, int Kmax, int force_global, void* stream);
+int wc_cam_seed_labels(const void* cam_f16, const int* first, const int* keys, long* lab_low, long* lab_high, int* flag, int B, int P,
+                       long HW, float low_thre, float high_thre, void* stream);
+int wc_cam_seed_merge(const long* lab_low, const long* lab_high, const int* slot_class, const void* gt_u8, void* label_u8,
+                      void* cmap_rgb, long* hist, long* cover, int* flag, int B, long HW, int S, int nc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,13 +240,16 @@ def save_payload(cam_out_dir, name, payload):
     np.save(os.path.join(cam_out_dir, name.replace("jpg", "npy")), payload)
 
 
-def run_worker(process_id, dataset_list, img_root, cam_out_dir, generator_factory, read_item, chunk=16):
-    """One worker: device process_id % device_count, its split_dataset share, `chunk` images per CamGenerator call."""
+def run_worker(process_id, dataset_list, img_root, cam_out_dir, generator_factory, read_item, chunk=16, seeds=None):
+    """One worker: device process_id % device_count, its split_dataset share, `chunk` images per CamGenerator call.  seeds:
+    seed_options()'s dict or None -- with it the maps stay on the device, go through a cam_seeds.SeedEvaluator chunk by chunk,
+    and the worker leaves its counts in seed_part_<process_id>.npz next to the CAMs."""
     items = dataset_list[process_id]
     if len(items) == 0:          # more workers than images: nothing to do, the GPU is not touched
         return 0
     torch.cuda.set_device(process_id % torch.cuda.device_count())
     gen = generator_factory()
+    ev = seeds["factory"]() if seeds else None
     for k in range(0, len(items), chunk):
         names, images, ids = [], [], []
         for it in items[k:k + chunk]:
@@ -254,12 +257,105 @@ def run_worker(process_id, dataset_list, img_root, cam_out_dir, generator_factor
             names.append(name)
             images.append(load_image(os.path.join(img_root, name)))
             ids.append(lab)
-        for name, payload in zip(names, gen(images, ids)):
+        if ev is None:
+            payloads = gen(images, ids)
+        else:
+            payloads = gen(images, ids, to_numpy=False)
+            stems = [os.path.splitext(os.path.basename(n))[0] for n in names]
+            gts = [read_gt(seeds["gt_root"], s) for s in stems] if seeds["gt_root"] else None
+            ev.add(payloads, images, gts, stems)
+        for name, payload in zip(names, payloads):
             if payload is None:
                 print("{} not have valid object".format(name))
-            else:
+            elif ev is None:
                 save_payload(cam_out_dir, name, payload)
+            elif seeds["save_cams"]:
+                save_payload(cam_out_dir, name, {"keys": payload["keys"].numpy(), "attn_highres": payload["attn_highres"].cpu().numpy()})
+    if ev is not None:
+        ev.finish()
+        save_part(cam_out_dir, process_id, ev.arrays())
     return 0
+
+
+# ---- seeds: threshold sweep, pseudo-label masks and their scores on the device (cam_seeds.py) -----------
+SEED_FLAGS = ("gt_root", "eval_thresholds", "pseudo_dir", "no_save_cams")
+
+
+def add_seed_arguments(p):
+    p.add_argument("--gt_root", type=str, default=None, help="ground-truth label maps <name>.png (8-bit index images): scores")
+    p.add_argument("--eval_thresholds", type=str, default=None,
+                   help="background thresholds of the seed mIoU sweep, first:last:step (0.05:0.80:0.05) or a comma list; needs --gt_root")
+    p.add_argument("--pseudo_dir", type=str, default=None, help="write the pseudo-label masks to DIR/prediction and DIR/prediction_cmap")
+    p.add_argument("--low_thre", type=float, default=0.35,
+                   help="at or below it a pixel is background (default 0.35: the AFA lineage's value, the reference's YAMLs carry none)")
+    p.add_argument("--high_thre", type=float, default=0.55,
+                   help="above it a pixel takes its class, between the two it is ignored (255) (default 0.55: the AFA lineage's value)")
+    p.add_argument("--refine", choices=("none", "crf"), default="none", help="pass the two seed maps through the dense CRF before the merge")
+    p.add_argument("--crf_bilateral", choices=("exact", "lattice"), default="exact")
+    p.add_argument("--no_save_cams", action="store_true", help="do not write the <name>.npy maps (scores / masks only)")
+
+
+def seed_options(args, num_classes):
+    """None for a run with none of the new flags (such a run builds no evaluator and imports none of its code); otherwise the
+    dict run_worker takes.  Flag combinations that would compute nothing are refused here, before any worker starts."""
+    if not any(getattr(args, f, None) for f in SEED_FLAGS):
+        if args.refine != "none":
+            raise RuntimeError("--refine needs --pseudo_dir")
+        return None
+    if args.eval_thresholds and not args.gt_root:
+        raise RuntimeError("--eval_thresholds needs --gt_root")
+    if not args.eval_thresholds and not args.pseudo_dir:
+        raise RuntimeError("--gt_root / --no_save_cams need --eval_thresholds or --pseudo_dir: nothing to compute")
+    if args.refine != "none" and not args.pseudo_dir:
+        raise RuntimeError("--refine needs --pseudo_dir")
+    from . import cam_seeds as CS
+    thresholds = CS.parse_thresholds(args.eval_thresholds) if args.eval_thresholds else None
+    kw = dict(num_classes=num_classes, thresholds=thresholds, low_thre=args.low_thre, high_thre=args.high_thre, refine=args.refine,
+              crf_bilateral=args.crf_bilateral, out_dir=args.pseudo_dir, masks=args.pseudo_dir is not None)
+    CS.SeedEvaluator(**{**kw, "out_dir": None})          # argument errors now, not in every worker
+    return {"factory": lambda: CS.SeedEvaluator(**kw), "gt_root": args.gt_root, "save_cams": not args.no_save_cams, "kw": kw}
+
+
+def read_gt(gt_root, stem):
+    from ..datasets.voc import read_label
+    return read_label(os.path.join(gt_root, stem + ".png"))
+
+
+def part_path(cam_out_dir, process_id):
+    return os.path.join(cam_out_dir, f"seed_part_{int(process_id)}.npz")
+
+
+def save_part(cam_out_dir, process_id, arrays):
+    """A worker's raw counts (cam_seeds.SeedEvaluator.arrays()); a leg that did not run is stored as an empty array."""
+    none = np.zeros(0, np.int64)
+    np.savez(part_path(cam_out_dir, process_id), images=np.int64(arrays["images"]),
+             **{k: none if arrays[k] is None else arrays[k] for k in ("bins", "hist", "cover")})
+
+
+def clear_parts(cam_out_dir):
+    for i in range(MAX_WORKERS):
+        if os.path.exists(part_path(cam_out_dir, i)):
+            os.remove(part_path(cam_out_dir, i))
+
+
+def write_seed_scores(cam_out_dir, n_workers, seeds):
+    """Sum the workers' parts into <cam_out_dir>/seed_scores.json (cam_seeds.summarise of the summed counts)."""
+    from . import cam_seeds as CS
+    total = {"bins": None, "hist": None, "cover": None, "images": 0}
+    for i in range(n_workers):
+        if not os.path.exists(part_path(cam_out_dir, i)):        # a worker with an empty share
+            continue
+        with np.load(part_path(cam_out_dir, i)) as part:
+            total["images"] += int(part["images"])
+            for k in ("bins", "hist", "cover"):
+                if part[k].size:
+                    total[k] = part[k].astype(np.int64) if total[k] is None else total[k] + part[k]
+    kw = seeds["kw"]
+    result = CS.summarise(kw["num_classes"], kw["thresholds"], total["bins"], total["hist"], total["cover"], total["images"],
+                          kw["low_thre"], kw["high_thre"], kw["refine"], kw["crf_bilateral"])
+    path = os.path.join(cam_out_dir, "seed_scores.json")
+    CS.write_scores(path, result)
+    return path
 
 
 def worker_commands(num_workers, module, argv):

@@ -9,6 +9,7 @@ from . import generate_cams as G
 from . import generate_cams_voc12 as V
 
 BOX_THRESHOLD = 0.7
+NUM_CLASSES = 81            # background included (the seed scores of --gt_root)
 FG_NAMES, BG_NAMES = "new_class_names_coco", "BACKGROUND_CATEGORY_COCO"
 
 MODULE = __spec__.name if __spec__ is not None else __name__      # importable name, also under `python -m`
@@ -23,6 +24,7 @@ def parse_args(argv=None):
     p.add_argument("--num_workers", type=int, default=1)
     p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
     p.add_argument("--worker_id", type=int, default=None, help=argparse.SUPPRESS)
+    G.add_seed_arguments(p)
     return p.parse_args(argv)
 
 
@@ -42,11 +44,20 @@ def main(argv=None):
     os.makedirs(args.cam_out_dir, exist_ok=True)
     items = read_split(args.split_file)
     n = min(max(args.num_workers, 1), G.MAX_WORKERS)
+    seeds = G.seed_options(args, NUM_CLASSES)
+    if seeds and args.worker_id is None:
+        G.clear_parts(args.cam_out_dir)
     if n > 1 and args.worker_id is None:
-        return G.spawn_workers(n, MODULE, argv)
+        rc = G.spawn_workers(n, MODULE, argv)
+        if seeds:
+            G.write_seed_scores(args.cam_out_dir, n, seeds)
+        return rc
     shares = G.split_dataset(items, n)
-    return G.run_worker(args.worker_id or 0, shares, args.img_root, args.cam_out_dir,
-                        lambda: V.make_generator(args.model, FG_NAMES, BG_NAMES, BOX_THRESHOLD), lambda it: it)
+    rc = G.run_worker(args.worker_id or 0, shares, args.img_root, args.cam_out_dir,
+                      lambda: V.make_generator(args.model, FG_NAMES, BG_NAMES, BOX_THRESHOLD), lambda it: it, seeds=seeds)
+    if seeds and args.worker_id is None:
+        G.write_seed_scores(args.cam_out_dir, 1, seeds)
+    return rc
 
 
 if __name__ == "__main__":

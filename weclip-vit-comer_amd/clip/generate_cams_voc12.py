@@ -17,6 +17,7 @@ import numpy as np
 from . import generate_cams as G
 
 BOX_THRESHOLD = 0.4          # scoremap2bbox threshold of the VOC dumper (voc12:170)
+NUM_CLASSES = 21            # background included (the seed scores of --gt_root)
 FG_NAMES, BG_NAMES = "new_class_names", "BACKGROUND_CATEGORY"
 
 MODULE = __spec__.name if __spec__ is not None else __name__      # importable name, also under `python -m`
@@ -31,6 +32,7 @@ def parse_args(argv=None):
     p.add_argument("--num_workers", type=int, default=1)
     p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
     p.add_argument("--worker_id", type=int, default=None, help=argparse.SUPPRESS)
+    G.add_seed_arguments(p)
     return p.parse_args(argv)
 
 
@@ -73,11 +75,20 @@ def main(argv=None):
     os.makedirs(args.cam_out_dir, exist_ok=True)
     train_list = [str(x) + ".jpg" for x in np.atleast_1d(np.loadtxt(args.split_file, dtype=str))]
     n = min(max(args.num_workers, 1), G.MAX_WORKERS)
+    seeds = G.seed_options(args, NUM_CLASSES)
+    if seeds and args.worker_id is None:
+        G.clear_parts(args.cam_out_dir)
     if n > 1 and args.worker_id is None:
-        return G.spawn_workers(n, MODULE, argv)
+        rc = G.spawn_workers(n, MODULE, argv)
+        if seeds:
+            G.write_seed_scores(args.cam_out_dir, n, seeds)
+        return rc
     shares = G.split_dataset(train_list, n)
-    return G.run_worker(args.worker_id or 0, shares, args.img_root, args.cam_out_dir, lambda: make_generator(args.model),
-                        read_item_factory(args.img_root))
+    rc = G.run_worker(args.worker_id or 0, shares, args.img_root, args.cam_out_dir, lambda: make_generator(args.model),
+                      read_item_factory(args.img_root), seeds=seeds)
+    if seeds and args.worker_id is None:
+        G.write_seed_scores(args.cam_out_dir, 1, seeds)
+    return rc
 
 
 if __name__ == "__main__":

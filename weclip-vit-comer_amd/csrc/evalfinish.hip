@@ -9,40 +9,11 @@
 //   label_finish_kernel : the same outputs for a ready int64 arg-max map (the CRF leg)                               (:158-161)
 // Bilinear arithmetic (so each arg-max is resize_argmax_kernel's) and the histogram skeleton: resample.h.  Flag contract =
 // confusion_hist_kernel's.
-// The colour of label v is the PASCAL VOC bit-interleaved map, ef_colour of voc_colour.h (shared with panels.hip).
+// The colour of label v is the PASCAL VOC bit-interleaved map, ef_colour of voc_colour.h (shared with panels.hip); the 4-label
+// store ef_store lives there too (shared with camseed.hip).
 #include "common.h"
 #include "resample.h"
 #include "voc_colour.h"
-
-// 4 labels -> the uint8 map and the RGB image at pixels [i, i + n) of a row-major grid.  Full groups whose first pixel is
-// 4-byte aligned in the output go out as one 32-bit and three 32-bit vector stores (neighbouring lanes write neighbouring words),
-// the rest by bytes.
-__device__ __forceinline__ void ef_store(const unsigned int* lab, int n, long i, unsigned char* __restrict__ u8,
-                                         unsigned char* __restrict__ rgb) {
-    if (u8) {
-        if (n == 4 && ((size_t)(u8 + i) & 3) == 0) {
-            *reinterpret_cast<unsigned int*>(u8 + i) = lab[0] | (lab[1] << 8) | (lab[2] << 16) | (lab[3] << 24);
-        } else {
-            for (int k = 0; k < n; ++k) u8[i + k] = (unsigned char)lab[k];
-        }
-    }
-    if (rgb) {
-        unsigned int c[4] = {0, 0, 0, 0};
-        for (int k = 0; k < n; ++k) c[k] = ef_colour(lab[k]);
-        if (n == 4 && ((size_t)(rgb + 3 * i) & 3) == 0) {
-            unsigned int* o = reinterpret_cast<unsigned int*>(rgb + 3 * i);
-            o[0] = c[0] | (c[1] << 24);
-            o[1] = (c[1] >> 8) | (c[2] << 16);
-            o[2] = (c[2] >> 16) | (c[3] << 8);
-        } else {
-            for (int k = 0; k < n; ++k) {
-                rgb[3 * (i + k) + 0] = (unsigned char)(c[k] & 255u);
-                rgb[3 * (i + k) + 1] = (unsigned char)((c[k] >> 8) & 255u);
-                rgb[3 * (i + k) + 2] = (unsigned char)(c[k] >> 16);
-            }
-        }
-    }
-}
 
 // One thread per group of 4 adjacent x of one label row (grid-stride over the Hl * ceil(Wl / 4) groups).  lds_mask bit k: histogram
 // k (0 seg1, 1 msc, 2 cam) is counted in LDS, at cell offset (number of lower set bits) * nc * nc; a histogram that is absent

@@ -595,8 +595,65 @@ def _(source, target, kernel_mul, kernel_num, fix_sigma):
     return source.new_empty((N, N), dtype=F32)
 
 
+
+@torch.library.custom_op(f"{_LIB}::cam_seed_sweep", mutates_args=(), device_types="cuda")
+def cam_seed_sweep(cams: Tensor, first: Tensor, keys: Tensor, gt: Tensor, thresholds: List[float], num_classes: int,
+                   kmax: int) -> Tensor:
+    """The background-threshold sweep of `_fast_hist(gt, cam_to_label(cam))` (reference utils/camutils.py:8-16,
+    utils/evaluate.py:9-16; csrc/camseed.hip) in one pass: cams (P, HW) fp16, first (B+1) / keys (P) int32 device tables, gt
+    (B, HW) uint8, T ascending thresholds, kmax >= the most pairs of an image -> bins (nc, nc, T+1) int64 counts over
+    (gt, class, number of thresholds below the pixel's maximum); clip.cam_seeds.confusion_from_bins turns them into the T
+    confusion matrices.  The tables are device tensors here, so a class id outside [0, nc - 1) is skipped and raises the device
+    flag of clip.cam_seeds.check_tables_in_range instead of a host error."""
+    from .clip import cam_seeds as CS
+    t = CS.PairTables.from_device(num_classes, first, keys, Kmax=kmax)
+    return CS.sweep_bins(cams, None, gt, list(thresholds), num_classes, tables=t)
+
+
+@cam_seed_sweep.register_fake
+def _(cams, first, keys, gt, thresholds, num_classes, kmax):
+    return cams.new_empty((num_classes, num_classes, len(thresholds) + 1), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{_LIB}::cam_seed_labels", mutates_args=(), device_types="cuda")
+def cam_seed_labels(cams: Tensor, first: Tensor, keys: Tensor, low_thre: float, high_thre: float) -> Tuple[Tensor, Tensor]:
+    """The two slot maps of the per-image body of cam_to_fg_bg_label (reference utils/camutils.py:55-65; csrc/camseed.hip) at the
+    image's own size: cams (P, HW) fp16, first (B+1) / keys (P) int32 -> (lab_low, lab_high) (B, HW) int64, slot 1 + rank of
+    the winning class among the image's ids where the maximum exceeds the threshold, else 0."""
+    from .clip import cam_seeds as CS
+    return CS.seed_labels(cams, None, low_thre, high_thre, tables=CS.PairTables.from_device(CS.MAX_CLASSES, first, keys))
+
+
+@cam_seed_labels.register_fake
+def _(cams, first, keys, low_thre, high_thre):
+    B = first.shape[0] - 1
+    return cams.new_empty((B, cams.shape[1]), dtype=torch.int64), cams.new_empty((B, cams.shape[1]), dtype=torch.int64)
+
+
+@torch.library.custom_op(f"{_LIB}::cam_seed_merge", mutates_args=(), device_types="cuda")
+def cam_seed_merge(lab_low: Tensor, lab_high: Tensor, slot_class: Tensor, gt: Optional[Tensor],
+                   num_classes: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The merge of cam_to_fg_bg_label (reference utils/camutils.py:77-79) + the `pseudo_scores` histogram
+    (utils/evaluate.py:38-45) + the VOC colour image for the B images of a bucket in one launch (csrc/camseed.hip): slot maps
+    (B, HW) int64, slot_class (B, S) int32, gt (B, HW) uint8 or None -> (label (B, HW) uint8, cmap (B, HW, 3) uint8, hist
+    (nc, nc) int64, cover int64[2] = [labelled pixels with gt < nc, pixels with gt < nc]; zeros without gt)."""
+    from .clip import cam_seeds as CS
+    t = CS.PairTables.from_device(num_classes, slot_class=slot_class)
+    label, cmap, hist, cover = CS.merge_labels(lab_low, lab_high, None, num_classes, gt=gt, want_cmap=True, tables=t)
+    if hist is None:
+        hist = lab_high.new_zeros((num_classes, num_classes))
+        cover = lab_high.new_zeros((2,))
+    return label, cmap, hist, cover
+
+
+@cam_seed_merge.register_fake
+def _(lab_low, lab_high, slot_class, gt, num_classes):
+    return (lab_high.new_empty(lab_high.shape, dtype=torch.uint8), lab_high.new_empty(tuple(lab_high.shape) + (3,), dtype=torch.uint8),
+            lab_high.new_empty((num_classes, num_classes)), lab_high.new_empty((2,)))
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
        "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
        "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice", "dense_energy_lattice", "energy_term_lattice",
-       "mmd_rbf", "rbf_kernel")
+       "mmd_rbf", "rbf_kernel", "cam_seed_sweep", "cam_seed_labels", "cam_seed_merge")
