@@ -890,6 +890,26 @@ int wc_eval_finish(const float* seg1, const float* msc, const long* cam, const l
 int wc_label_finish(const long* pred, const long* gt, void* out_u8, void* cmap_rgb, long* hist, int* flag, int H, int W, int nc,
                     void* stream);
 
+/* ---- predict entry point: the per-image tail without a label map (csrc/predict.hip) ------------ */
+/* wc_predict_finish: one predicted image in one launch over its own (H,W) grid: the resize + arg-max of
+ *   test_msc_flip_voc.py:92-96, or the arg-max of the CRF's Q of :146-161, the colour image of utils/imutils.py:136-154, and
+ *   the confidence of the arg-max, which the reference does not keep.
+ *   src (C,Hs,Ws) f32: mode 0 logits on the model's grid, mode 1 probabilities with Hs == H and Ws == W (the CRF's Q).
+ *   image (H,W,3) uint8 HWC or NULL.  Per pixel v_c = bilinear(src)[c] (align_corners=False, scale = in / out), best = the first
+ *   maximum over c: the value wc_resize_argmax / wc_eval_finish write, bit for bit.  conf = 1 / sum_c exp(v_c - v_best) (mode 0,
+ *   f32, one pass with a running maximum) or clamp(v_best, 0, 1) (mode 1); conf8 = (int)(255 * conf + 0.5f).  Written label =
+ *   best, or 255 where ignore_below > 0 and conf8 < ignore_below.  Outputs, each NULL-able, written for EVERY pixel:
+ *   pred_u8 (H,W) uint8 = the written label; cmap_rgb (H,W,3) uint8 = its PASCAL VOC colour; conf_u8 (H,W) uint8 = conf8
+ *   (never affected by ignore_below); overlay_rgb (H,W,3) uint8 = (alpha256 * colour + (256 - alpha256) * image + 128) >> 8 per
+ *   channel (needs image).  stats int64[2C + 1], ADDED to and never zeroed: [c] += pixels whose written label is c,
+ *   [C + c] += the sum of their conf8, [2C] += ignored pixels.  Integer atomics only (32-bit LDS cells per workgroup, flushed
+ *   once): two calls give the same bits.  64-bit pixel indices.  One launch, no allocation, no host read.
+ *   WC_ERR_ARG, nothing launched: src NULL; C outside [1,255] (255 is the ignore label); a size <= 0; mode outside {0,1};
+ *   mode 1 with another grid; alpha256 outside [0,256]; ignore_below outside [0,255]; overlay_rgb without image. */
+int wc_predict_finish(const float* src, const unsigned char* image, void* pred_u8, void* cmap_rgb, void* conf_u8,
+                      void* overlay_rgb, long* stats, int C, int Hs, int Ws, int H, int W, int mode, int alpha256, int ignore_below,
+                      void* stream);
+
 /* ---- the AFA pseudo-label chain of utils/camutils.py (csrc/camlabel.hip) ----------------------- */
 /* Every entry checks its limits first and returns WC_ERR_ARG with nothing launched; everything runs on `stream`; no entry
  * allocates, reads device memory on the host or uses an atomic (two calls on the same input give the same bits).

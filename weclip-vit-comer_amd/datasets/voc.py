@@ -129,7 +129,11 @@ class _SegMixin:
     def _init_seg(self, resize_range, rescale_range, crop_size, img_fliplr, ignore_index, aug, name_list_dir):
         self.aug, self.ignore_index, self.resize_range, self.rescale_range = aug, ignore_index, resize_range, rescale_range
         self.crop_size, self.img_fliplr = crop_size, img_fliplr
-        self.label_list = load_cls_label_list(name_list_dir=name_list_dir)
+        # stage "test" never looks a class label up (raw() below): a tree without any label file, such as VOC's test set, opens
+        if self.stage == "test" and not os.path.exists(os.path.join(name_list_dir, "cls_labels_onehot.npy")):
+            self.label_list = {}
+        else:
+            self.label_list = load_cls_label_list(name_list_dir=name_list_dir)
 
     def raw(self, idx):
         name, key, image, label = self.read(idx)

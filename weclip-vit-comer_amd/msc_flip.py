@@ -68,14 +68,16 @@ class MscFlipEvaluator:
             self.crf_hist = torch.zeros(self.nc, self.nc, device=dev, dtype=torch.int64)
 
     @torch.no_grad()
-    def logits(self, inputs, class_ids=None, want_cam=False, cam_size=None):
+    def logits(self, inputs, class_ids=None, want_cam=False, cam_size=None, run_cam=True):
         """inputs (1,3,H,W) -> (seg (nc,h,w): scale-1 un-flipped logits, msc (nc,h,w): multi-scale + flip average).
         class_ids: the image's class ids; the model then gets `labels=[ids, ids]` for every pair (a VOC model built without
         `dataset_root_path` has no other way to its CAM leg).  want_cam: the CAM label map of the scale-1 pair's first image
         (test_msc_flip_voc.py:69-71; None for a model without a CAM leg in 'val') comes back as a third value; cam_size: its
         (H, W) -- the label's, which the reference reads off the GT PNG -- instead of the resized input's.
         With either, the VOC model's CAM / PAR chain is skipped at the non-unit scales, where the reference computes and
-        discards it (seg is bit-equal with and without: tests/test_msc_flip_eval_gpu.py)."""
+        discards it (seg is bit-equal with and without: tests/test_msc_flip_eval_gpu.py).
+        run_cam=False: the chain is skipped at scale 1 as well, so a VOC model needs neither class ids nor a label file (the
+        predict entry point, predict.py); the CAM map that want_cam asks for is then None."""
         x = inputs[0].float().contiguous()
         _, H, W = x.shape
         if self.resize_long:                                  # F.interpolate(size=(_h, _w)): scale = in / out
@@ -89,18 +91,21 @@ class MscFlipEvaluator:
         extended = class_ids is not None or want_cam
         kw = {} if class_ids is None else {"labels": [list(class_ids)] * 2}
         sized = {} if cam_size is None else {"sizes": [tuple(cam_size)] * 2}
-        out = self.model(pair, ["", ""], mode="val", **kw, **sized)
-        segs = _seg_of(out).float().contiguous()
-        seg1 = segs[0].contiguous()
-        msc = torch.empty_like(seg1)
-        w = 1.0 / (1 + sum(1 for s in self.scales if s != 1.0))
-        flip_avg(segs, msc, w, accumulate=False)
-        skip_cam = extended and bool(getattr(self.model, "val_runs_cam", False))
+        runs_cam = bool(getattr(self.model, "val_runs_cam", False))
+        skip_cam = (extended or not run_cam) and runs_cam     # at the non-unit scales
         had = "val_runs_cam" in vars(self.model)
         before = vars(self.model).get("val_runs_cam")
         try:
-            if skip_cam:
+            if not run_cam and runs_cam:
                 self.model.val_runs_cam = False               # instance level: the class keeps its own
+            out = self.model(pair, ["", ""], mode="val", **kw, **sized)
+            segs = _seg_of(out).float().contiguous()
+            seg1 = segs[0].contiguous()
+            msc = torch.empty_like(seg1)
+            w = 1.0 / (1 + sum(1 for s in self.scales if s != 1.0))
+            flip_avg(segs, msc, w, accumulate=False)
+            if skip_cam:
+                self.model.val_runs_cam = False
             for s in self.scales:
                 if s == 1.0:
                     continue

@@ -13,6 +13,7 @@ numpy.  The histograms and the out-of-range flag are read once, in `finish()`.  
 rank evaluates its share of the images and writes their files; rank 0 alone prints and writes `scores.json`.
 """
 import argparse
+import contextlib
 import json
 import os
 import queue
@@ -118,11 +119,9 @@ class WriterPool:
     `finish()`.  alloc / event: the device side (tests pass host stand-ins)."""
 
     def __init__(self, out_dir, writers=4, depth=None, save_logits=False, alloc=_cuda_alloc, event=_cuda_event):
-        self.out_dir, self.dirs = out_dir, {k: os.path.join(out_dir, k) for k in ("logit", "prediction", "prediction_cmap")}
-        for k, d in self.dirs.items():
-            if k != "logit" or save_logits:
-                os.makedirs(d, exist_ok=True)
+        self.out_dir = out_dir
         self.save_logits = bool(save_logits)
+        self._make_dirs()
         self.writers = max(1, int(writers))
         self.depth = int(depth) if depth else 2 * self.writers
         self._alloc = alloc
@@ -136,12 +135,24 @@ class WriterPool:
         for t in self.threads:
             t.start()
 
-    def acquire(self, H, W, logit_shape=None, block=True):
-        """The next slot of the ring with views for an (H, W) image.  block=False: queue.Full when it is still in flight."""
+    def _make_dirs(self):
+        """The directories this pool writes into (a subclass with other files names its own: predict.PredictWriterPool)."""
+        self.dirs = {k: os.path.join(self.out_dir, k) for k in ("logit", "prediction", "prediction_cmap")}
+        for k, d in self.dirs.items():
+            if k != "logit" or self.save_logits:
+                os.makedirs(d, exist_ok=True)
+
+    def _next_slot(self, block):
+        """The next slot of the ring once its writer has freed it.  block=False: queue.Full when it is still in flight."""
         slot = self.slots[self._next]
         if not slot.free.wait(None if block else 0):
             raise queue.Full(f"WriterPool: all {self.depth} buffers are in flight")
         self._next = (self._next + 1) % self.depth
+        return slot
+
+    def acquire(self, H, W, logit_shape=None, block=True):
+        """The next slot of the ring with views for an (H, W) image.  block=False: queue.Full when it is still in flight."""
+        slot = self._next_slot(block)
         n_img = 4 * H * W                                                     # [pred H*W | cmap 3*H*W]; 4-byte aligned end
         n_log = 4 * int(np.prod(logit_shape)) if (self.save_logits and logit_shape is not None) else 0
         need = n_img + 2 * n_log
@@ -213,9 +224,14 @@ def image_of(inputs, mean=None, std=None):
     """inputs (1,3,H,W): the loader's normalised pixels -> the (H,W,3) uint8 image they came from (the CRF's image).  The
     normalisation is (v - mean) / std of an integer v: undoing it lands within 1e-4 of v, and rounding returns v."""
     from .data import MEAN, STD
-    m = torch.tensor(mean or MEAN, device=inputs.device, dtype=F32).view(3, 1, 1)
-    s = torch.tensor(std or STD, device=inputs.device, dtype=F32).view(3, 1, 1)
+    key = (str(inputs.device), tuple(mean or MEAN), tuple(std or STD))
+    if key not in _NORM_ROWS:                                 # built once: a host list -> device tensor makes the host wait
+        _NORM_ROWS[key] = tuple(torch.tensor(v, device=inputs.device, dtype=F32).view(3, 1, 1) for v in key[1:])
+    m, s = _NORM_ROWS[key]
     return (inputs[0].float() * s + m).round().clamp(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+
+_NORM_ROWS = {}
 
 
 class SplitEvaluator:
@@ -368,30 +384,60 @@ def print_scores(result):
         print(result[leg])
 
 
-def main(argv=None):
+@contextlib.contextmanager
+def distributed_run():
+    """The process group of a command-line run (shared with predict.py): -> (rank, world).  A run that ends well meets the other
+    ranks in a barrier; the group is destroyed either way."""
     import torch.distributed as dist
+    from . import train as T
+    world = T.init_distributed()
+    try:
+        yield (dist.get_rank() if world > 1 else 0), world
+        if world > 1:
+            dist.barrier()
+    finally:
+        if world > 1 and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def split_dataset(cfg, args, split, stage):
+    """The Seg dataset of `--dataset` over `split` ("val" reads the label PNGs, "test" does not)."""
+    ds = cfg.dataset
+    if args.dataset == "coco":
+        from .datasets.coco import CocoSegDataset as SegDataset
+    else:
+        from .datasets.voc import VOC12SegDataset as SegDataset
+    return SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=split, stage=stage, aug=False,
+                      ignore_index=ds.ignore_index, num_classes=ds.num_classes)
+
+
+def load_model(cfg, args):
+    """The model of `--dataset` with the weights of `--model_path`, in eval mode."""
+    from . import train as T
+    model = T.build_model(cfg, args.dataset, args.reference_root)
+    model.load_state_dict(torch.load(args.model_path, map_location="cpu"), strict=False)      # test_msc_flip_voc.py:194-196
+    return model.eval()
+
+
+def crf_of(args):
+    """The DenseCRF of `--crf` / `--crf_bilateral` with the reference's parameters, or None."""
+    if not args.crf:
+        return None
+    from .utils.dcrf import DenseCRF
+    return DenseCRF(**CRF_PARAMS, bilateral=args.crf_bilateral)
+
+
+def main(argv=None):
     from . import train as T
     from .datasets import DeviceLoader
     args = parse_args(argv)
     cfg = T.load_config(args.config)
-    world = T.init_distributed()
-    rank = dist.get_rank() if world > 1 else 0
-    try:
+    with distributed_run() as (rank, world):
         ds = cfg.dataset
-        if args.dataset == "coco":
-            from .datasets.coco import CocoSegDataset as SegDataset
-        else:
-            from .datasets.voc import VOC12SegDataset as SegDataset
-        dataset = SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=args.eval_set, stage="val", aug=False,
-                             ignore_index=ds.ignore_index, num_classes=ds.num_classes)
-        model = T.build_model(cfg, args.dataset, args.reference_root)
-        model.load_state_dict(torch.load(args.model_path, map_location="cpu"), strict=False)      # test_msc_flip_voc.py:194-196
-        model.eval()
+        dataset = split_dataset(cfg, args, args.eval_set, "val")
+        model = load_model(cfg, args)
         out_dir, _ = output_dirs(args.work_dir, args.eval_set)
-        crf = None
-        if args.crf:
-            from .utils.dcrf import DenseCRF
-            crf = DenseCRF(**CRF_PARAMS, bilateral=args.crf_bilateral)
+        crf = crf_of(args)
         if rank == 0:
             print(cfg)
             print(args)
@@ -404,11 +450,6 @@ def main(argv=None):
             # scores.json: finish()'s dict plus the four summed histograms ("hist": {leg: nc x nc counts})
             with open(os.path.join(out_dir, "scores.json"), "w") as f:
                 json.dump(to_json(dict(result, hist={k: v.tolist() for k, v in ev.hist_host.items()})), f, allow_nan=False)
-        if world > 1:
-            dist.barrier()
-    finally:
-        if world > 1 and dist.is_initialized():
-            dist.destroy_process_group()
     return 0
 
 

@@ -652,8 +652,35 @@ def _(lab_low, lab_high, slot_class, gt, num_classes):
             lab_high.new_empty((num_classes, num_classes)), lab_high.new_empty((2,)))
 
 
+@torch.library.custom_op(f"{_LIB}::predict_finish", mutates_args=(), device_types="cuda")
+def predict_finish(src: Tensor, image: Optional[Tensor], out_h: int, out_w: int, mode: int, alpha256: int,
+                   ignore_below: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """The per-image tail of the predict entry point in one launch (csrc/predict.hip; reference test_msc_flip_voc.py:92-96,
+    :146-161, utils/imutils.py:136-154): src (C, Hs, Ws) f32 logits (mode 0) or probabilities on the output grid (mode 1), image
+    (H, W, 3) uint8 or None -> (label (H, W) uint8 with 255 where the confidence is below ignore_below, its colour image (H, W, 3)
+    uint8, confidence (H, W) uint8, overlay (H, W, 3) uint8 -- zeros without an image --, stats int64[2C + 1] = per label the
+    pixel count, per label the confidence sum, the ignored pixels).  No autograd: every output is an integer map."""
+    from . import predict as P
+    C = src.shape[0]
+    u8 = lambda *shape: torch.empty(shape, device=src.device, dtype=torch.uint8)      # noqa: E731
+    pred, cmap, conf = u8(out_h, out_w), u8(out_h, out_w, 3), u8(out_h, out_w)
+    overlay = u8(out_h, out_w, 3) if image is not None else torch.zeros(out_h, out_w, 3, device=src.device, dtype=torch.uint8)
+    stats = torch.zeros(2 * C + 1, device=src.device, dtype=torch.int64)
+    P.predict_finish(src, (out_h, out_w), image=image, pred_u8=pred, cmap_rgb=cmap, conf_u8=conf,
+                     overlay_rgb=overlay if image is not None else None, stats=stats, mode=mode, alpha256=alpha256,
+                     ignore_below=ignore_below)
+    return pred, cmap, conf, overlay, stats
+
+
+@predict_finish.register_fake
+def _(src, image, out_h, out_w, mode, alpha256, ignore_below):
+    u8 = lambda *shape: src.new_empty(shape, dtype=torch.uint8)                        # noqa: E731
+    return (u8(out_h, out_w), u8(out_h, out_w, 3), u8(out_h, out_w), u8(out_h, out_w, 3),
+            src.new_empty((2 * src.shape[0] + 1,), dtype=torch.int64))
+
+
 OPS = ("par_forward", "par_labels", "trans_mat", "attention", "linear_f16", "layernorm", "bilinear_resize", "confusion_hist",
        "seg_loss", "ce_loss", "aff_loss", "linear", "linear_bwd", "layer_norm", "layer_norm_bwd", "dense_crf", "encode_text",
        "bilateral_filter_batch", "dense_energy", "dense_energy_bwd", "energy_term", "aff_propagate",
        "panel_images", "panel_labels", "panel_attn", "dense_crf_lattice", "dense_energy_lattice", "energy_term_lattice",
-       "mmd_rbf", "rbf_kernel", "cam_seed_sweep", "cam_seed_labels", "cam_seed_merge")
+       "mmd_rbf", "rbf_kernel", "cam_seed_sweep", "cam_seed_labels", "cam_seed_merge", "predict_finish")
