@@ -198,7 +198,7 @@ def test_writer_pool_makes_only_the_requested_directories(tmp_path):
 
 
 def test_the_parents_pool_is_unchanged(tmp_path):
-    """PredictWriterPool subclasses msc_flip_eval.WriterPool through two hooks; the parent's tree and layout stay."""
+    """PredictWriterPool and msc_flip_eval.WriterPool are siblings on one ring; the evaluation pool's tree and layout stay."""
     from weclip_vit_comer_amd import msc_flip_eval as E
     pool = E.WriterPool(str(tmp_path / "val"), writers=1, alloc=_host_alloc, event=_Event)
     slot = pool.acquire(5, 7)

@@ -287,22 +287,14 @@ class BucketWriter(WriterPool):
     outputs, commit(slot, names) makes the ONE device -> host copy of the bucket, and a writer thread cuts it into the B pairs
     prediction/NAME.png (mode L), prediction_cmap/NAME.png (RGB)."""
 
-    def commit(self, slot, names):
-        need = slot.layout[3]
-        slot.free.clear()
-        slot.host[:need].copy_(slot.dev[:need], non_blocking=True)
-        slot.copied.record()
-        self.jobs.put((slot, list(names)))
-
     def _write(self, slot, names):
         from PIL import Image
         BH, W = slot.layout[:2]
         B = len(names)
         H = BH // B
         slot.copied.synchronize()
-        host = slot.host.numpy()
-        pred = host[:BH * W].reshape(B, H, W)
-        cmap = host[BH * W:4 * BH * W].reshape(B, H, W, 3)
+        pred = self.host(slot, "pred").reshape(B, H, W)
+        cmap = self.host(slot, "cmap").reshape(B, H, W, 3)
         for b, name in enumerate(names):
             Image.fromarray(pred[b], mode="L").save(os.path.join(self.dirs["prediction"], name + ".png"))
             Image.fromarray(cmap[b], mode="RGB").save(os.path.join(self.dirs["prediction_cmap"], name + ".png"))

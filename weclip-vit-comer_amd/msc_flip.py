@@ -186,3 +186,12 @@ def reduce_hist(hist, group=None):
 def shard(items, rank, world):
     """Rank r evaluates items r, r + world, ... (replicas only: images are independent units)."""
     return list(items)[rank::world]
+
+
+def shard_batches(loader, rank, world):
+    """The batches of `loader` that are rank's share: all of them from a loader built with this rank / world, which yields the
+    share already (DeviceLoader's index_plan: order[rank::world]); batches rank, rank + world, ... from any other."""
+    sharded = (getattr(loader, "world", 1), getattr(loader, "rank", 0)) == (world, rank)
+    for i, batch in enumerate(loader):
+        if sharded or i % world == rank:
+            yield batch

@@ -13,24 +13,19 @@ numpy.  The histograms and the out-of-range flag are read once, in `finish()`.  
 rank evaluates its share of the images and writes their files; rank 0 alone prints and writes `scores.json`.
 """
 import argparse
-import contextlib
 import json
 import os
-import queue
-import threading
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from . import msc_flip
+from . import entry, msc_flip
+from .entry import CRF_PARAMS, DEFAULTS, crf_of, distributed_run, load_model, parse_scales, split_dataset  # noqa: F401  (re-exported)
 from .utils import evaluate
+from .utils.writer_ring import WriterRing, _Slot, _cuda_alloc, _cuda_event  # noqa: F401  (re-exported)
 
 F32 = torch.float32
-DEFAULTS = {"voc": ("configs/voc_attn_reg.yaml", "/your/path/WeCLIP/WeCLIP_model_iter_30000.pth"),      # test_msc_flip_voc.py:20-28
-            "coco": ("configs/coco_attn_reg.yaml", "/your/path/WeCLIP/WeCLIP_model_iter_80000.pth"),    # test_msc_flip_coco.py:20-28
-            "seg": ("configs/voc_attn_reg.yaml", "/your/path/WeCLIP/WeCLIP_model_iter_30000.pth")}      # test_msc_flip_seg.py:20-28
-CRF_PARAMS = dict(iter_max=10, pos_xy_std=3, pos_w=3, bi_xy_std=64, bi_rgb_std=5, bi_w=4)               # test_msc_flip_voc.py:126-133
 LEGS = ("cam", "seg", "msc_seg", "crf")
 
 
@@ -54,8 +49,7 @@ def eval_finish(seg1, msc, out_hw, num_classes, cam=None, gt=None, pred1_u8=None
         if t is not None and tuple(t.shape) != (num_classes, num_classes):
             raise RuntimeError(f"eval_finish: {name} must be (num_classes, num_classes)")
     if flag is None:
-        from .validate import _flag
-        flag = _flag(seg1.device)
+        flag = evaluate.range_flag(seg1.device)
     U8, I64 = torch.uint8, torch.int64
     L.lib().wc_eval_finish(L.ptr(seg1, F32, "seg1"), L.ptr(msc, F32, "msc"), L.ptr(cam, I64, "cam"), L.ptr(gt, I64, "gt"),
                            L.ptr(pred1_u8, U8, "pred1_u8"), L.ptr(predm_u8, U8, "predm_u8"), L.ptr(cmap_rgb, U8, "cmap_rgb"),
@@ -73,8 +67,7 @@ def label_finish(pred, num_classes, gt=None, out_u8=None, cmap_rgb=None, hist=No
     if hist is not None and tuple(hist.shape) != (num_classes, num_classes):
         raise RuntimeError("label_finish: hist must be (num_classes, num_classes)")
     if flag is None:
-        from .validate import _flag
-        flag = _flag(pred.device)
+        flag = evaluate.range_flag(pred.device)
     L.lib().wc_label_finish(L.ptr(pred, torch.int64, "pred"), L.ptr(gt, torch.int64, "gt"), L.ptr(out_u8, torch.uint8, "out_u8"),
                             L.ptr(cmap_rgb, torch.uint8, "cmap_rgb"), L.ptr(hist, torch.int64, "hist"),
                             L.ptr(flag, torch.int32, "flag"), H, W, int(num_classes), L.stream())
@@ -87,136 +80,44 @@ def output_dirs(work_dir, eval_set):
     return out, {k: os.path.join(out, k) for k in ("logit", "prediction", "prediction_cmap")}
 
 
-class _Slot:
-    """One buffer pair of the ring: `dev` the kernels write, `host` (pinned) the writers read, one event for the copy between."""
-
-    def __init__(self, event):
-        self.dev = self.host = None
-        self.copied = event
-        self.free = threading.Event()
-        self.free.set()
-        self.views = None
-
-
-def _cuda_alloc(nbytes):
-    return torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-
-
-def _cuda_event():
-    return torch.cuda.Event()
-
-
-class WriterPool:
-    """A ring of `depth` (dev, pinned host) buffer pairs and `writers` host threads behind it.
+class WriterPool(WriterRing):
+    """The evaluation's files behind the ring of utils/writer_ring.py:
 
         slot = pool.acquire(H, W, logit_shape)      # waits until a pair is free: at most `depth` images are in flight
         ... kernels write slot.views["pred"] (H,W) u8, ["cmap"] (H,W,3) u8, ["segs"] / ["msc_segs"] (C,h,w) f32 ...
         pool.commit(slot, name)                      # ONE asynchronous copy dev -> host, an event, and the job is queued
 
-    A writer waits for the slot's event, writes prediction/NAME.png (mode L), prediction_cmap/NAME.png (RGB) and, with
-    save_logits, logit/NAME.npy ({"segs": (1,C,h,w), "msc_segs": (1,C,h,w)} f32, test_msc_flip_voc.py:111), then frees the
-    slot.  The buffers only grow; nothing is allocated per image.  The first exception of a writer is kept and raised by
-    `finish()`.  alloc / event: the device side (tests pass host stand-ins)."""
+    A writer waits for the slot's event and writes prediction/NAME.png (mode L), prediction_cmap/NAME.png (RGB) and, with
+    save_logits, logit/NAME.npy ({"segs": (1,C,h,w), "msc_segs": (1,C,h,w)} f32, test_msc_flip_voc.py:111)."""
 
     def __init__(self, out_dir, writers=4, depth=None, save_logits=False, alloc=_cuda_alloc, event=_cuda_event):
         self.out_dir = out_dir
         self.save_logits = bool(save_logits)
-        self._make_dirs()
-        self.writers = max(1, int(writers))
-        self.depth = int(depth) if depth else 2 * self.writers
-        self._alloc = alloc
-        self.slots = [_Slot(event()) for _ in range(self.depth)]
-        self._next = 0
-        self.jobs = queue.Queue(maxsize=self.depth)
-        self.error = None
-        self.written = 0
-        self._lock = threading.Lock()
-        self.threads = [threading.Thread(target=self._work, name=f"weclip-write-{i}", daemon=True) for i in range(self.writers)]
-        for t in self.threads:
-            t.start()
-
-    def _make_dirs(self):
-        """The directories this pool writes into (a subclass with other files names its own: predict.PredictWriterPool)."""
-        self.dirs = {k: os.path.join(self.out_dir, k) for k in ("logit", "prediction", "prediction_cmap")}
+        self.dirs = {k: os.path.join(out_dir, k) for k in ("logit", "prediction", "prediction_cmap")}
         for k, d in self.dirs.items():
             if k != "logit" or self.save_logits:
                 os.makedirs(d, exist_ok=True)
-
-    def _next_slot(self, block):
-        """The next slot of the ring once its writer has freed it.  block=False: queue.Full when it is still in flight."""
-        slot = self.slots[self._next]
-        if not slot.free.wait(None if block else 0):
-            raise queue.Full(f"WriterPool: all {self.depth} buffers are in flight")
-        self._next = (self._next + 1) % self.depth
-        return slot
+        super().__init__(writers, depth, alloc, event)
 
     def acquire(self, H, W, logit_shape=None, block=True):
         """The next slot of the ring with views for an (H, W) image.  block=False: queue.Full when it is still in flight."""
-        slot = self._next_slot(block)
-        n_img = 4 * H * W                                                     # [pred H*W | cmap 3*H*W]; 4-byte aligned end
-        n_log = 4 * int(np.prod(logit_shape)) if (self.save_logits and logit_shape is not None) else 0
-        need = n_img + 2 * n_log
-        if slot.dev is None or slot.dev.numel() < need:
-            slot.dev, slot.host = self._alloc(int(need * 1.25))
-        d = slot.dev
-        slot.views = {"pred": d[:H * W].view(H, W), "cmap": d[H * W:n_img].view(H, W, 3)}
-        if n_log:
-            slot.views["segs"] = d[n_img:n_img + n_log].view(F32).view(*logit_shape)
-            slot.views["msc_segs"] = d[n_img + n_log:need].view(F32).view(*logit_shape)
-        slot.layout = (H, W, tuple(logit_shape) if n_log else None, need)
+        slot = self.next_slot(block)
+        logits = tuple(logit_shape) if (self.save_logits and logit_shape is not None) else None
+        sections = [("pred", (H, W), torch.uint8), ("cmap", (H, W, 3), torch.uint8)]
+        if logits:
+            sections += [("segs", logits, F32), ("msc_segs", logits, F32)]
+        # packed [pred H*W | cmap 3*H*W], the layout the files were always cut from: it ends 4-byte aligned, where the f32 start
+        slot.layout = (H, W, logits, self.carve(slot, sections, align=1))
         return slot
-
-    def commit(self, slot, name):
-        need = slot.layout[3]
-        slot.free.clear()
-        slot.host[:need].copy_(slot.dev[:need], non_blocking=True)
-        slot.copied.record()
-        self.jobs.put((slot, str(name)))
 
     def _write(self, slot, name):
         from PIL import Image
-        H, W, logit_shape, need = slot.layout
         slot.copied.synchronize()
-        host = slot.host.numpy()
-        Image.fromarray(host[:H * W].reshape(H, W), mode="L").save(os.path.join(self.dirs["prediction"], name + ".png"))
-        Image.fromarray(host[H * W:4 * H * W].reshape(H, W, 3), mode="RGB").save(os.path.join(self.dirs["prediction_cmap"], name + ".png"))
-        if logit_shape is not None:
-            n_log = (need - 4 * H * W) // 2
-            a = host[4 * H * W:4 * H * W + n_log].view(np.float32).reshape((1,) + logit_shape)
-            b = host[4 * H * W + n_log:need].view(np.float32).reshape((1,) + logit_shape)
-            np.save(os.path.join(self.dirs["logit"], name + ".npy"), {"segs": a, "msc_segs": b})
-
-    def _work(self):
-        while True:
-            job = self.jobs.get()
-            try:
-                if job is None:
-                    return
-                slot, name = job
-                try:
-                    self._write(slot, name)
-                    with self._lock:
-                        self.written += 1
-                except BaseException as e:                                    # kept for finish(); the slot is freed either way
-                    with self._lock:
-                        if self.error is None:
-                            self.error = e
-                finally:
-                    slot.free.set()
-            finally:
-                self.jobs.task_done()
-
-    def finish(self):
-        """Wait for every queued file, end the threads, raise the first writer exception.  -> number of images written."""
-        self.jobs.join()
-        for _ in self.threads:
-            self.jobs.put(None)
-        for t in self.threads:
-            t.join()
-        self.threads = []
-        if self.error is not None:
-            raise self.error
-        return self.written
+        Image.fromarray(self.host(slot, "pred"), mode="L").save(os.path.join(self.dirs["prediction"], name + ".png"))
+        Image.fromarray(self.host(slot, "cmap"), mode="RGB").save(os.path.join(self.dirs["prediction_cmap"], name + ".png"))
+        if "segs" in slot.spans:
+            np.save(os.path.join(self.dirs["logit"], name + ".npy"),
+                    {k: self.host(slot, k)[None] for k in ("segs", "msc_segs")})
 
 
 # ---------------------------------------------------------------------------------------------- the split
@@ -288,11 +189,7 @@ class SplitEvaluator:
         """loader: a DeviceLoader over an aug=False Seg dataset (batch_size 1); sharded like `Validator.run`.  -> finish()."""
         from .datasets import labels_from_onehot
         self.model.eval()
-        # a loader built with this rank / world already yields the share (index_plan: order[rank::world])
-        sharded = (getattr(loader, "world", 1), getattr(loader, "rank", 0)) == (self.world, self.rank)
-        for i, (names, inputs, labels, _) in enumerate(loader):
-            if not sharded and i % self.world != self.rank:
-                continue
+        for names, inputs, labels, _ in msc_flip.shard_batches(loader, self.rank, self.world):
             ids = labels_from_onehot(loader.last_cls_labels)[0] if self.has_cam else None
             self.add(names[0], inputs, labels, ids, image=image_of(inputs) if self.crf is not None else None)
         return self.finish()
@@ -301,13 +198,8 @@ class SplitEvaluator:
         """Drain the writers, all-reduce the four histograms and the image count (every rank takes part in every reduce,
         whatever its share), check the flag.  -> {"cam" | "seg" | "msc_seg" | "crf": evaluate.scores_from_hist dict or None for
         an absent leg, "pixels": {leg: histogram sum}, "images": n}."""
-        files_error = None
-        if self.pool is not None:
-            try:
-                self.pool.finish()
-            except BaseException as e:                                        # raised below: the other ranks wait in the reduces
-                files_error = e
-            self.pool = None
+        pool, self.pool = self.pool, None
+        files_error = pool.drain() if pool is not None else None              # raised below: the other ranks wait in the reduces
         hists = {"cam": self.cam_hist, "seg": self.hist, "msc_seg": self.msc_hist, "crf": self.crf_hist}
         for k in LEGS:
             msc_flip.reduce_hist(hists[k])
@@ -328,8 +220,6 @@ class SplitEvaluator:
 
 def to_json(result):
     """finish()'s dict as strict JSON data: numpy scalars -> float, class-id keys -> str, non-finite -> None."""
-    from .train import strict_json
-
     def plain(v):
         if isinstance(v, dict):
             return {str(k): plain(x) for k, x in v.items()}
@@ -338,41 +228,24 @@ def to_json(result):
         if isinstance(v, (np.integer, int)):
             return int(v)
         return v
-    return strict_json(plain(result))
+    return entry.strict_json(plain(result))
 
 
 # ---------------------------------------------------------------------------------------------- the command line
-def parse_scales(text):
-    return [float(s) for s in str(text).split(",") if s.strip()]
-
-
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m weclip_vit_comer_amd.msc_flip_eval", description=__doc__.split("\n\n")[0])
-    p.add_argument("--config", default=None, type=str, help="the reference's YAML (default: configs/voc_attn_reg.yaml, coco_attn_reg.yaml)")
+    entry.add_model_arguments(p)
+    entry.add_run_arguments(p)
     p.add_argument("--work_dir", default="results", type=str, help="files go under work_dir/eval_set/")
     p.add_argument("--bkg_score", default=0.45, type=float, help="accepted and unused, as in the reference")
-    p.add_argument("--resize_long", default=512, type=int, help="resize the long side")
     p.add_argument("--eval_set", default="val", type=str)
-    p.add_argument("--model_path", default=None, type=str, help="a WeCLIP_model_iter_N.pth (model.state_dict())")
-    p.add_argument("--dataset", choices=("voc", "coco", "seg"), default="voc", help="seg: the supervised variant on VOC")
-    p.add_argument("--scales", type=parse_scales, default=[1.0, 0.75])
-    p.add_argument("--crf", action=argparse.BooleanOptionalAction, default=False, help="the crf_proc leg (commented out in the reference)")
-    p.add_argument("--crf_bilateral", choices=("exact", "lattice"), default="exact",
-                   help="the CRF leg's bilateral message: the exact all-pairs sum, or the permutohedral lattice (as pydensecrf)")
     p.add_argument("--save_logits", action="store_true", help="logit/NAME.npy as the reference writes it")
-    p.add_argument("--threads", type=int, default=8, help="decode threads of the loader")
-    p.add_argument("--writers", type=int, default=4, help="host threads that write the PNG files")
-    p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
     return p
 
 
 def parse_args(argv=None):
     """The parsed arguments with the per-dataset defaults of the reference's three scripts filled in."""
-    args = build_parser().parse_args(argv)
-    config, model_path = DEFAULTS[args.dataset]
-    args.config = args.config or config
-    args.model_path = args.model_path or model_path
-    return args
+    return entry.fill_defaults(build_parser().parse_args(argv))
 
 
 def print_scores(result):
@@ -384,54 +257,10 @@ def print_scores(result):
         print(result[leg])
 
 
-@contextlib.contextmanager
-def distributed_run():
-    """The process group of a command-line run (shared with predict.py): -> (rank, world).  A run that ends well meets the other
-    ranks in a barrier; the group is destroyed either way."""
-    import torch.distributed as dist
-    from . import train as T
-    world = T.init_distributed()
-    try:
-        yield (dist.get_rank() if world > 1 else 0), world
-        if world > 1:
-            dist.barrier()
-    finally:
-        if world > 1 and dist.is_initialized():
-            dist.destroy_process_group()
-
-
-def split_dataset(cfg, args, split, stage):
-    """The Seg dataset of `--dataset` over `split` ("val" reads the label PNGs, "test" does not)."""
-    ds = cfg.dataset
-    if args.dataset == "coco":
-        from .datasets.coco import CocoSegDataset as SegDataset
-    else:
-        from .datasets.voc import VOC12SegDataset as SegDataset
-    return SegDataset(root_dir=ds.root_dir, name_list_dir=ds.name_list_dir, split=split, stage=stage, aug=False,
-                      ignore_index=ds.ignore_index, num_classes=ds.num_classes)
-
-
-def load_model(cfg, args):
-    """The model of `--dataset` with the weights of `--model_path`, in eval mode."""
-    from . import train as T
-    model = T.build_model(cfg, args.dataset, args.reference_root)
-    model.load_state_dict(torch.load(args.model_path, map_location="cpu"), strict=False)      # test_msc_flip_voc.py:194-196
-    return model.eval()
-
-
-def crf_of(args):
-    """The DenseCRF of `--crf` / `--crf_bilateral` with the reference's parameters, or None."""
-    if not args.crf:
-        return None
-    from .utils.dcrf import DenseCRF
-    return DenseCRF(**CRF_PARAMS, bilateral=args.crf_bilateral)
-
-
 def main(argv=None):
-    from . import train as T
     from .datasets import DeviceLoader
     args = parse_args(argv)
-    cfg = T.load_config(args.config)
+    cfg = entry.load_config(args.config)
     with distributed_run() as (rank, world):
         ds = cfg.dataset
         dataset = split_dataset(cfg, args, args.eval_set, "val")

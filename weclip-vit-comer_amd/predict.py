@@ -12,7 +12,7 @@ VOC / COCO tree.  Per image: `MscFlipEvaluator.logits(inputs, run_cam=False)` (t
 grid: the uint8 label map (255 where the confidence is below `--ignore_below`), its colour image, the uint8 confidence map
 (soft-max probability of the arg-max, or the CRF's Q of it, times 255), the colour image blended over the input, and per label
 the pixel count and confidence sum.  The requested maps go to the host in one asynchronous copy into the ring of pinned buffers
-of `msc_flip_eval.WriterPool`; host threads write `prediction/NAME.png` (mode L, or P with the VOC palette: what the VOC
+of `utils.writer_ring.WriterRing`; host threads write `prediction/NAME.png` (mode L, or P with the VOC palette: what the VOC
 evaluation server takes), `prediction_cmap/NAME.png`, `confidence/NAME.png`, `overlay/NAME.png`.  The per-image statistics stay
 in a device table that is read once, in `finish()`, which writes `summary.json`.  Under `python -m torch.distributed.run` every
 rank predicts its share of the images and writes their files; rank 0 writes the one `summary.json`.
@@ -25,8 +25,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import msc_flip
-from . import msc_flip_eval as E
+from . import entry, msc_flip
+from .msc_flip_eval import image_of
+from .utils.writer_ring import WriterRing, _cuda_alloc, _cuda_event
 
 F32 = torch.float32
 KINDS = ("prediction", "prediction_cmap", "confidence", "overlay")
@@ -79,53 +80,41 @@ def parse_outputs(text):
     return tuple(k for k in KINDS if k in names)
 
 
-class PredictWriterPool(E.WriterPool):
-    """`WriterPool` with the predict entry point's files: of the four kinds only those in `outputs` have a directory, a view in the
-    slot and a share of the one device-to-host copy.
+class PredictWriterPool(WriterRing):
+    """The predict entry point's files behind the ring of utils/writer_ring.py: of the four kinds only those in `outputs` have a
+    directory, a view in the slot and a share of the one device-to-host copy.
 
         slot = pool.acquire(H, W)        # slot.views[kind]: (H,W) u8 for prediction / confidence, (H,W,3) u8 for the other two
         pool.commit(slot, name)          # name may hold sub-directories ("sub/img_3"): the files mirror them
 
     prediction/NAME.png is mode L, or with `palette` mode P carrying the VOC palette over the same index bytes."""
 
-    def __init__(self, out_dir, outputs=KINDS[:2], palette=False, writers=4, depth=None, alloc=E._cuda_alloc, event=E._cuda_event):
+    def __init__(self, out_dir, outputs=KINDS[:2], palette=False, writers=4, depth=None, alloc=_cuda_alloc, event=_cuda_event):
+        self.out_dir = out_dir
         self.outputs = parse_outputs(outputs)
         self.palette = voc_palette() if palette else None
-        super().__init__(out_dir, writers=writers, depth=depth, save_logits=False, alloc=alloc, event=event)
-
-    def _make_dirs(self):
-        self.dirs = {k: os.path.join(self.out_dir, k) for k in self.outputs}
-        os.makedirs(self.out_dir, exist_ok=True)
+        self.dirs = {k: os.path.join(out_dir, k) for k in self.outputs}
+        os.makedirs(out_dir, exist_ok=True)
         for d in self.dirs.values():
             os.makedirs(d, exist_ok=True)
+        super().__init__(writers, depth, alloc, event)
 
     def acquire(self, H, W, block=True):
-        slot = self._next_slot(block)
-        sections, pos = {}, 0
-        for k in self.outputs:                                # every section starts at a multiple of 4 bytes
-            sections[k] = (pos, pos + _CHANNELS[k] * H * W)
-            pos = -(-sections[k][1] // 4) * 4
-        if slot.dev is None or slot.dev.numel() < pos:
-            slot.dev, slot.host = self._alloc(int(pos * 1.25))
-        slot.views = {k: slot.dev[a:b].view(*((H, W) if _CHANNELS[k] == 1 else (H, W, 3))) for k, (a, b) in sections.items()}
-        slot.layout = (H, W, sections, pos)
+        slot = self.next_slot(block)
+        used = self.carve(slot, [(k, (H, W) if _CHANNELS[k] == 1 else (H, W, 3), torch.uint8) for k in self.outputs])
+        slot.layout = (H, W, self.outputs, used)
         return slot
 
     def _write(self, slot, name):
         from PIL import Image
-        H, W, sections, _ = slot.layout
         slot.copied.synchronize()
-        host = slot.host.numpy()
-        for k, (a, b) in sections.items():
+        for k in slot.layout[2]:
             path = os.path.join(self.dirs[k], name + ".png")
             if os.path.dirname(name):
                 os.makedirs(os.path.dirname(path), exist_ok=True)
-            if _CHANNELS[k] == 3:
-                im = Image.fromarray(host[a:b].reshape(H, W, 3), mode="RGB")
-            else:
-                im = Image.fromarray(host[a:b].reshape(H, W), mode="L")
-                if k == "prediction" and self.palette is not None:
-                    im.putpalette(self.palette)               # L -> P over the same bytes
+            im = Image.fromarray(self.host(slot, k), mode="L" if _CHANNELS[k] == 1 else "RGB")
+            if k == "prediction" and self.palette is not None:
+                im.putpalette(self.palette)                   # L -> P over the same bytes
             im.save(path)
 
 
@@ -144,12 +133,11 @@ def image_records(names, sizes, stats, num_classes):
 
 def make_summary(records, args):
     """summary.json: the run's arguments, the image count and the records sorted by name; a name that occurs twice raises."""
-    from .train import strict_json
     records = sorted(records, key=lambda r: r["name"])
     for a, b in zip(records, records[1:]):
         if a["name"] == b["name"]:
             raise RuntimeError(f"predict: image {a['name']!r} was predicted twice")
-    return strict_json({"args": args, "images": len(records), "per_image": records})
+    return entry.strict_json({"args": args, "images": len(records), "per_image": records})
 
 
 def check_crf_sizes(dataset):
@@ -209,7 +197,7 @@ class Predictor:
             self.stats = grown
         slot = self.pool.acquire(H, W) if self.pool else None
         v = slot.views if slot else {}
-        image = E.image_of(x) if (self.crf is not None or "overlay" in v) else None
+        image = image_of(x) if (self.crf is not None or "overlay" in v) else None
         src, mode = msc, 0
         if self.crf is not None:
             from .utils import dcrf
@@ -228,10 +216,7 @@ class Predictor:
         self.model.eval()
         if self.crf is not None:
             check_crf_sizes(loader.dataset)
-        sharded = (getattr(loader, "world", 1), getattr(loader, "rank", 0)) == (self.world, self.rank)
-        for i, batch in enumerate(loader):
-            if not sharded and i % self.world != self.rank:
-                continue
+        for batch in msc_flip.shard_batches(loader, self.rank, self.world):
             self.add(batch[0][0], batch[1])
         return self.finish()
 
@@ -239,14 +224,9 @@ class Predictor:
         """Drain the writers, read the stats table once, collect every rank's records (each rank takes part, whatever its
         share); rank 0 writes summary.json.  -> the summary dict (on every rank)."""
         import torch.distributed as dist
-        files_error = None
-        if self.pool is not None:
-            try:
-                self.pool.finish()
-            except BaseException as e:                        # raised below: the other ranks wait in the gather
-                files_error = e
-            self.pool = None
-        n = len(self.names)
+        pool, self.pool = self.pool, None
+        files_error = pool.drain() if pool is not None else None      # raised below: the other ranks wait in the gather
+        n =len(self.names)
         records = image_records(self.names, self.sizes, self.stats[:n].cpu().numpy(), self.nc)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             parts = [None] * dist.get_world_size()
@@ -265,16 +245,8 @@ class Predictor:
 # ---------------------------------------------------------------------------------------------- the command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m weclip_vit_comer_amd.predict", description=__doc__.split("\n\n")[0])
-    p.add_argument("--config", default=None, type=str, help="the reference's YAML (default: configs/voc_attn_reg.yaml, coco_attn_reg.yaml)")
-    p.add_argument("--model_path", default=None, type=str, help="a WeCLIP_model_iter_N.pth (model.state_dict())")
-    p.add_argument("--dataset", choices=("voc", "coco", "seg"), default="voc", help="which model; seg: the supervised variant")
-    p.add_argument("--reference_root", type=str, default=None, help="reference checkout holding clip/clip_text.py and the BPE merges")
-    p.add_argument("--scales", type=E.parse_scales, default=[1.0, 0.75])
-    p.add_argument("--resize_long", default=512, type=int, help="resize the long side")
-    p.add_argument("--crf", action=argparse.BooleanOptionalAction, default=False, help="dense CRF on the multi-scale logits")
-    p.add_argument("--crf_bilateral", choices=("exact", "lattice"), default="exact")
-    p.add_argument("--threads", type=int, default=8, help="decode threads of the loader")
-    p.add_argument("--writers", type=int, default=4, help="host threads that write the PNG files")
+    entry.add_model_arguments(p)
+    entry.add_run_arguments(p)
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("--images", type=str, default=None, metavar="SOURCE", help="a directory, a glob, or a text file of paths")
     src.add_argument("--split", type=str, default=None, metavar="NAME",
@@ -290,12 +262,9 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    """The parsed arguments with msc_flip_eval's per-dataset defaults filled in."""
+    """The parsed arguments with the per-dataset defaults filled in."""
     p = build_parser()
-    args = p.parse_args(argv)
-    config, model_path = E.DEFAULTS[args.dataset]
-    args.config = args.config or config
-    args.model_path = args.model_path or model_path
+    args = entry.fill_defaults(p.parse_args(argv))
     if not 0 <= args.ignore_below <= 255:
         p.error("--ignore_below must be in 0..255")
     if not 0.0 <= args.alpha <= 1.0:
@@ -306,23 +275,22 @@ def parse_args(argv=None):
 
 
 def main(argv=None):
-    from . import train as T
     from .datasets import DeviceLoader
     args = parse_args(argv)
-    cfg = T.load_config(args.config)
-    with E.distributed_run() as (rank, world):
+    cfg = entry.load_config(args.config)
+    with entry.distributed_run() as (rank, world):
         if args.images is not None:
             from .datasets.folder import ImageFolderDataset
             dataset = ImageFolderDataset(args.images, recursive=args.recursive)
         else:
-            dataset = E.split_dataset(cfg, args, args.split, "test")
+            dataset = entry.split_dataset(cfg, args, args.split, "test")
         if args.crf:
             check_crf_sizes(dataset)
-        model = E.load_model(cfg, args)
+        model = entry.load_model(cfg, args)
         if rank == 0:
             print(cfg)
             print(args)
-        pr = Predictor(model, cfg.dataset.num_classes, scales=args.scales, resize_long=args.resize_long, crf=E.crf_of(args),
+        pr = Predictor(model, cfg.dataset.num_classes, scales=args.scales, resize_long=args.resize_long, crf=entry.crf_of(args),
                        out_dir=args.out_dir, outputs=args.outputs, alpha=args.alpha, ignore_below=args.ignore_below,
                        palette=args.palette, rank=rank, world=world, writers=args.writers)
         loader = DeviceLoader(dataset, batch_size=1, shuffle=False, rank=rank, world=world, threads=args.threads)

@@ -36,7 +36,6 @@ import argparse
 import datetime
 import json
 import logging
-import math
 import os
 import random
 import re
@@ -45,7 +44,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .entry import Config, _wrap, build_model, init_distributed, load_config, strict_json  # noqa: F401  (re-exported)
 from .train_step import OPTIMIZER_TYPES, SupervisedTrainStep, TrainStep, make_optimizer
+from .utils.writer_ring import WriterRing, _cuda_alloc, _cuda_event
 
 LOG = logging.getLogger("weclip.train")
 LOG_FORMAT = "Iter: %d; Elasped: %s; ETA: %s; LR: %.3e;, pseudo_seg_loss: %.4f, attn_loss: %.4f, pseudo_seg_mAcc: %.4f"   # :280
@@ -65,46 +66,9 @@ class _SaveAfter(dict):
 
 SAVE_AFTER = _SaveAfter(voc=26000, coco=40000)          # dist_clip_voc.py:288, dist_clip_coco.py:287
 MODEL_FILE, STATE_FILE = "WeCLIP_model_iter_%d.pth", "train_state_iter_%d.pth"
-_SCI = re.compile(r"^[+-]?(\d+\.?\d*|\.\d+)[eE][+-]?\d+$")
 
 
-# ---------------------------------------------------------------------------------------------- configuration
-class Config(dict):
-    """A dict with attribute access (`cfg.train.max_iters`), the part of OmegaConf the reference's scripts use."""
-
-    def __getattr__(self, key):
-        try:
-            return self[key]
-        except KeyError:
-            raise AttributeError(key) from None
-
-    def __setattr__(self, key, value):
-        self[key] = value
-
-
-def _wrap(v):
-    if isinstance(v, dict):
-        return Config((k, _wrap(x)) for k, x in v.items())
-    if isinstance(v, (list, tuple)):
-        return [_wrap(x) for x in v]
-    if isinstance(v, str) and _SCI.match(v.strip()):    # YAML 1.1 (PyYAML) reads `2e-4` / `1e-6` as strings: it wants a dot
-        return float(v)
-    return v
-
-
-def load_config(path, crop_size=None, work_dir=None):
-    """The reference's YAML -> Config.  Numbers spelt without a dot in the mantissa (`2e-4`) come out as floats; crop_size /
-    work_dir override `dataset.crop_size` / `work_dir.dir` as the reference's command line does (:302-306)."""
-    import yaml
-    with open(path) as f:
-        cfg = _wrap(yaml.safe_load(f))
-    if crop_size is not None:
-        cfg.dataset.crop_size = int(crop_size)
-    if work_dir is not None:
-        cfg.work_dir.dir = work_dir
-    return cfg
-
-
+# ---------------------------------------------------------------------------------------------- the command line
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m weclip_vit_comer_amd.train", description=__doc__.split("\n\n")[0])
     p.add_argument("--config", type=str, required=True, help="the reference's YAML (configs/voc_attn_reg.yaml, coco_attn_reg.yaml)")
@@ -233,18 +197,6 @@ def reg_settings(cfg, args):
     return reg
 
 
-def strict_json(v):
-    """Non-finite floats -> None, recursively: `json.dumps` would write them as the bare tokens NaN / Infinity, which strict
-    JSON readers refuse.  (A window's loss IS NaN when a batch's pseudo labels hold no foreground pixel, as in the reference.)"""
-    if isinstance(v, dict):
-        return {k: strict_json(x) for k, x in v.items()}
-    if isinstance(v, (list, tuple)):
-        return [strict_json(x) for x in v]
-    if isinstance(v, float) and not math.isfinite(v):
-        return None
-    return v
-
-
 def append_metrics(path, record):
     with open(path, "a") as f:
         f.write(json.dumps(strict_json(record), allow_nan=False) + "\n")
@@ -338,124 +290,40 @@ class LoggedSupervisedTrainStep(SupervisedTrainStep):
 
 
 # ---------------------------------------------------------------------------------------------- the panel files
-class PanelWriter:
-    """A ring of `depth` (device, pinned host) buffer pairs and `writers` host threads behind it, after msc_flip_eval.WriterPool:
+class PanelWriter(WriterRing):
+    """The panel files behind the ring of utils/writer_ring.py:
 
         slot = pw.acquire({"images": (h, w), ...})   # waits for the slot's writer; slot.views[name]: zeroed (3,h,w) uint8 canvases
         ... the panel kernels paint the canvases ...
         pw.commit(slot, n_iter)                      # ONE asynchronous copy device -> host, one event, the job is queued
 
     A writer waits for the slot's event and saves out_dir/iter_<n_iter>_<name>.png with Pillow; `on_image(name, chw, n_iter)`
-    (tensorboard's add_image, where it imports) is called with the same host array.  The buffers only grow.  The first
-    exception of a writer is kept and raised by `finish()`."""
+    (tensorboard's add_image, where it imports) is called with the same host array."""
 
-    def __init__(self, out_dir, writers=2, depth=2, on_image=None):
-        import queue
-        import threading
-        from .msc_flip_eval import _Slot, _cuda_event
+    def __init__(self, out_dir, writers=2, depth=2, on_image=None, alloc=_cuda_alloc, event=_cuda_event):
         self.out_dir, self.on_image = out_dir, on_image
         os.makedirs(out_dir, exist_ok=True)
-        self.depth = max(1, int(depth))
-        self.slots = [_Slot(_cuda_event()) for _ in range(self.depth)]
-        self._next = 0
-        self.jobs = queue.Queue(maxsize=self.depth)
-        self.error = None
-        self.written = 0
-        self._lock = threading.Lock()
-        self.threads = [threading.Thread(target=self._work, name=f"weclip-panel-{i}", daemon=True) for i in range(max(1, int(writers)))]
-        for t in self.threads:
-            t.start()
+        super().__init__(writers, depth, alloc, event, thread_name="weclip-panel")
 
     def acquire(self, shapes):
-        from .msc_flip_eval import _cuda_alloc
-        slot = self.slots[self._next]
-        slot.free.wait()
-        self._next = (self._next + 1) % self.depth
-        need = sum(3 * h * w for h, w in shapes.values())
-        if slot.dev is None or slot.dev.numel() < need:
-            slot.dev, slot.host = _cuda_alloc(need)
-        slot.dev[:need].zero_()                          # the grids' borders: the kernels write the tiles only
-        slot.views, slot.layout, off = {}, [], 0
-        for name, (h, w) in shapes.items():
-            slot.views[name] = slot.dev[off:off + 3 * h * w].view(3, h, w)
-            slot.layout.append((name, off, h, w))
-            off += 3 * h * w
+        slot = self.next_slot()
+        used = self.carve(slot, [(name, (3, h, w), torch.uint8) for name, (h, w) in shapes.items()])
+        slot.dev[:used].zero_()                          # the grids' borders: the kernels write the tiles only
+        slot.layout = [(name, slot.spans[name][0], h, w) for name, (h, w) in shapes.items()]
         return slot
-
-    def commit(self, slot, n_iter):
-        need = sum(3 * h * w for _, _, h, w in slot.layout)
-        slot.free.clear()
-        slot.host[:need].copy_(slot.dev[:need], non_blocking=True)
-        slot.copied.record()
-        self.jobs.put((slot, int(n_iter)))
 
     def _write(self, slot, n_iter):
         from PIL import Image
         slot.copied.synchronize()
-        host = slot.host.numpy()
-        for name, off, h, w in slot.layout:
-            chw = host[off:off + 3 * h * w].reshape(3, h, w)
+        for name in slot.spans:
+            chw = self.host(slot, name)
             Image.fromarray(np.ascontiguousarray(chw.transpose(1, 2, 0)), mode="RGB").save(
                 os.path.join(self.out_dir, f"iter_{n_iter}_{name}.png"))
             if self.on_image is not None:
                 self.on_image(name, chw, n_iter)
 
-    def _work(self):
-        while True:
-            job = self.jobs.get()
-            try:
-                if job is None:
-                    return
-                try:
-                    self._write(*job)
-                    with self._lock:
-                        self.written += 1
-                except BaseException as e:               # kept for finish(); the slot is freed either way
-                    with self._lock:
-                        if self.error is None:
-                            self.error = e
-                finally:
-                    job[0].free.set()
-            finally:
-                self.jobs.task_done()
-
-    def finish(self):
-        """Wait for every queued panel set, end the threads, raise the first writer exception.  -> sets written."""
-        self.jobs.join()
-        for _ in self.threads:
-            self.jobs.put(None)
-        for t in self.threads:
-            t.join()
-        self.threads = []
-        if self.error is not None:
-            raise self.error
-        return self.written
-
 
 # ---------------------------------------------------------------------------------------------- the driver
-def build_model(cfg, kind="voc", reference_root=None):
-    """The WeCLIP of `cfg.clip_init` for `kind` ("voc", "coco", or "seg": the supervised variant) with its text rows.  Shared with
-    the evaluation entry point (msc_flip_eval.py)."""
-    if reference_root:
-        from . import install_dropin
-        install_dropin(reference_root=reference_root)
-    if kind == "voc":
-        from .WeCLIP_model.model_attn_aff_voc import WeCLIP
-    elif kind == "coco":
-        from .WeCLIP_model.model_attn_aff_coco import WeCLIP
-    else:
-        from .WeCLIP_model.model_attn_aff_voc_seg import WeCLIP
-    ci = cfg.clip_init
-    text = None
-    if ci.get("text_features"):
-        rows = torch.load(ci.text_features, map_location="cuda")
-        text = (rows["bg"].float(), rows["fg"].float())
-    extra = {} if kind == "seg" else {"comer": bool(ci.get("comer", False))}
-    return WeCLIP(num_classes=cfg.dataset.num_classes, clip_model=ci.clip_pretrain_path, embedding_dim=ci.embedding_dim,
-                  in_channels=list(ci.in_channels), dataset_root_path=cfg.dataset.root_dir, device="cuda", text_features=text,
-                  **extra)
-
-
 class Trainer:
     """cfg: load_config(); args: build_parser().parse_args().  model: a ready WeCLIP instead of the one built from
     cfg.clip_init (embedding, tests).  rank_dump_dir: every rank writes `rank<r>.pth` (trainable parameters, iteration,
@@ -761,23 +629,6 @@ class Trainer:
                         "seg_hist": self.validator.seg_hist.cpu(), "cam_hist": self.validator.cam_hist.cpu()},
                        os.path.join(self.rank_dump_dir, f"rank{self.rank}.pth"))
             self.rank_dump_dir = None
-
-
-def init_distributed():
-    """Under `python -m torch.distributed.run`: RCCL, one rank per GPU; WECLIP_DIST_BACKEND=gloo is the rehearsal switch of
-    bench.py (ranks share the GPUs that exist, gradients exchanged through the host).  Starts no processes."""
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    backend = os.environ.get("WECLIP_DIST_BACKEND", "nccl")
-    if backend != "nccl":
-        local = local % max(torch.cuda.device_count(), 1)
-    torch.cuda.set_device(local)
-    if world > 1:
-        if backend == "nccl":
-            dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend=backend)
-    return world
 
 
 def main(argv=None):

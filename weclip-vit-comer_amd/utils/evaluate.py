@@ -35,11 +35,8 @@ def confusion_hist(label_true, label_pred, num_classes, out=None):
         lp = lp.long()
     if out is None:
         out = torch.zeros(num_classes, num_classes, device=lt.device, dtype=torch.int64)
-    flag = _flags.get(lt.device)
-    if flag is None:
-        flag = _flags[lt.device] = torch.zeros(1, device=lt.device, dtype=torch.int32)
     L.lib().wc_confusion_hist(L.ptr(lt, torch.int64, "label_true"), L.ptr(lp, torch.int64, "label_pred"),
-                              L.ptr(out, torch.int64, "hist"), L.ptr(flag, torch.int32, "flag"), lt.numel(),
+                              L.ptr(out, torch.int64, "hist"), L.ptr(range_flag(lt.device), torch.int32, "flag"), lt.numel(),
                               int(num_classes), L.stream())
     return out
 
@@ -47,10 +44,25 @@ def confusion_hist(label_true, label_pred, num_classes, out=None):
 _flags = {}
 
 
+def _indexed(device):
+    device = torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+
+def range_flag(device):
+    """The int32 device flag a histogram kernel raises at a predicted label outside [0, nc): one per device, created on first
+    use (outside any graph capture) and kept under the indexed device, so "cuda" means the current one."""
+    device = _indexed(device)
+    flag = _flags.get(device)
+    if flag is None:
+        flag = _flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
+    return flag
+
+
 def check_predictions_in_range(device):
-    """True unless a confusion_hist call on `device` saw a predicted label outside [0, nc) since start-up (one
+    """True unless a kernel given `range_flag(device)` saw a predicted label outside [0, nc) since start-up (one
     device->host read; call it once after the evaluation loop, not per image)."""
-    f = _flags.get(torch.device(device))
+    f = _flags.get(_indexed(device))
     return f is None or int(f.item()) == 0
 
 

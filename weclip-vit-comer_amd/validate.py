@@ -13,19 +13,7 @@ from . import msc_flip
 from .utils import evaluate
 
 F32 = torch.float32
-
-
-def _flag(device):
-    """The device flag `evaluate.check_predictions_in_range` reads (one per device, shared with `confusion_hist`).
-    COUPLING: this restates the lazy creation inside `evaluate.confusion_hist` on its module-private `_flags` dict (keyed by
-    the indexed device); a public accessor in `evaluate` should replace it when that module is next touched."""
-    device = torch.device(device)
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    flag = evaluate._flags.get(device)
-    if flag is None:
-        flag = evaluate._flags[device] = torch.zeros(1, device=device, dtype=torch.int32)
-    return flag
+_flag = evaluate.range_flag                                # the flag `evaluate.check_predictions_in_range` reads
 
 
 def val_pair_hist(seg, cam, gt, num_classes, seg_hist, cam_hist=None, flag=None):
@@ -125,11 +113,7 @@ class Validator:
         self.reset()
         self.model.eval()
         try:
-            # a loader built with this rank / world already yields the share (index_plan: order[rank::world])
-            sharded = (getattr(loader, "world", 1), getattr(loader, "rank", 0)) == (self.world, self.rank)
-            for i, (_, inputs, labels, _) in enumerate(loader):
-                if not sharded and i % self.world != self.rank:
-                    continue
+            for _, inputs, labels, _ in msc_flip.shard_batches(loader, self.rank, self.world):
                 self.add(inputs, labels, labels_from_onehot(loader.last_cls_labels)[0])
             return self.finish()
         finally:
