@@ -147,6 +147,20 @@ def test_filter_images_of_a_batch_are_isolated(hw, K):
     assert not torch.equal(batch, exact)
 
 
+@pytest.mark.parametrize("hw,K,kind", [((13, 11), 21, "noise"), ((40, 36), 33, "constant")])
+def test_filter_is_the_crf_lattice_filter(hw, K, kind):
+    """The dense CRF and the energy loss run one lattice filter: one image through bilateral_filter_batch(bilateral="lattice")
+    (no ROI, no gate) is bit-equal to utils.dcrf.lattice_filter on the same image in HWC form and the same planes.  Both build
+    with lat_point, splat and blur with the same kernels on the same operand values, and end in 1 * (acc * alpha)."""
+    from weclip_vit_comer_amd.utils import dcrf
+    H, W = hw
+    img = _images(1, H, W, kind, seed=7)[0].cuda()
+    seg = TE._probs(1, K, H, W, seed=8).cuda()
+    got = _losses().bilateral_filter_batch(img[None], seg, 15.0, 50.0, bilateral="lattice")[0]
+    crf = dcrf.lattice_filter(img.permute(1, 2, 0).contiguous(), seg[0], 50.0, 15.0)
+    assert got.abs().max().item() > 0 and torch.equal(got, crf)
+
+
 def test_colours_outside_the_range_are_clamped_and_flagged():
     """A colour above 256 is clamped for the key and OR-ed into the device flag; the other images of the batch are untouched."""
     LS = _losses()

@@ -17,14 +17,19 @@
 //                       entries on one vertex) are cut into 256-entry chunks summed by other groups into `partial` rows, which
 //                       the owner adds in chunk order.  No float atomics: two calls are bit-identical.
 //   blur              : d + 1 ping-pong passes new = old + (n1 + n2) / 2, 16-byte loads of whole rows.
-//   slice             : 32 lanes own a pixel; out = alpha sum_r b_r val[vertex_r]; the inference form fuses dcrf.hip's epilogue
-//                       (n(i) w_bil, the Gaussian message, -U, the softmax over labels, the writes of Q and of n Q).
+//   slice             : 32 lanes own a pixel; out = alpha sum_r b_r val[vertex_r] (lat_slice_gather, lattice_shared.h); the
+//                       inference form fuses dcrf.hip's epilogue (n(i) w_bil, the Gaussian message, -U, the softmax over labels,
+//                       the writes of Q and of n Q).
+// The structure, splat and blur kernels here are the only ones: csrc/energy_lattice.hip (the dense energy loss) runs them through
+// lattice_shared::structure and lattice_shared::filter_rows, defined at the end of this file.  A vertex count M >= 0 in the
+// arguments is the one the host read back (this file's entries: a structure whose count differs is left alone); M < 0 means
+// that the count stays on the device (the energy loss: grids cover the worst case 6 HW, rows past meta[0] exit).
 // The kernels of this file contain no loop without a compile-time or segment-length bound, never wait on another workgroup and
 // never retry; rocPRIM's device sort and scan are used as they ship.
 // Error model: include/weclip_hip.h (wc_dcrf_lattice_*).
 #include "common.h"
 #include "dcrf_shared.h"
-#include "lattice_shared.h"       // the layout, the per-pixel build and the chunk sum: shared with csrc/energy_lattice.hip
+#include "lattice_shared.h"       // the layout and the device code shared as text with csrc/energy_lattice.hip
 
 #include <string.h>
 
@@ -173,7 +178,7 @@ __global__ __launch_bounds__(256) void lat_splat_extra_kernel(SplatArgs A, long 
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     const long xi = g / A.q;
     const int c4 = (int)(g - xi * A.q);
-    if (A.meta[0] != A.M || xi >= cap || xi >= A.meta[2]) return;
+    if ((A.M >= 0 && A.meta[0] != A.M) || xi >= cap || xi >= A.meta[2]) return;
     const u32 start = A.xstart[xi];
     const u32 end = min(start + LAT_CHUNK, A.segstart[A.xvert[xi] + 1]);
     A.partial[xi * A.q + c4] = lat_chunk_sum(A, start, end, c4);
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(256) void lat_splat_kernel(SplatArgs A) {
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     const long v = g / A.q;
     const int c4 = (int)(g - v * A.q);
-    if (A.meta[0] != A.M || v > A.M) return;
+    if (lat_row_idle(A.meta, A.M, v)) return;
     if (v == 0) {
         A.val[c4] = make_float4(0.f, 0.f, 0.f, 0.f);
         return;
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(256) void lat_blur_kernel(const float4* __restrict_
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     const long v = g / q;
     const int c4 = (int)(g - v * q);
-    if (meta[0] != M || v > M) return;
+    if (lat_row_idle(meta, M, v)) return;
     const u32 n1 = nbr[v * LAT_NBR + 2 * j], n2 = nbr[v * LAT_NBR + 2 * j + 1];
     const float4 a = in[v * q + c4], b = in[(long)n1 * q + c4], c = in[(long)n2 * q + c4];
     out[v * q + c4] = make_float4(a.x + 0.5f * (b.x + c.x), a.y + 0.5f * (b.y + c.y), a.z + 0.5f * (b.z + c.z),
@@ -245,17 +250,8 @@ __global__ __launch_bounds__(256) void lat_slice_kernel(SliceArgs A) {
     const int i = blockIdx.x * 8 + (threadIdx.x >> 5);
     const int N = A.N, C = A.C, CP = A.CP;
     const int ic = min(i, N - 1);
-    u32 vr[LAT_D1];
-    float br[LAT_D1];
-#pragma unroll
-    for (int r = 0; r < LAT_D1; ++r) vr[r] = A.pixvert[(long)ic * LAT_D1 + r], br[r] = A.bary[(long)ic * LAT_D1 + r];
     float acc[CT];
-#pragma unroll
-    for (int k = 0; k < CT; ++k) acc[k] = 0.f;
-#pragma unroll
-    for (int r = 0; r < LAT_D1; ++r)
-#pragma unroll
-        for (int k = 0; k < CT; ++k) acc[k] = fmaf(br[r], A.val[(long)vr[r] * CP + 32 * k + l31], acc[k]);
+    lat_slice_gather<CT>(A.val, A.pixvert, A.bary, ic, CP, l31, acc);
 #pragma unroll
     for (int k = 0; k < CT; ++k) acc[k] *= LAT_ALPHA;
     if (A.mode == 0) {
@@ -369,28 +365,6 @@ int check_values(int C, int H, int W, long M, const char* who) {
     return WC_OK;
 }
 
-// vals[0] (M + 1, CP) = blurred splat of V (N, CP); vals[1] is the ping-pong partner
-int filter_rows(const Lat& L, const LatWs& w, const float* V, float* vals, long N, int CP, long M, hipStream_t st) {
-    float* va = vals;
-    float* vb = vals + (M + 1) * CP;
-    SplatArgs a;
-    a.V = (const float4*)V, a.val = (float4*)va, a.partial = (float4*)w.partial;
-    a.slots = L.slots[0], a.bary = L.bary, a.segstart = L.segstart, a.xid = L.xid, a.xstart = L.xstart, a.xvert = L.xvert;
-    a.meta = L.meta, a.q = CP / 4, a.M = (int)M;
-    const long XC = N * LAT_D1 / LAT_CHUNK + 1;
-    hipLaunchKernelGGL(lat_splat_extra_kernel, dim3(wc_cdiv(XC * a.q, 256)), dim3(256), 0, st, a, XC);
-    WC_LAUNCH_CHECK("lat_splat_extra_kernel");
-    const dim3 grid(wc_cdiv((M + 1) * a.q, 256));
-    hipLaunchKernelGGL(lat_splat_kernel, grid, dim3(256), 0, st, a);
-    WC_LAUNCH_CHECK("lat_splat_kernel");
-    for (int j = 0; j < LAT_D1; ++j) {
-        hipLaunchKernelGGL(lat_blur_kernel, grid, dim3(256), 0, st, (const float4*)((j & 1) ? vb : va), (float4*)((j & 1) ? va : vb),
-                           L.nbr, L.meta, j, a.q, (int)M);
-        WC_LAUNCH_CHECK("lat_blur_kernel");
-    }
-    return WC_OK;             // LAT_D1 is even: the result is back in vals[0]
-}
-
 int launch_slice(SliceArgs a, hipStream_t st) {
     const dim3 grid(wc_cdiv(a.N, 8)), block(256);
     switch (a.CP / 32) {
@@ -414,7 +388,7 @@ SliceArgs slice_args(const Lat& L, const float* vals, long N, int C, int CP, lon
 int bil_norm(const Lat& L, const LatWs& w, float* vals, float* S, long N, long M, hipStream_t st) {
     hipLaunchKernelGGL(lat_ones_kernel, dim3(wc_cdiv(32 * N, 256)), dim3(256), 0, st, w.Vb, 32 * N);
     WC_LAUNCH_CHECK("lat_ones_kernel");
-    if (int rc = filter_rows(L, w, w.Vb, vals, N, 32, M, st)) return rc;
+    if (int rc = lattice_shared::filter_rows(L, w.Vb, vals, w.partial, N, 32, M, st)) return rc;
     SliceArgs a = slice_args(L, vals, N, 1, 32, M);
     a.mode = 0, a.S = S ? S : w.tmp, a.nrm = w.nrm + N;
     return launch_slice(a, st);
@@ -521,6 +495,28 @@ int lattice_shared::structure(const Lat& L, int NE, hipStream_t st, const char* 
     return WC_OK;
 }
 
+int lattice_shared::filter_rows(const Lat& L, const float* V, float* vals, float* partial, long N, int CP, long M, hipStream_t st) {
+    const long rows = M >= 0 ? M : N * LAT_D1;
+    float* va = vals;
+    float* vb = vals + (rows + 1) * CP;
+    SplatArgs a;
+    a.V = (const float4*)V, a.val = (float4*)va, a.partial = (float4*)partial;
+    a.slots = L.slots[0], a.bary = L.bary, a.segstart = L.segstart, a.xid = L.xid, a.xstart = L.xstart, a.xvert = L.xvert;
+    a.meta = L.meta, a.q = CP / 4, a.M = M >= 0 ? (int)M : -1;
+    const long XC = N * LAT_D1 / LAT_CHUNK + 1;
+    hipLaunchKernelGGL(lat_splat_extra_kernel, dim3(wc_cdiv(XC * a.q, 256)), dim3(256), 0, st, a, XC);
+    WC_LAUNCH_CHECK("lat_splat_extra_kernel");
+    const dim3 grid(wc_cdiv((rows + 1) * a.q, 256));
+    hipLaunchKernelGGL(lat_splat_kernel, grid, dim3(256), 0, st, a);
+    WC_LAUNCH_CHECK("lat_splat_kernel");
+    for (int j = 0; j < LAT_D1; ++j) {
+        hipLaunchKernelGGL(lat_blur_kernel, grid, dim3(256), 0, st, (const float4*)((j & 1) ? vb : va), (float4*)((j & 1) ? va : vb),
+                           L.nbr, L.meta, j, a.q, a.M);
+        WC_LAUNCH_CHECK("lat_blur_kernel");
+    }
+    return WC_OK;             // LAT_D1 is even: the result is back in vals
+}
+
 #define LAT_OPEN(who)                                                    \
     if (int rc = check_values(C, H, W, M, who)) return rc;               \
     hipStream_t st = (hipStream_t)stream;                                \
@@ -537,7 +533,7 @@ extern "C" int wc_dcrf_lattice_filter(const void* lat, const float* in, float* o
     hipLaunchKernelGGL(lat_operand_kernel, dim3(wc_cdiv((long)C * N, 256)), dim3(256), 0, st, in, (const float*)nullptr, w.Vb, C, CP,
                        (int)N);
     WC_LAUNCH_CHECK("lat_operand_kernel");
-    if (int rc = filter_rows(L, w, w.Vb, vals, N, CP, M, st)) return rc;
+    if (int rc = lattice_shared::filter_rows(L, w.Vb, vals, w.partial, N, CP, M, st)) return rc;
     SliceArgs a = slice_args(L, vals, N, C, CP, M);
     a.mode = 1, a.out = out, a.nb = nullptr;
     return launch_slice(a, st);
@@ -554,7 +550,7 @@ extern "C" int wc_dcrf_lattice_message(const void* lat, const float* Q, float* m
     if (int rc = dcrf_shared::operands(Q, w.nrm, w.Vb, w.Vp, C, CP, (int)N, st)) return rc;
     if (int rc = dcrf_shared::gauss_message(C, H, W, pos_xy_std, w.Vp, w.tmp, w.G, st)) return rc;
     if (int rc = dcrf_shared::scale(w.G, w.nrm, msg_pos, C, (int)N, st)) return rc;
-    if (int rc = filter_rows(L, w, w.Vb, vals, N, CP, M, st)) return rc;
+    if (int rc = lattice_shared::filter_rows(L, w.Vb, vals, w.partial, N, CP, M, st)) return rc;
     SliceArgs a = slice_args(L, vals, N, C, CP, M);
     a.mode = 1, a.out = msg_bil, a.nb = w.nrm + N;
     return launch_slice(a, st);
@@ -574,7 +570,7 @@ extern "C" int wc_dcrf_lattice_inference(const void* lat, const float* unary, fl
     if (int rc = dcrf_shared::init(unary, w.nrm, Q, w.Vb, w.Vp, C, CP, (int)N, st)) return rc;
     for (int it = 0; it < iter_max; ++it) {
         if (int rc = dcrf_shared::gauss_message(C, H, W, pos_xy_std, w.Vp, w.tmp, w.G, st)) return rc;
-        if (int rc = filter_rows(L, w, w.Vb, vals, N, CP, M, st)) return rc;
+        if (int rc = lattice_shared::filter_rows(L, w.Vb, vals, w.partial, N, CP, M, st)) return rc;
         SliceArgs a = slice_args(L, vals, N, C, CP, M);
         a.mode = 2, a.nb = w.nrm + N, a.U = unary, a.G = w.G, a.npos = w.nrm, a.w_bil = bi_w, a.w_pos = pos_w;
         a.Q = Q, a.Vb_out = w.Vb, a.Vp_out = w.Vp;

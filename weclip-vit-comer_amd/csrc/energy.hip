@@ -8,29 +8,22 @@
 //                          (N, HW) = ROI - max_k P, 1 where unlabelled, 0 where negative.  P is read along the pixels (the
 //                          contiguous side of a (K, HW) plane set), turned in LDS, and the 64 x CP tile -- one contiguous
 //                          stretch of V -- is written in order: both sides of the transpose are coalesced.
-//   energy_filter_kernel : AS(n, l, i) = sum_j k_n(i, j) V(n, j, l), the hot path: dcrf_bil_kernel's structure and arithmetic
-//                          (csrc/dcrf.hip) with the image index in the grid and without normalisers.  A wave owns 32 query
-//                          pixels, a workgroup 4 waves; 64-key tiles of features and of V stream through LDS with the next
-//                          tile's loads in flight; the exponent is formed in f32 from DIFFERENCES of raw features,
-//                          log2(e) / (2 sigma^2) is folded into two coefficients so that a bare v_exp_f32 gives k, and the
-//                          f32-input MFMA (v_mfma_f32_32x32x2_f32: A = V^T, B = K) accumulates each tile in its own
-//                          accumulator, which is then added to the running total.  Epilogue: A = Gate * AS -> (N, K, H, W),
-//                          and this workgroup's partial of sum S * A (S re-read from V) -> partials[n][workgroup].
+//   energy_filter_kernel : AS(n, l, i) = sum_j k_n(i, j) V(n, j, l), the hot path: the exact all-pairs sum bil_exact_sum of
+//                          csrc/bilateral_exact.h (which csrc/dcrf.hip's dcrf_bil_kernel runs too) with the image index in the
+//                          grid and without normalisers.  Epilogue: A = Gate * AS -> (N, K, H, W), and this workgroup's
+//                          partial of sum S * A (S re-read from V) -> partials[n][workgroup].
 //   energy_finish_kernel : loss = -(1/N) sum of the partials, one workgroup, fixed order, f64 accumulation.
 //   energy_bwd_kernel    : grad_P = (-2/N) g A ROI, g read from device memory.
 // No atomics anywhere: every output is a fixed-order sum, bit-identical from run to run.
-// Error model (per element of AS, relative to sum_j k |V_j|): dcrf.hip's, for the same arithmetic: eps = 2^-10.
+// Error model (per element of AS, relative to sum_j k |V_j|): bil_exact_sum's, stated in csrc/bilateral_exact.h: eps = 2^-10.
 #include "common.h"
+#include "bilateral_exact.h"
 #include "energy_shared.h"        // what csrc/energy_lattice.hip (the opt-in lattice form of the filter) runs of this file
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define EN_MAX_K 128
 #define EN_MAX_HW (640 * 640)
 #define EN_MAX_N 65535            // the image index is a grid dimension
-#define EN_KT 64                  // keys per LDS tile
-#define EN_NT 256                 // 4 waves x 32 queries
-#define EN_QW (EN_NT / 2)         // queries per workgroup
+#define EN_QW (BIL_NT / 2)        // queries per workgroup
 #define EN_PP 64                  // pixels per prep workgroup
 
 // ------------------------------------------------------------------------------------------------ prep
@@ -92,96 +85,19 @@ struct EnergyFilterArgs {
 };
 
 template <int CT>
-__global__ __launch_bounds__(EN_NT, 2) void energy_filter_kernel(EnergyFilterArgs A) {
+__global__ __launch_bounds__(BIL_NT, 2) void energy_filter_kernel(EnergyFilterArgs A) {
     constexpr int CP = 32 * CT;
-    constexpr int VST = CP + ((CT & 1) ? 0 : 32);      // LDS row stride: the two half-waves read rows 32 banks apart
-    constexpr int NVL = EN_KT * CP / 4 / EN_NT;        // float4 of V per thread per tile
-    __shared__ __attribute__((aligned(16))) float sf[EN_KT * 8];
-    __shared__ __attribute__((aligned(16))) float sv[EN_KT * VST];
     __shared__ float red[4];
-
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l31 = lane & 31;
     const int N = A.HW, n = blockIdx.y;
-    const float* feat = A.feat + 8L * n * N;
     const float* V = A.V + (long)n * N * CP;
     const int qi = blockIdx.x * EN_QW + wave * 32 + l31;
     const int qc = qi < N ? qi : N - 1;
-    const float4 qf = *reinterpret_cast<const float4*>(feat + 8L * qc);
-    const float qb = feat[8L * qc + 4];
-    const float axy = A.a_xy, argb = A.a_rgb;
-
     f32x16 tot[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[c][r] = 0.f;
+    bil_exact_sum<CT>(A.feat + 8L * n * N, V, N, qc, A.a_xy, A.a_rgb, tot);
 
-    // register staging of the next tile (out-of-range keys: zero features and zero V rows)
-    float4 rf;
-    float4 rv[NVL];
-    auto gload = [&](int t) {
-        const int k0 = t * EN_KT;
-        if (tid < EN_KT * 2) {
-            const int key = min(k0 + (tid >> 1), N - 1);
-            rf = *reinterpret_cast<const float4*>(feat + 8L * key + 4 * (tid & 1));
-            if (k0 + (tid >> 1) >= N) rf = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int u = 0; u < NVL; ++u) {
-            const int e = tid + EN_NT * u;                  // float4 index in the 64 x CP tile
-            const int kr = e / (CP / 4);
-            const int key = min(k0 + kr, N - 1);
-            rv[u] = *reinterpret_cast<const float4*>(V + (long)key * CP + 4 * (e % (CP / 4)));
-        }
-#pragma unroll
-        for (int u = 0; u < NVL; ++u)
-            if (k0 + (tid + EN_NT * u) / (CP / 4) >= N) rv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto lstore = [&]() {
-        if (tid < EN_KT * 2) *reinterpret_cast<float4*>(sf + 4 * tid) = rf;
-#pragma unroll
-        for (int u = 0; u < NVL; ++u) {
-            const int e = tid + EN_NT * u;
-            const int kr = e / (CP / 4);
-            *reinterpret_cast<float4*>(sv + kr * VST + 4 * (e % (CP / 4))) = rv[u];
-        }
-    };
-
-    const int ntiles = (N + EN_KT - 1) / EN_KT;
-    gload(0);
-    for (int t = 0; t < ntiles; ++t) {
-        __syncthreads();                                    // previous tile consumed
-        lstore();
-        __syncthreads();
-        if (t + 1 < ntiles) gload(t + 1);                   // in flight during the tile's arithmetic
-        f32x16 acc[CT];
-#pragma unroll
-        for (int c = 0; c < CT; ++c)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-#pragma unroll 4
-        for (int s = 0; s < EN_KT / 2; ++s) {
-            const int key = 2 * s + h;
-            const float4 kf = *reinterpret_cast<const float4*>(sf + 8 * key);
-            const float kb = sf[8 * key + 4];
-            const float dx = qf.x - kf.x, dy = qf.y - kf.y;
-            const float dr = qf.z - kf.z, dg = qf.w - kf.w, db = qb - kb;
-            float pxy = dx * dx;
-            pxy = fmaf(dy, dy, pxy);
-            float prgb = dr * dr;
-            prgb = fmaf(dg, dg, prgb);
-            prgb = fmaf(db, db, prgb);
-            const float k = __builtin_amdgcn_exp2f(-fmaf(pxy, axy, prgb * argb));
-#pragma unroll
-            for (int c = 0; c < CT; ++c)
-                acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(sv[key * VST + 32 * c + l31], k, acc[c], 0, 0, 0);
-        }
-#pragma unroll
-        for (int c = 0; c < CT; ++c) tot[c] += acc[c];
-    }
-
-    // epilogue: tot[c][r] = AS(label 32c + (r & 3) + 8 (r >> 2) + 4h, query qi); a lane's labels come in runs of four
+    // epilogue: tot[c][r] = AS(label bil_label(c, r, h), query qi); a lane's labels come in runs of four
     const int K = A.K;
     const float g = A.gate ? A.gate[(long)n * N + qc] : 1.f;
     float4 sq[CT * 4];
@@ -196,7 +112,7 @@ __global__ __launch_bounds__(EN_NT, 2) void energy_filter_kernel(EnergyFilterArg
         for (int c = 0; c < CT; ++c)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int l = 32 * c + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int l = bil_label(c, r, h);
                 if (l < K) {
                     const float a = g * tot[c][r];
                     out[(long)l * N] = a;
@@ -285,7 +201,7 @@ int prep_and_filter(const EPlan& p, const EWs& w, const float* images, const flo
     WC_LAUNCH_CHECK("energy_prep_kernel");
     EnergyFilterArgs a = {};
     a.feat = w.feat, a.V = w.V, a.gate = gate, a.out = out, a.part = part, a.HW = p.HW, a.K = p.K, a.a_xy = p.a_xy, a.a_rgb = p.a_rgb;
-    const dim3 grid(p.nwg, p.N), block(EN_NT);
+    const dim3 grid(p.nwg, p.N), block(BIL_NT);
     const int idx = wc_prof_begin(st);
     switch (p.CT) {
         case 1: hipLaunchKernelGGL(energy_filter_kernel<1>, grid, block, 0, st, a); break;

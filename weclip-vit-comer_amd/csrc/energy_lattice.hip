@@ -9,10 +9,12 @@
 //   el_build_kernel  : one thread per pixel reads the three NCHW f32 planes (no HWC copy) and runs lat_point (lattice_shared.h):
 //                      fp64 keys and weights, colours outside 0..256 clamped for the key and reported by an integer OR.
 //   structure        : lattice_shared::structure, dcrf_lattice.hip's own kernels around rocPRIM's sort and scans.
-//   el_splat_*       : lat_chunk_sum over V's rows of this image, segments over 256 entries chunk by chunk, as the CRF's.
-//   el_blur_kernel   : d + 1 ping-pong passes new = old + (n1 + n2) / 2, forward order 0..d.
-//   el_slice_kernel  : 32 lanes own a pixel, a workgroup 32 pixels: AS = alpha sum_r b_r val[vertex_r]; epilogue A = Gate * AS
-//                      -> (K, HW) planes and this workgroup's partial of sum S * A (S re-read from V).
+//   filter_rows      : lattice_shared::filter_rows, dcrf_lattice.hip's splat, extra-chunk splat and blur kernels over V's rows of
+//                      this image (segments over 256 entries chunk by chunk; d + 1 ping-pong blur passes, forward order 0..d),
+//                      called with M < 0.
+//   el_slice_kernel  : 32 lanes own a pixel, a workgroup 32 pixels: AS = alpha sum_r b_r val[vertex_r] (lat_slice_gather,
+//                      lattice_shared.h); epilogue A = Gate * AS -> (K, HW) planes and this workgroup's partial of sum S * A
+//                      (S re-read from V).
 // The vertex count M never reaches the host: every kernel that needs it reads meta[0] on the device, the grids cover the proven
 // worst case M <= 6 HW (every pixel touches d + 1 = 6 vertices) and workgroups beyond M exit at the top.  No host
 // synchronisation, no allocation, every launch and every rocPRIM call on the caller's stream: an entry can be captured into a
@@ -39,55 +41,6 @@ __global__ __launch_bounds__(256) void el_build_kernel(BuildArgs A) {
     if (flag) atomicOr(A.meta + 1, flag);          // an integer OR over all images of the call
 }
 
-// ------------------------------------------------------------------------------------------------ splat, blur
-// the chunks of long segments after their first -> partial rows; grid covers the a-priori bound on X
-__global__ __launch_bounds__(256) void el_splat_extra_kernel(SplatArgs A, long cap) {
-    const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    const long xi = g / A.q;
-    const int c4 = (int)(g - xi * A.q);
-    if (xi >= cap || xi >= A.meta[2]) return;
-    const u32 start = A.xstart[xi];
-    const u32 end = min(start + LAT_CHUNK, A.segstart[A.xvert[xi] + 1]);
-    A.partial[xi * A.q + c4] = lat_chunk_sum(A, start, end, c4);
-}
-
-// val[v] = first chunk + the partial rows in chunk order; val[0] = 0; grid covers cap = 6 HW vertices, M from the device
-__global__ __launch_bounds__(256) void el_splat_kernel(SplatArgs A, long cap) {
-    const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = g / A.q;
-    const int c4 = (int)(g - v * A.q);
-    if (v > cap || v > A.meta[0]) return;
-    if (v == 0) {
-        A.val[c4] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const u32 start = A.segstart[v], endall = A.segstart[v + 1];
-    float4 acc = lat_chunk_sum(A, start, min(endall, start + LAT_CHUNK), c4);
-    const u32 len = endall - start;
-    if (len > LAT_CHUNK) {
-        const long x0 = (long)A.xid[start + LAT_CHUNK] - 1;
-        const int n = (int)((len - 1) / LAT_CHUNK);
-        for (int k = 0; k < n; ++k) {
-            const float4 p = A.partial[(x0 + k) * A.q + c4];
-            acc.x += p.x, acc.y += p.y, acc.z += p.z, acc.w += p.w;
-        }
-    }
-    A.val[v * A.q + c4] = acc;
-}
-
-__global__ __launch_bounds__(256) void el_blur_kernel(const float4* __restrict__ in, float4* __restrict__ out,
-                                                      const u32* __restrict__ nbr, const int* __restrict__ meta, int j, int q,
-                                                      long cap) {
-    const long g = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = g / q;
-    const int c4 = (int)(g - v * q);
-    if (v > cap || v > meta[0]) return;
-    const u32 n1 = nbr[v * LAT_NBR + 2 * j], n2 = nbr[v * LAT_NBR + 2 * j + 1];
-    const float4 a = in[v * q + c4], b = in[(long)n1 * q + c4], c = in[(long)n2 * q + c4];
-    out[v * q + c4] = make_float4(a.x + 0.5f * (b.x + c.x), a.y + 0.5f * (b.y + c.y), a.z + 0.5f * (b.z + c.z),
-                                  a.w + 0.5f * (b.w + c.w));
-}
-
 // ------------------------------------------------------------------------------------------------ slice
 struct ElSliceArgs {
     const float* val;         // (M + 1, CP)
@@ -111,17 +64,10 @@ __global__ __launch_bounds__(256) void el_slice_kernel(ElSliceArgs A) {
     for (int it = 0; it < EL_PIX / 8; ++it) {
         const int i = blockIdx.x * EL_PIX + it * 8 + (tid >> 5);
         const int ic = min(i, HW - 1);
-        u32 vr[LAT_D1];
-        float br[LAT_D1];
-#pragma unroll
-        for (int r = 0; r < LAT_D1; ++r) vr[r] = A.pixvert[(long)ic * LAT_D1 + r], br[r] = A.bary[(long)ic * LAT_D1 + r];
         float acc[CT], sv[CT];
 #pragma unroll
-        for (int k = 0; k < CT; ++k) acc[k] = 0.f, sv[k] = A.V[(long)ic * CP + 32 * k + l31];
-#pragma unroll
-        for (int r = 0; r < LAT_D1; ++r)
-#pragma unroll
-            for (int k = 0; k < CT; ++k) acc[k] = fmaf(br[r], A.val[(long)vr[r] * CP + 32 * k + l31], acc[k]);
+        for (int k = 0; k < CT; ++k) sv[k] = A.V[(long)ic * CP + 32 * k + l31];
+        lat_slice_gather<CT>(A.val, A.pixvert, A.bary, ic, CP, l31, acc);
         const float g = A.gate ? A.gate[ic] : 1.f;
         if (i < HW) {
 #pragma unroll
@@ -192,7 +138,7 @@ int el_run(const char* who, const float* images, const float* segs, const float*
     if (int rc = lattice_shared::check_bound(H, W, sigma_xy, sigma_rgb, b.s, who)) return rc;      // before any launch
     WC_CHECK_ARG((uintptr_t)lat % 256 == 0 && (uintptr_t)ws % 256 == 0, "%s: bad argument: lat and ws must be 256-byte aligned", who);
     const long HW = (long)H * W;
-    const int NE = (int)(HW * LAT_D1), CP = 32 * ((K + 31) / 32), q = CP / 4;
+    const int NE = (int)(HW * LAT_D1), CP = 32 * ((K + 31) / 32);
     size_t tb = 0;
     if (int rc = lattice_shared::temp_bytes(NE, &tb, who)) return rc;
     const Lat L = lat_carve(lat, HW, tb, el_meta_bytes(N));
@@ -204,33 +150,18 @@ int el_run(const char* who, const float* images, const float* segs, const float*
     if (int rc = energy_shared::prep(images, segs, rois, unlabel, w.feat, w.V, gate, N, K, H, W, st)) return rc;
     b.is_u8 = 0, b.H = H, b.W = W, b.xy_std = sigma_xy, b.rgb_std = sigma_rgb;
     b.keys = L.keys[1], b.slots = L.slots[1], b.bary = L.bary, b.meta = L.meta;
-    float* va = w.vals;
-    float* vb = w.vals + (long)(NE + 1) * CP;
-    const long XC = NE / LAT_CHUNK + 1;
-    const dim3 blk(256), gv(wc_cdiv((long)(NE + 1) * q, 256));           // worst case M = 6 HW
     for (int n = 0; n < N; ++n) {
         int idx = wc_prof_begin_always(st);
         b.img = images + (long)n * 3 * HW;
-        hipLaunchKernelGGL(el_build_kernel, dim3(wc_cdiv(HW, 256)), blk, 0, st, b);
+        hipLaunchKernelGGL(el_build_kernel, dim3(wc_cdiv(HW, 256)), dim3(256), 0, st, b);
         WC_LAUNCH_CHECK("el_build_kernel");
         if (int rc = lattice_shared::structure(L, NE, st, who)) return rc;
         wc_prof_end_n(idx, "energy_lattice_build", 0.0, st, 1);
         idx = wc_prof_begin_always(st);
-        SplatArgs a;
-        a.V = (const float4*)(w.V + (long)n * HW * CP), a.val = (float4*)va, a.partial = (float4*)w.partial;
-        a.slots = L.slots[0], a.bary = L.bary, a.segstart = L.segstart, a.xid = L.xid, a.xstart = L.xstart, a.xvert = L.xvert;
-        a.meta = L.meta, a.q = q, a.M = 0;
-        hipLaunchKernelGGL(el_splat_extra_kernel, dim3(wc_cdiv(XC * q, 256)), blk, 0, st, a, XC);
-        WC_LAUNCH_CHECK("el_splat_extra_kernel");
-        hipLaunchKernelGGL(el_splat_kernel, gv, blk, 0, st, a, (long)NE);
-        WC_LAUNCH_CHECK("el_splat_kernel");
-        for (int j = 0; j < LAT_D1; ++j) {                   // LAT_D1 is even: the result is back in va
-            hipLaunchKernelGGL(el_blur_kernel, gv, blk, 0, st, (const float4*)((j & 1) ? vb : va), (float4*)((j & 1) ? va : vb), L.nbr,
-                               L.meta, j, q, (long)NE);
-            WC_LAUNCH_CHECK("el_blur_kernel");
-        }
+        // M = -1: the vertex count stays on the device
+        if (int rc = lattice_shared::filter_rows(L, w.V + (long)n * HW * CP, w.vals, w.partial, HW, CP, -1, st)) return rc;
         ElSliceArgs s;
-        s.val = va, s.pixvert = L.pixvert, s.bary = L.bary, s.V = w.V + (long)n * HW * CP;
+        s.val = w.vals, s.pixvert = L.pixvert, s.bary = L.bary, s.V = w.V + (long)n * HW * CP;
         s.gate = gate ? gate + (long)n * HW : nullptr, s.out = out + (long)n * K * HW;
         s.part = loss ? w.part + (long)n * w.nwg : nullptr;
         s.meta = L.meta, s.n = n, s.HW = (int)HW, s.K = K, s.CP = CP;

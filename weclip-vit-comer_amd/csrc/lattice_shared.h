@@ -1,7 +1,9 @@
-// The parts of csrc/dcrf_lattice.hip that csrc/energy_lattice.hip runs unchanged: the structure's layout, the per-pixel fp64
-// build (device code, shared as text so that both files form the same keys and weights bit for bit), the in-order chunk sum of
-// the splat, and thin host wrappers over dcrf_lattice.hip's own structure kernels (defined at the end of dcrf_lattice.hip), so
-// the dense CRF and the dense energy loss share one lattice.  The algorithm is pinned to tests/dcrf_lattice_ref.py.
+// The one permutohedral lattice under the dense CRF (csrc/dcrf_lattice.hip) and the dense energy loss (csrc/energy_lattice.hip):
+// the structure's layout; device code shared as text, so that both files form the same bits: the per-pixel fp64 build
+// (lat_point), the in-order chunk sum of the splat (lat_chunk_sum) and the slice's gather (lat_slice_gather); and host entries
+// over the kernels that dcrf_lattice.hip alone holds (defined at its end): the structure behind the per-pixel build, and the
+// filter itself, filter_rows: splat, extra-chunk splat and blur.  Each file keeps its own build kernel (the image layouts differ)
+// and its own slice kernel (the epilogues differ).  The algorithm is pinned to tests/dcrf_lattice_ref.py.
 #pragma once
 #include "common.h"
 
@@ -191,8 +193,16 @@ struct SplatArgs {
     const u32* xstart;
     const u32* xvert;
     const int* meta;
-    int q, M;
+    int q, M;                 // M >= 0: the vertex count the host read back; M < 0: the count stays on the device
 };
+
+// The one guard of the splat and blur kernels, for vertex row v.  M >= 0 (the CRF's entries): the grid covers M + 1 rows and a
+// structure whose count is not the M the buffers were sized for is left alone (stale-structure check).  M < 0 (the energy
+// loss's entries): the grid covers the proven worst case 6 HW + 1 rows and the rows past the device's count exit here.
+__device__ __forceinline__ bool lat_row_idle(const int* meta, int M, long v) {
+    const int m = meta[0];
+    return (M >= 0 && m != M) || v > m;
+}
 
 // sum of entries [start, end) of the sorted list, in order, four loads in flight
 __device__ __forceinline__ float4 lat_chunk_sum(const SplatArgs& A, u32 start, u32 end, int c4) {
@@ -217,6 +227,24 @@ __device__ __forceinline__ float4 lat_chunk_sum(const SplatArgs& A, u32 start, u
     return acc;
 }
 
+// ------------------------------------------------------------------------------------------------ slice
+// acc[k] = sum_r b_r val[vertex_r][32 k + l31] of pixel ic, in the order r = 0..d (alpha is the caller's to apply); 32 lanes own
+// a pixel and a lane CT columns
+template <int CT>
+__device__ __forceinline__ void lat_slice_gather(const float* __restrict__ val, const u32* __restrict__ pixvert,
+                                                 const float* __restrict__ bary, int ic, int CP, int l31, float (&acc)[CT]) {
+    u32 vr[LAT_D1];
+    float br[LAT_D1];
+#pragma unroll
+    for (int r = 0; r < LAT_D1; ++r) vr[r] = pixvert[(long)ic * LAT_D1 + r], br[r] = bary[(long)ic * LAT_D1 + r];
+#pragma unroll
+    for (int k = 0; k < CT; ++k) acc[k] = 0.f;
+#pragma unroll
+    for (int r = 0; r < LAT_D1; ++r)
+#pragma unroll
+        for (int k = 0; k < CT; ++k) acc[k] = fmaf(br[r], val[(long)vr[r] * CP + 32 * k + l31], acc[k]);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 namespace lattice_shared {
 
@@ -227,5 +255,9 @@ int temp_bytes(long NE, size_t* bytes, const char* who);
 // Everything of the build behind the per-pixel kernel: the (key, slot) pairs of L.keys[1] / L.slots[1] -> sorted entries,
 // vertices, segments, extra chunks and blur neighbours; M -> L.meta[0], X -> L.meta[2].  No host synchronisation.
 int structure(const Lat& L, int NE, hipStream_t st, const char* who);
+// The filter up to the slice: vals[0 .. rows] (rows + 1, CP) = the blurred splat of V (N, CP), rows = M when M >= 0 (the count
+// the host read back) and the worst case 6 N when M < 0 (the count stays on the device: SplatArgs).  The ping-pong partner
+// is the (rows + 1, CP) block behind vals; partial: (6 N / 256 + 2, CP) for the extra chunks.  No host synchronisation.
+int filter_rows(const Lat& L, const float* V, float* vals, float* partial, long N, int CP, long M, hipStream_t st);
 
 }  // namespace lattice_shared
