@@ -319,6 +319,8 @@ int wc_cls_rows(float* x, const float* cls, const float* pos0, int B, int L, int
  *   cosine logits against pre-normalised text rows text[text_idx[p,t]] (t < n_text[p], row
  *   stride Tmax), softmax -> probs (P,Tmax); df (P,E) = d probs[p,cls] / d pooled feature.
  *   partial: workspace B*ceil(L/16)*E f32.  logit_scale = exp(CLIP.logit_scale).
+ *   Three launches behind the pooling, none with a workgroup per pair on the projection: y (B,Ed) = pooled feature @ proj
+ *   per (image, 64 columns), the soft-max part per pair -> dy (P,Ed), df per (pair, 64 rows).  y, dy: those workspaces.
  * wc_lnpost_bwd: dx2 (P,L,E) = gs * backward of ln_post+mean-pool (token 0 gets 0);
  *   written as f32 and as fp16 hi/lo GEMM operands.
  * wc_ln2_bwd_add: g16 = fp16((dx2 + LN2_bwd(da2; x1)) / gs): the gradient arriving at the fp16
@@ -332,7 +334,13 @@ int wc_cls_rows(float* x, const float* cls, const float* pos0, int B, int L, int
 int wc_cam_head(const float* x2, const float* lnw, const float* lnb, const float* proj,
                 const float* text, const int* text_idx, const int* n_text, const int* pair_img,
                 const int* pair_cls, float logit_scale, float* partial, float* probs, float* df,
-                int B, int P, int L, int E, int Ed, int Tmax, void* stream);
+                float* y, float* dy, int B, int P, int L, int E, int Ed, int Tmax, void* stream);
+/* wc_cam_head in its earlier form, one workgroup per pair for everything behind the pooling: bit-identical probs and df.
+ * Kept as the comparator of tests/test_cam_head_wide_gpu.py and of A/B timings; y and dy are required and left alone. */
+int wc_cam_head_single(const float* x2, const float* lnw, const float* lnb, const float* proj,
+                       const float* text, const int* text_idx, const int* n_text, const int* pair_img,
+                       const int* pair_cls, float logit_scale, float* partial, float* probs, float* df,
+                       float* y, float* dy, int B, int P, int L, int E, int Ed, int Tmax, void* stream);
 int wc_lnpost_bwd(const float* df, const float* x2, const float* lnw, float gs, const int* pair_img,
                   float* d32, void* dhi, void* dlo, int P, int L, int E, void* stream);
 int wc_ln2_bwd_add(const float* da2, const float* dx2, const float* x1, const float* lnw, float gs,
@@ -394,6 +402,10 @@ int wc_aff_tsym_apply(const float* W, const float* r, const float* c, const floa
 int wc_tsym(const float* W, const float* r, const float* c, float* T, int B, int hw, void* stream);
 int wc_box_mask(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out,
                 int* boxes, int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream);
+/* wc_box_mask in its earlier form (256 threads per pair, a box fill that walks every box per pixel): the same mask_out, V, nbox
+ * and set of boxes.  Kept as the comparator of tests/test_box_mask_wide_gpu.py and of A/B timings. */
+int wc_box_mask_single(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out,
+                       int* boxes, int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream);
 int wc_cam_upsample(const float* R, const int* nk, float* stats, float* cams, int B, int h, int w, int K,
                     int C, int H, int W, void* stream);
 

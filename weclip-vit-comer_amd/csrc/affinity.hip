@@ -409,11 +409,14 @@ __global__ __launch_bounds__(256) void tsym_kernel(const float* __restrict__ W, 
 
 // One workgroup per pair: box mask of the CAM and V[img, l, slot] = mask ? cam : 0.
 // clip/utils.py:115-142 (scoremap2bbox) + clip/clip_tool.py:179-190.
-__global__ __launch_bounds__(256) void box_mask_kernel(const float* __restrict__ cam, const int* __restrict__ pair_img,
-                                                        const int* __restrict__ pair_slot, float* __restrict__ V,
-                                                        float* __restrict__ mask_out, int* __restrict__ boxes,
-                                                        int* __restrict__ nbox, int maxbox, int h, int w, int K,
-                                                        double thr) {
+// The earlier form (wc_box_mask_single): 256 threads, 4 pixels each at 32 x 32, and a box fill in which every pixel walks every
+// box.  Kept as the comparator of tests/test_box_mask_wide_gpu.py and of A/B timings; box_mask_kernel below gives the same
+// mask, V, nbox and set of boxes.
+__global__ __launch_bounds__(256) void box_mask_single_kernel(const float* __restrict__ cam, const int* __restrict__ pair_img,
+                                                               const int* __restrict__ pair_slot, float* __restrict__ V,
+                                                               float* __restrict__ mask_out, int* __restrict__ boxes,
+                                                               int* __restrict__ nbox, int maxbox, int h, int w, int K,
+                                                               double thr) {
     extern __shared__ int smi[];   // lab[hw] | xmin[hw] | xmax[hw] | ymin[hw] | ymax[hw] | roots[hw] | misc[4]
     const int hw = h * w, p = blockIdx.x, tid = threadIdx.x;
     int* lab = smi;
@@ -512,6 +515,144 @@ __global__ __launch_bounds__(256) void box_mask_kernel(const float* __restrict__
         }
         if (mask_out) mask_out[(long)p * hw + i] = inside ? 1.f : 0.f;
         if (slot >= 0) V[((long)img * hw + i) * K + slot] = inside ? cp[i] : 0.f;      // slot -1: a padding pair (PairPlan pad)
+    }
+}
+
+// The same result with one thread per pixel (blockDim.x = h*w rounded up to a wave, at most 1024; strided beyond that) and a box
+// fill whose cost does not depend on the number of components.  LDS layout and size are the single form's.
+//   labels:  the same min-label sweeps, branch-free (clamped neighbour coordinates stay inside the 3 x 3 neighbourhood, and the
+//            background's -1 is the largest unsigned), two barriers per sweep (the changed flag alternates between two words).
+//            The sweep that changes nothing has seen, at every pixel, a label <= those of all its neighbours, so a component's
+//            labels are all equal; labels are pixel indices of the component and its smallest pixel keeps its own, so every
+//            label is that smallest index already: there is no chain left to chase.
+//   boxes:   a foreground neighbour belongs to the same component, so only a pixel with background (or the border) on a side can
+//            hold the component's extreme on that side: the four LDS atomics are issued by edge pixels only.
+//   fill:    +1 / -1 at the corners of each half-open box in an integer map (x1 <= w-1, y1 <= h-1: the corners are inside the map),
+//            a column and a row prefix pass, inside = count > 0.  Integer and exact.
+__global__ __launch_bounds__(1024) void box_mask_kernel(const float* __restrict__ cam, const int* __restrict__ pair_img,
+                                                         const int* __restrict__ pair_slot, float* __restrict__ V,
+                                                         float* __restrict__ mask_out, int* __restrict__ boxes,
+                                                         int* __restrict__ nbox, int maxbox, int h, int w, int K,
+                                                         double thr) {
+    extern __shared__ int smi[];   // lab[hw] (then cnt[hw]) | xmin[hw] | xmax[hw] | ymin[hw] | ymax[hw] | roots[hw] | misc[4]
+    const int hw = h * w, p = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+    int* lab = smi;
+    int* xmin = lab + hw;
+    int* xmax = xmin + hw;
+    int* ymin = xmax + hw;
+    int* ymax = ymin + hw;
+    int* roots = ymax + hw;
+    int* misc = roots + hw;   // [0] max u8, [1] / [3] changed flag of the even / odd sweeps, [2] root count
+    const float* cp = cam + (long)p * hw;
+    const float c0 = tid < hw ? cp[tid] : 0.f;                          // the thread's first pixel stays in a register
+    auto camv = [&](int i) { return i == tid ? c0 : cp[i]; };
+    if (tid < 4) misc[tid] = 0;
+    __syncthreads();
+    int mx = 0;
+    for (int i = tid; i < hw; i += nthr) {
+        const int u = (int)(unsigned char)(camv(i) * 255.0f);
+        mx = u > mx ? u : mx;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int v = __shfl_xor(mx, o, 64);
+        mx = v > mx ? v : mx;
+    }
+    if ((tid & 63) == 0) atomicMax(&misc[0], mx);
+    __syncthreads();
+    const int theta = (int)(thr * (double)misc[0]);
+    for (int i = tid; i < hw; i += nthr) {
+        const int u = (int)(unsigned char)(camv(i) * 255.0f);
+        lab[i] = (u > theta) ? i : -1;
+        xmin[i] = w; xmax[i] = -1; ymin[i] = h; ymax[i] = -1;
+    }
+    __syncthreads();
+    for (int it = 0; it < hw + 2; ++it) {
+        int* flag = misc + 1 + 2 * (it & 1);
+        int changed = 0;
+        for (int i = tid; i < hw; i += nthr) {
+            const int l = lab[i];
+            if (l < 0) continue;
+            const int y = i / w, x = i - y * w;
+            const int r0 = (y > 0 ? y - 1 : y) * w, r1 = y * w, r2 = (y < h - 1 ? y + 1 : y) * w;
+            const int xa = x > 0 ? x - 1 : x, xb = x < w - 1 ? x + 1 : x;
+            const unsigned n0 = lab[r0 + xa], n1 = lab[r0 + x], n2 = lab[r0 + xb], n3 = lab[r1 + xa], n4 = lab[r1 + xb],
+                           n5 = lab[r2 + xa], n6 = lab[r2 + x], n7 = lab[r2 + xb];
+            const unsigned best = min(min(min(n0, n1), min(n2, n3)), min(min(n4, n5), min(n6, n7)));
+            if (best < (unsigned)l) { lab[i] = (int)best; changed = 1; }
+        }
+        if (changed) *flag = 1;
+        if (tid == 0) misc[1 + 2 * ((it + 1) & 1)] = 0;       // the other flag: read last before the barrier that ended sweep it - 1
+        __syncthreads();
+        if (*flag == 0) break;
+        // pointer jumping: a label is also a pixel index, so lab[lab[i]] is a label of the same component that is at
+        // least as small -- the minimum then travels along whole chains per sweep (O(log diameter) sweeps instead of
+        // O(diameter)); racing reads only see other valid labels of the component, the fixed point is unchanged
+        for (int i = tid; i < hw; i += nthr) {
+            const int l = lab[i];
+            if (l >= 0) {
+                const int ll = lab[l];
+                if (ll < l) lab[i] = ll;
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = tid; i < hw; i += nthr) {
+        const int l = lab[i];
+        if (l < 0) continue;
+        const int y = i / w, x = i - y * w;
+        if (x == 0 || lab[i - 1] < 0) atomicMin(&xmin[l], x);
+        if (x == w - 1 || lab[i + 1] < 0) atomicMax(&xmax[l], x);
+        if (y == 0 || lab[i - w] < 0) atomicMin(&ymin[l], y);
+        if (y == h - 1 || lab[i + w] < 0) atomicMax(&ymax[l], y);
+        if (l == i) roots[atomicAdd(&misc[2], 1)] = i;
+    }
+    __syncthreads();
+    const int nroot = misc[2];
+    if (boxes) {   // estimated_boxes of scoremap2bbox: [x0, y0, min(x0+w, W-1), min(y0+h, H-1)]
+        if (tid == 0) nbox[p] = nroot;
+        for (int k = tid; k < nroot && k < maxbox; k += nthr) {
+            const int r = roots[k];
+            int* bx = boxes + ((long)p * maxbox + k) * 4;
+            bx[0] = xmin[r]; bx[1] = ymin[r];
+            bx[2] = (xmax[r] + 1 < w - 1) ? xmax[r] + 1 : w - 1;
+            bx[3] = (ymax[r] + 1 < h - 1) ? ymax[r] + 1 : h - 1;
+        }
+    }
+    int* cnt = lab;            // the labels are dead: cnt[y, x] = number of boxes that hold pixel (x, y)
+    for (int i = tid; i < hw; i += nthr) cnt[i] = 0;
+    __syncthreads();
+    for (int k = tid; k < nroot; k += nthr) {
+        const int r = roots[k];
+        const int x0 = xmin[r], y0 = ymin[r];
+        int x1 = xmax[r] + 1, y1 = ymax[r] + 1;
+        x1 = x1 < w - 1 ? x1 : w - 1;
+        y1 = y1 < h - 1 ? y1 : h - 1;
+        if (x1 > x0 && y1 > y0) {     // (a component in the last column or row alone has an empty box)
+            atomicAdd(&cnt[y0 * w + x0], 1);
+            atomicAdd(&cnt[y0 * w + x1], -1);
+            atomicAdd(&cnt[y1 * w + x0], -1);
+            atomicAdd(&cnt[y1 * w + x1], 1);
+        }
+    }
+    __syncthreads();
+    for (int x = tid; x < w; x += nthr) {
+        int s = 0;
+#pragma unroll 8
+        for (int y = 0; y < h; ++y) { s += cnt[y * w + x]; cnt[y * w + x] = s; }
+    }
+    __syncthreads();
+    for (int y = tid; y < h; y += nthr) {
+        int s = 0;
+#pragma unroll 8
+        for (int x = 0; x < w; ++x) { s += cnt[y * w + x]; cnt[y * w + x] = s; }
+    }
+    __syncthreads();
+    const int img = pair_img[p], slot = pair_slot[p];
+    for (int i = tid; i < hw; i += nthr) {
+        const bool inside = cnt[i] > 0;
+        if (mask_out) mask_out[(long)p * hw + i] = inside ? 1.f : 0.f;
+        if (slot >= 0) V[((long)img * hw + i) * K + slot] = inside ? camv(i) : 0.f;      // slot -1: a padding pair (PairPlan pad)
     }
 }
 
@@ -687,16 +828,33 @@ extern "C" int wc_tsym(const float* W, const float* r, const float* c, float* T,
     return WC_OK;
 }
 
-extern "C" int wc_box_mask(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out,
-                           int* boxes, int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream) {
+static int box_mask_launch(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out, int* boxes,
+                           int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream, bool wide) {
     WC_CHECK_ARG(cam && pair_img && pair_slot && V && P > 0 && h > 0 && w > 0 && K > 0, "wc_box_mask: bad argument");
     WC_CHECK_ARG(!boxes || (nbox && maxbox > 0), "wc_box_mask: boxes needs nbox and maxbox");
     const size_t sm = ((size_t)6 * h * w + 4) * sizeof(int);
     WC_CHECK_ARG(sm <= 160 * 1024, "wc_box_mask: CAM grid too large (h*w <= 6800)");
-    hipLaunchKernelGGL(box_mask_kernel, dim3(P), dim3(256), sm, (hipStream_t)stream, cam, pair_img, pair_slot, V,
-                       mask_out, boxes, nbox, maxbox, h, w, K, thr);
-    WC_LAUNCH_CHECK("box_mask_kernel");
+    if (wide) {
+        const int nthr = h * w >= 1024 ? 1024 : (h * w + 63) / 64 * 64;
+        hipLaunchKernelGGL(box_mask_kernel, dim3(P), dim3(nthr), sm, (hipStream_t)stream, cam, pair_img, pair_slot, V,
+                           mask_out, boxes, nbox, maxbox, h, w, K, thr);
+        WC_LAUNCH_CHECK("box_mask_kernel");
+    } else {
+        hipLaunchKernelGGL(box_mask_single_kernel, dim3(P), dim3(256), sm, (hipStream_t)stream, cam, pair_img, pair_slot, V,
+                           mask_out, boxes, nbox, maxbox, h, w, K, thr);
+        WC_LAUNCH_CHECK("box_mask_single_kernel");
+    }
     return WC_OK;
+}
+
+extern "C" int wc_box_mask(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out,
+                           int* boxes, int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream) {
+    return box_mask_launch(cam, pair_img, pair_slot, V, mask_out, boxes, nbox, maxbox, P, h, w, K, thr, stream, true);
+}
+
+extern "C" int wc_box_mask_single(const float* cam, const int* pair_img, const int* pair_slot, float* V, float* mask_out,
+                                  int* boxes, int* nbox, int maxbox, int P, int h, int w, int K, double thr, void* stream) {
+    return box_mask_launch(cam, pair_img, pair_slot, V, mask_out, boxes, nbox, maxbox, P, h, w, K, thr, stream, false);
 }
 
 extern "C" int wc_cam_upsample(const float* R, const int* nk, float* stats, float* cams, int B, int h, int w, int K,

@@ -74,52 +74,50 @@ __global__ __launch_bounds__(256) void lnpost_pool_kernel(const float* __restric
 
 // (b) per pair: f = mean token feature, y = f proj, probs = softmax(s * yhat . that), seed -> df
 // text rows are pre-normalised; text_idx[p, t] indexes rows of `text` (T_p = n_text[p] rows in use).
-__global__ __launch_bounds__(512) void cam_head_kernel(const float* __restrict__ partial,
-                                                        const float* __restrict__ proj,
-                                                        const float* __restrict__ text,
-                                                        const int* __restrict__ text_idx,
-                                                        const int* __restrict__ n_text,
-                                                        const int* __restrict__ pair_img,
-                                                        const int* __restrict__ pair_cls, float logit_scale,
-                                                        float* __restrict__ probs, float* __restrict__ df,
-                                                        int L, int E, int Ed, int nchunk, int Tmax) {
-    extern __shared__ float sm[];   // f[E] | y[Ed] | dy[Ed] | logit[Tmax] | red[16]
-    float* f = sm;
-    float* y = f + E;
-    float* dy = y + Ed;
-    float* lg = dy + Ed;
-    float* red = lg + Tmax;
-    const int p = blockIdx.x, img = pair_img[p], cls = pair_cls[p], T = n_text[p], tid = threadIdx.x;
-    for (int e = tid; e < E; e += 512) {
-        const float* pp = partial + (long)img * nchunk * E + e;
-        float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // 8 independent loads in flight
+// The four parts are device functions shared by two forms that give bit-identical probs and df (every output element keeps its
+// accumulation order):
+//   wide   (wc_cam_head):        cam_head_y_kernel (image, 64 columns of Ed) -> cam_head_pair_kernel (pair) ->
+//                                cam_head_df_kernel (pair, 64 rows of E): no workgroup reads more than ~0.4 MB
+//   single (wc_cam_head_single): cam_head_kernel, one workgroup per pair does all four (3.1 MB of proj through one CU); the
+//                                comparator of tests/test_cam_head_wide_gpu.py and of the A/B
+// f[e] = mean over patch tokens of ln_post(x2[img]) from the pooled partials (all threads of the workgroup).  A thread carries
+// NQ elements e at a time (8 NQ independent loads in flight; elements past E read element E - 1 and are dropped): the 256-thread
+// wide stage would otherwise walk the chunks three times in a row at E = 768
+template <int NQ>
+__device__ __forceinline__ void cam_head_pool(const float* __restrict__ partial, float* f, int img, int L, int E, int nchunk) {
+    const int nthr = blockDim.x;
+    for (int e0 = threadIdx.x; e0 < E; e0 += NQ * nthr) {
+        const float* pp[NQ];
+        float s[NQ][8];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const int e = e0 + q * nthr;
+            pp[q] = partial + (long)img * nchunk * E + (e < E ? e : E - 1);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s[q][u] = 0.f;
+        }
         int c = 0;
         for (; c + 8 <= nchunk; c += 8)
 #pragma unroll
-            for (int u = 0; u < 8; ++u) s[u] += pp[(long)(c + u) * E];
-        for (; c < nchunk; ++c) s[0] += pp[(long)c * E];
-        f[e] = (((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]))) / (L - 1);
-    }
-    __syncthreads();
-    for (int t = tid; t < Ed; t += 512) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int e = 0;
-        for (; e + 16 <= E; e += 16) {           // 16 coalesced row loads in flight per thread
-            float pv[16];
+            for (int q = 0; q < NQ; ++q)
 #pragma unroll
-            for (int u = 0; u < 16; ++u) pv[u] = proj[(long)(e + u) * Ed + t];
+                for (int u = 0; u < 8; ++u) s[q][u] += pp[q][(long)(c + u) * E];
+        for (; c < nchunk; ++c)
 #pragma unroll
-            for (int u = 0; u < 16; u += 4) {
-                s0 = fmaf(f[e + u], pv[u], s0);
-                s1 = fmaf(f[e + u + 1], pv[u + 1], s1);
-                s2 = fmaf(f[e + u + 2], pv[u + 2], s2);
-                s3 = fmaf(f[e + u + 3], pv[u + 3], s3);
-            }
-        }
-        for (; e < E; ++e) s0 = fmaf(f[e], proj[(long)e * Ed + t], s0);
-        y[t] = (s0 + s1) + (s2 + s3);
+            for (int q = 0; q < NQ; ++q) s[q][0] += pp[q][(long)c * E];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            if (e0 + q * nthr < E)
+                f[e0 + q * nthr] = (((s[q][0] + s[q][1]) + (s[q][2] + s[q][3])) + ((s[q][4] + s[q][5]) + (s[q][6] + s[q][7]))) / (L - 1);
     }
-    __syncthreads();
+}
+
+// y (LDS, Ed values, visible to the 512 threads) -> yhat in y, d probs[p, cls] / d y in dy (both LDS), probs[p, :] written.
+// Ends with a barrier.
+__device__ __forceinline__ void cam_head_pair_part(float* y, float* dy, float* lg, float* red, const float* __restrict__ text,
+                                                   const int* __restrict__ text_idx, int p, int T, int cls, float logit_scale,
+                                                   float* __restrict__ probs, int Ed, int Tmax) {
+    const int tid = threadIdx.x;
     float q = 0.f;
     for (int t = tid; t < Ed; t += 512) q += y[t] * y[t];
     const float ynorm = sqrtf(block_sum(q, red));
@@ -148,11 +146,24 @@ __global__ __launch_bounds__(512) void cam_head_kernel(const float* __restrict__
     __syncthreads();
     const float pj = lg[cls];
     // dyhat = s * sum_t dlogit_t that_t,  dlogit_t = pj (delta_jt - p_t)
+    // (eight text rows in flight per thread: one row index and one row element per step of t were two dependent loads each)
     for (int k = tid; k < Ed; k += 512) {
         float s = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const float dl = pj * ((t == cls ? 1.f : 0.f) - lg[t]);
-            s = fmaf(dl, text[(long)text_idx[(long)p * Tmax + t] * Ed + k], s);
+        for (int t0 = 0; t0 < T; t0 += 8) {
+            float tv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int t = t0 + u < T ? t0 + u : T - 1;
+                tv[u] = text[(long)text_idx[(long)p * Tmax + t] * Ed + k];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int t = t0 + u;
+                if (t < T) {
+                    const float dl = pj * ((t == cls ? 1.f : 0.f) - lg[t]);
+                    s = fmaf(dl, tv[u], s);
+                }
+            }
         }
         dy[k] = logit_scale * s;
     }
@@ -163,14 +174,20 @@ __global__ __launch_bounds__(512) void cam_head_kernel(const float* __restrict__
     __syncthreads();
     for (int k = tid; k < Ed; k += 512) dy[k] = (dy[k] - y[k] * dot) / ynorm;   // d/dy of y/|y|
     __syncthreads();
-    // df = proj dy: 8 rows of proj per wave at a time, 8 lanes per row reading 16-B pieces (coalesced 128 B per
-    // row and step, all loads of a row independent), 3-step shuffle reduction over the 8 lanes
+}
+
+// dfp[e] = proj[e, :] . dy (LDS) for the rows ebeg <= e < eend (ebeg a multiple of 64), 512 threads.
+// 8 rows of proj per wave at a time, 8 lanes per row reading 16-B pieces (coalesced 128 B per row and step, all loads of a
+// row independent), 3-step shuffle reduction over the 8 lanes
+__device__ __forceinline__ void cam_head_df_rows(const float* __restrict__ proj, const float* dy, float* __restrict__ dfp, int Ed,
+                                                 int ebeg, int eend) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if ((Ed & 3) == 0) {
         const int rsub = lane >> 3, j = lane & 7;
-        for (int e0 = wv * 8; e0 < E; e0 += 64) {
+        for (int e0 = ebeg + wv * 8; e0 < eend; e0 += 64) {
             const int e = e0 + rsub;
             float s = 0.f;
-            if (e < E) {
+            if (e < eend) {
                 const float* pr = proj + (long)e * Ed;
 #pragma unroll 4
                 for (int k = 4 * j; k < Ed; k += 32) {
@@ -184,16 +201,116 @@ __global__ __launch_bounds__(512) void cam_head_kernel(const float* __restrict__
             s += __shfl_xor(s, 1, 64);
             s += __shfl_xor(s, 2, 64);
             s += __shfl_xor(s, 4, 64);
-            if (j == 0 && e < E) df[(long)p * E + e] = s;
+            if (j == 0 && e < eend) dfp[e] = s;
         }
     } else {
-        for (int e = tid; e < E; e += 512) {
+        for (int e = ebeg + tid; e < eend; e += 512) {
             const float* pr = proj + (long)e * Ed;
             float s = 0.f;
             for (int k = 0; k < Ed; ++k) s = fmaf(pr[k], dy[k], s);
-            df[(long)p * E + e] = s;
+            dfp[e] = s;
         }
     }
+}
+
+__global__ __launch_bounds__(512) void cam_head_kernel(const float* __restrict__ partial,
+                                                        const float* __restrict__ proj,
+                                                        const float* __restrict__ text,
+                                                        const int* __restrict__ text_idx,
+                                                        const int* __restrict__ n_text,
+                                                        const int* __restrict__ pair_img,
+                                                        const int* __restrict__ pair_cls, float logit_scale,
+                                                        float* __restrict__ probs, float* __restrict__ df,
+                                                        int L, int E, int Ed, int nchunk, int Tmax) {
+    extern __shared__ float sm[];   // f[E] | y[Ed] | dy[Ed] | logit[Tmax] | red[16]
+    float* f = sm;
+    float* y = f + E;
+    float* dy = y + Ed;
+    float* lg = dy + Ed;
+    float* red = lg + Tmax;
+    const int p = blockIdx.x, img = pair_img[p], cls = pair_cls[p], T = n_text[p], tid = threadIdx.x;
+    cam_head_pool<1>(partial, f, img, L, E, nchunk);
+    __syncthreads();
+    for (int t = tid; t < Ed; t += 512) {
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        int e = 0;
+        for (; e + 16 <= E; e += 16) {           // 16 coalesced row loads in flight per thread
+            float pv[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) pv[u] = proj[(long)(e + u) * Ed + t];
+#pragma unroll
+            for (int u = 0; u < 16; u += 4) {
+                s0 = fmaf(f[e + u], pv[u], s0);
+                s1 = fmaf(f[e + u + 1], pv[u + 1], s1);
+                s2 = fmaf(f[e + u + 2], pv[u + 2], s2);
+                s3 = fmaf(f[e + u + 3], pv[u + 3], s3);
+            }
+        }
+        for (; e < E; ++e) s0 = fmaf(f[e], proj[(long)e * Ed + t], s0);
+        y[t] = (s0 + s1) + (s2 + s3);
+    }
+    __syncthreads();
+    cam_head_pair_part(y, dy, lg, red, text, text_idx, p, T, cls, logit_scale, probs, Ed, Tmax);
+    cam_head_df_rows(proj, dy, df + (long)p * E, Ed, 0, E);
+}
+
+// wide stage A: y[img, t] = f . proj[:, t] for the 64 columns t of blockIdx.x.  Wave j carries the chain s_j of cam_head_kernel
+// (rows e = j mod 4 of the 16-row groups, in order; wave 0 appends the E % 16 remainder to s0 as the single form does), so the
+// four chains of a column run side by side instead of in one thread: 32 row loads (256 B each per wave) in flight per thread
+__global__ __launch_bounds__(256) void cam_head_y_kernel(const float* __restrict__ partial, const float* __restrict__ proj,
+                                                          float* __restrict__ yg, int L, int E, int Ed, int nchunk) {
+    extern __shared__ float sm[];   // f[E] | s[4][64]
+    float* f = sm;
+    float* sp = f + E;
+    const int img = blockIdx.y, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+    cam_head_pool<4>(partial, f, img, L, E, nchunk);
+    __syncthreads();
+    const int t = blockIdx.x * 64 + lane;
+    const float* pc = proj + (t < Ed ? t : Ed - 1);          // columns past Ed read column Ed - 1 and are dropped
+    const int E16 = E & ~15;
+    float s = 0.f;
+    int e = j;
+    for (; e + 124 < E16; e += 128) {
+        float pv[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) pv[u] = pc[(long)(e + 4 * u) * Ed];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) s = fmaf(f[e + 4 * u], pv[u], s);
+    }
+    for (; e < E16; e += 4) s = fmaf(f[e], pc[(long)e * Ed], s);
+    if (j == 0)
+        for (e = E16; e < E; ++e) s = fmaf(f[e], pc[(long)e * Ed], s);
+    sp[j * 64 + lane] = s;
+    __syncthreads();
+    if (j == 0 && t < Ed) yg[(long)img * Ed + t] = (sp[lane] + sp[64 + lane]) + (sp[128 + lane] + sp[192 + lane]);
+}
+
+// wide stage B: one workgroup per pair, y of its image -> probs[p, :] and dy[p, :]
+__global__ __launch_bounds__(512) void cam_head_pair_kernel(const float* __restrict__ yg, const float* __restrict__ text,
+                                                             const int* __restrict__ text_idx, const int* __restrict__ n_text,
+                                                             const int* __restrict__ pair_img, const int* __restrict__ pair_cls,
+                                                             float logit_scale, float* __restrict__ probs,
+                                                             float* __restrict__ dyg, int Ed, int Tmax) {
+    extern __shared__ float sm[];   // y[Ed] | dy[Ed] | logit[Tmax] | red[16]
+    float* y = sm;
+    float* dy = y + Ed;
+    float* lg = dy + Ed;
+    float* red = lg + Tmax;
+    const int p = blockIdx.x, img = pair_img[p], tid = threadIdx.x;
+    for (int t = tid; t < Ed; t += 512) y[t] = yg[(long)img * Ed + t];
+    __syncthreads();
+    cam_head_pair_part(y, dy, lg, red, text, text_idx, p, n_text[p], pair_cls[p], logit_scale, probs, Ed, Tmax);
+    for (int k = tid; k < Ed; k += 512) dyg[(long)p * Ed + k] = dy[k];
+}
+
+// wide stage C: df[p, e] = proj[e, :] . dy[p] for the 64 rows e of blockIdx.x
+__global__ __launch_bounds__(512) void cam_head_df_kernel(const float* __restrict__ proj, const float* __restrict__ dyg,
+                                                           float* __restrict__ df, int E, int Ed) {
+    extern __shared__ float sm[];   // dy[Ed]
+    const int p = blockIdx.y, ebeg = blockIdx.x * 64;
+    for (int k = threadIdx.x; k < Ed; k += 512) sm[k] = dyg[(long)p * Ed + k];
+    __syncthreads();
+    cam_head_df_rows(proj, sm, df + (long)p * E, Ed, ebeg, ebeg + 64 < E ? ebeg + 64 : E);
 }
 
 // (c) dx2[p,l,:] = gs * LNpost_bwd(df[p]/(L-1); x2[img,l,:]) for l >= 1, 0 for l = 0.
@@ -694,17 +811,19 @@ __global__ __launch_bounds__(1024) void cam_norm_kernel(float* __restrict__ cam,
 }
 
 // ---------------------------------------------------------------------------------------------
-extern "C" int wc_cam_head(const float* x2, const float* lnw, const float* lnb, const float* proj,
-                           const float* text, const int* text_idx, const int* n_text, const int* pair_img,
-                           const int* pair_cls, float logit_scale, float* partial, float* probs, float* df,
-                           int B, int P, int L, int E, int Ed, int Tmax, void* stream) {
+// y: workspace B*Ed f32, dy: workspace P*Ed f32 (the wide form's stage outputs; the single form leaves them alone)
+static int cam_head_launch(const float* x2, const float* lnw, const float* lnb, const float* proj, const float* text,
+                           const int* text_idx, const int* n_text, const int* pair_img, const int* pair_cls,
+                           float logit_scale, float* partial, float* probs, float* df, float* y, float* dy, int B, int P,
+                           int L, int E, int Ed, int Tmax, void* stream, bool wide) {
     WC_CHECK_ARG(x2 && lnw && lnb && proj && text && text_idx && n_text && pair_img && pair_cls && partial &&
-                     probs && df && B > 0 && P > 0 && L > 1 && E > 0 && Ed > 0,
+                     probs && df && y && dy && B > 0 && P > 0 && L > 1 && E > 0 && Ed > 0,
                  "wc_cam_head: bad argument");
     WC_CHECK_ARG(Tmax > 0 && Tmax <= 512 && E <= 4096 && Ed <= 4096, "wc_cam_head: Tmax <= 512, E, Ed <= 4096");
     hipStream_t st = (hipStream_t)stream;
     const int nchunk = wc_cdiv(L, LNP_ROWS);
     WC_CHECK_ARG(E <= 1024, "wc_cam_head: E <= 1024");
+    WC_CHECK_ARG(B <= 65535 && P <= 65535, "wc_cam_head: too many images/pairs for one launch");
     if (E <= 256)
         hipLaunchKernelGGL(lnpost_pool_kernel<4>, dim3(nchunk, B), dim3(256), 4 * E * sizeof(float), st, x2, lnw, lnb,
                            1e-5f, partial, L, E, nchunk);
@@ -712,11 +831,38 @@ extern "C" int wc_cam_head(const float* x2, const float* lnw, const float* lnb, 
         hipLaunchKernelGGL(lnpost_pool_kernel<16>, dim3(nchunk, B), dim3(256), 4 * E * sizeof(float), st, x2, lnw, lnb,
                            1e-5f, partial, L, E, nchunk);
     WC_LAUNCH_CHECK("lnpost_pool_kernel");
-    const size_t sm = (E + 2 * Ed + Tmax + 16) * sizeof(float);
-    hipLaunchKernelGGL(cam_head_kernel, dim3(P), dim3(512), sm, st, partial, proj, text, text_idx, n_text,
-                       pair_img, pair_cls, logit_scale, probs, df, L, E, Ed, nchunk, Tmax);
-    WC_LAUNCH_CHECK("cam_head_kernel");
+    if (!wide) {
+        const size_t sm = (E + 2 * Ed + Tmax + 16) * sizeof(float);
+        hipLaunchKernelGGL(cam_head_kernel, dim3(P), dim3(512), sm, st, partial, proj, text, text_idx, n_text,
+                           pair_img, pair_cls, logit_scale, probs, df, L, E, Ed, nchunk, Tmax);
+        WC_LAUNCH_CHECK("cam_head_kernel");
+        return WC_OK;
+    }
+    hipLaunchKernelGGL(cam_head_y_kernel, dim3(wc_cdiv(Ed, 64), B), dim3(256), (E + 256) * sizeof(float), st, partial, proj, y,
+                       L, E, Ed, nchunk);
+    WC_LAUNCH_CHECK("cam_head_y_kernel");
+    hipLaunchKernelGGL(cam_head_pair_kernel, dim3(P), dim3(512), (2 * Ed + Tmax + 16) * sizeof(float), st, y, text, text_idx,
+                       n_text, pair_img, pair_cls, logit_scale, probs, dy, Ed, Tmax);
+    WC_LAUNCH_CHECK("cam_head_pair_kernel");
+    hipLaunchKernelGGL(cam_head_df_kernel, dim3(wc_cdiv(E, 64), P), dim3(512), Ed * sizeof(float), st, proj, dy, df, E, Ed);
+    WC_LAUNCH_CHECK("cam_head_df_kernel");
     return WC_OK;
+}
+
+extern "C" int wc_cam_head(const float* x2, const float* lnw, const float* lnb, const float* proj,
+                           const float* text, const int* text_idx, const int* n_text, const int* pair_img,
+                           const int* pair_cls, float logit_scale, float* partial, float* probs, float* df,
+                           float* y, float* dy, int B, int P, int L, int E, int Ed, int Tmax, void* stream) {
+    return cam_head_launch(x2, lnw, lnb, proj, text, text_idx, n_text, pair_img, pair_cls, logit_scale, partial, probs, df,
+                           y, dy, B, P, L, E, Ed, Tmax, stream, true);
+}
+
+extern "C" int wc_cam_head_single(const float* x2, const float* lnw, const float* lnb, const float* proj,
+                                  const float* text, const int* text_idx, const int* n_text, const int* pair_img,
+                                  const int* pair_cls, float logit_scale, float* partial, float* probs, float* df,
+                                  float* y, float* dy, int B, int P, int L, int E, int Ed, int Tmax, void* stream) {
+    return cam_head_launch(x2, lnw, lnb, proj, text, text_idx, n_text, pair_img, pair_cls, logit_scale, partial, probs, df,
+                           y, dy, B, P, L, E, Ed, Tmax, stream, false);
 }
 
 extern "C" int wc_lnpost_bwd(const float* df, const float* x2, const float* lnw, float gs,

@@ -60,13 +60,15 @@ class LastLayerState:
         partial = torch.empty(B * nchunk * E, device=dev, dtype=F32)
         probs = torch.zeros(P, Tmax, device=dev, dtype=F32)
         df = torch.empty(P, E, device=dev, dtype=F32)
+        y = torch.empty(B, Ed, device=dev, dtype=F32)        # stage outputs of the three launches
+        dy = torch.empty(P, Ed, device=dev, dtype=F32)
         L.lib().wc_cam_head(L.ptr(self.x2, F32), L.ptr(v.ln_post.weight.detach().float(), F32),
                             L.ptr(v.ln_post.bias.detach().float(), F32),
                             L.ptr(v.proj.detach().float().contiguous(), F32), L.ptr(text_hat, F32),
                             L.ptr(text_idx, torch.int32), L.ptr(n_text, torch.int32),
                             L.ptr(pair_img, torch.int32), L.ptr(pair_cls, torch.int32),
                             _logit_scale(self.m), L.ptr(partial), L.ptr(probs),
-                            L.ptr(df), B, P, Lq, E, Ed, Tmax, L.stream())
+                            L.ptr(df), L.ptr(y), L.ptr(dy), B, P, Lq, E, Ed, Tmax, L.stream())
         return probs, df
 
     def class_probs(self, text):
