@@ -10,7 +10,8 @@
  *     launched; WC_ERR_HIP 2: HIP runtime error); wc_last_error() gives the message
  *     (thread-local).  The Python host raises RuntimeError, like the stock torch ops the
  *     reference calls do.
- *   - no global state except thread-local error text; re-entrant per device.
+ *   - no global state except thread-local error text and the kernel form set by wc_par_sweep_form (results do not depend
+ *     on it); re-entrant per device.
  *
  * Each entry cites the reference interface it replaces (paths relative to the reference
  * repository dayae1204/WeCLIP-ViT-CoMer).
@@ -61,6 +62,12 @@ int wc_par_forward(const float* img, const float* masks, float* out, float* tmp,
 int wc_par_forward_h(const float* img, const float* masks, float* out, float* tmp, float* aff_ws,
                    int B, int C, int H, int W, const int* h_dilations, int n_dil, int num_iter,
                    int group, void* stream);
+/* Kernel form of the sweeps of wc_par_forward_h (process-wide; both forms give bit-identical masks): 0 = the 64 x 8 tile with
+ * a 12-pixel halo and gathered far taps (the comparator of tests/test_par_strip_gpu.py and of A/B timings), 1 = the strip walk
+ * with a rolling 24-pixel-halo window in LDS, -1 = the default: WECLIP_PAR_SWEEP from the environment, else form 1, for
+ * launches of at least one 64-row segment of a 64-pixel strip per CU, and form 0 below that.  Dilations above 24 always run
+ * form 0.  seg_rows: rows of a strip per workgroup, 0 = planned from the CU count. */
+int wc_par_sweep_form(int form, int seg_rows);
 /* WeCLIP_model/model_attn_aff_voc.py:49-57 (`_refine_cams` tail): labels = valid_key[argmax_c].
  * valid_key (B,C) i64, nch (B) i32 channels in use per image (NULL = C), labels (B,H,W) i64. */
 int wc_par_labels(const float* masks, const int64_t* valid_key, const int* nch, int64_t* labels,

@@ -66,7 +66,9 @@ class PAR(nn.Module):
         h16 = T == 48 and not config.exact() and config.par_q16
         # group so that aff + masks of a group stay (mostly) inside the 256 MiB Infinity Cache across the sweeps: measured
         # at 512x512, C = 3, 16 images (fast form, 35.7 MB per image): groups of 6 / 7 / 8 / 9 / 16 -> 2.27 / 2.28 / 2.24 /
-        # 2.39 / 2.71 ms; the groups are balanced (16 images = 8 + 8, not 6 + 6 + 4)
+        # 2.39 / 2.71 ms with the tile sweep; 6 / 7 / 8 -> 2.163 / 2.139 / 2.057 ms with the strip walk (tile sweep in the same
+        # process: 2.234 / 2.233 / 2.184), which also gets one workgroup per CU from 8 images; the groups are balanced
+        # (16 images = 8 + 8, not 6 + 6 + 4)
         per_img = ((T // 2 + 1 if h16 else T) + 3 * C) * h * w * 4
         gmax = max(1, min(b, (288 << 20) // max(per_img, 1)))
         n_groups = -(-b // gmax)

@@ -331,6 +331,154 @@ __global__ __launch_bounds__(64 * ROWS) void par_iter_kernel(const float* __rest
     }
 }
 
+// The H16 sweep as a strip walk.  A workgroup (8 waves) owns S rows of one 64-pixel strip of one image and walks down them
+// R = 8 rows a step: one wave per row, one pixel per thread.  The mask rows in work plus PAR_STRIP_HALO rows above and below,
+// 64 + 2 * PAR_STRIP_HALO columns, all CG channels, live in an LDS ring of RING = 2 R + 2 * PAR_STRIP_HALO = 64 rows holding
+// replicate-padded values: ring row u % RING holds the image row clamp(y0 - PAR_STRIP_HALO + u).  A step loads only the R rows
+// below its window (into the slots of the R rows above it, which no tap of this step reads), so every mask value is fetched
+// (S + 48) / S * 112 / 64 times per sweep instead of 5.5 + 8 (tile fill + far taps of par_iter_kernel<CG, true, true, 8, 12>),
+// and all 48 taps are LDS reads.  One barrier a step.  Only one workgroup fits a CU, so a thread keeps the 25 affinity dwords
+// of its next pixel in flight while it computes.  A wave is one row, so ring rows and tap offsets are scalar arithmetic.
+// Arithmetic per pixel: the FMA chain of par_iter_kernel in tap order on the same dword halves, then * scale (bit-identical).
+#define PAR_STRIP_HALO 24
+#define PAR_STRIP_ROWS 8
+template <int CG>
+__global__ __launch_bounds__(64 * PAR_STRIP_ROWS) void par_strip_kernel(const float* __restrict__ aff, const float* __restrict__ min,
+                                                                        float* __restrict__ mout, int C, int H, int W, int S,
+                                                                        ParTaps taps) {
+    constexpr int HL = PAR_STRIP_HALO, R = PAR_STRIP_ROWS, TW = 64 + 2 * HL, RING = 2 * R + 2 * HL, T = 48, Q = PAR_Q_SLOTS(T);
+    constexpr int FILL = (R + 2 * HL) / R;           // rows per wave of the first window
+    static_assert((R + 2 * HL) % R == 0, "whole rows per wave");
+    extern __shared__ float ring[];                  // [CG][RING][TW]
+    const int lx = threadIdx.x & 63;
+    const int ly = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int y0 = blockIdx.y * S;
+    const int rows = H - y0 < S ? H - y0 : S;
+    const int nsteps = (rows + R - 1) / R;
+    const int xg = blockIdx.x * 64 + lx;
+    const int xc = xg < W ? xg : W - 1;              // out-of-image threads compute on a clamped pixel and do not store
+    const long HW = (long)H * W;
+    // every address is a wave-uniform pointer (a wave is one row of one strip) + a 32-bit lane offset: the scalar-base addressing
+    // form, one address register per stream instead of a 64-bit pair per load
+    const unsigned* AQ = reinterpret_cast<const unsigned*>(aff) + ((long)blockIdx.z * H * ((W + 63) >> 6) + blockIdx.x) * (long)Q * 64;
+    const unsigned la = (unsigned)(xc & 63) * 4u, lo = (unsigned)xg * 4u;
+    const long arow = (long)((W + 63) >> 6) * Q * 64;      // dwords between two rows of one strip
+    const float* M = min + (long)blockIdx.z * C * HW;
+    float* O = mout + (long)blockIdx.z * C * HW;
+    // the two ring columns this thread fills (lx, lx + 64) as clamped image columns (lanes 48..63 load a second value too, a
+    // valid address, and do not write it: no branch around the loads)
+    const unsigned c0 = (unsigned)clampi(blockIdx.x * 64 + lx - HL, W - 1) * 4u, c1 = (unsigned)clampi(blockIdx.x * 64 + lx + 64 - HL, W - 1) * 4u;
+    const bool two = lx + 64 < TW;
+    // dwords j0 .. j0 + n - 1 of the affinity record of the thread's pixel of step s
+    auto load_aff = [&](unsigned (&a)[Q], int s, int j0, int n) {
+        const int y = y0 + s * R + ly;
+        const unsigned* A2 = AQ + (y < H ? y : H - 1) * arow;
+#pragma unroll
+        for (int j = j0; j < j0 + n; ++j) a[j] = *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(A2 + j * 64) + la);
+    };
+    for (int cb = 0; cb < C; cb += CG) {
+        const float* Mc[CG];
+#pragma unroll
+        for (int k = 0; k < CG; ++k) Mc[k] = M + (long)(cb + k < C ? cb + k : C - 1) * HW;
+        unsigned cur[Q];
+        load_aff(cur, 0, 0, Q);                      // in flight beside the window fill
+        if (cb) __syncthreads();                     // the previous channel group is done with the ring
+        {
+            float v[FILL][2][CG];
+#pragma unroll
+            for (int j = 0; j < FILL; ++j) {
+                const long ro = (long)clampi(y0 - HL + ly + R * j, H - 1) * W;
+#pragma unroll
+                for (int k = 0; k < CG; ++k) {
+                    v[j][0][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Mc[k] + ro) + c0);
+                    v[j][1][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Mc[k] + ro) + c1);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < FILL; ++j)
+#pragma unroll
+                for (int k = 0; k < CG; ++k) {
+                    ring[(k * RING + ly + R * j) * TW + lx] = v[j][0][k];
+                    if (two) ring[(k * RING + ly + R * j) * TW + lx + 64] = v[j][1][k];
+                }
+        }
+        __syncthreads();
+        int rb = 0;                                  // (s * R) % RING: ring row of the top of the step's window
+        // the thread's pixel of step s from the ring and the affinities in a.  more: the four dwords of a dilation are requested
+        // again for step s + 1 as soon as its eight taps are done -- the next step's affinities are in flight during this one
+        // without a second set of 25 registers
+        auto sweep = [&](unsigned (&a)[Q], int s, bool more) {
+            const int y = y0 + s * R + ly;
+            const int ur = rb + ly + HL;                 // the pixel's own ring row, before the wrap
+            float acc[CG];
+#pragma unroll
+            for (int k = 0; k < CG; ++k) acc[k] = 0.f;
+#pragma unroll
+            for (int t = 0; t < T; t += 8) {
+                float m[8][CG];
+                // the 8 neighbours of one dilation d (build_taps order) from three ring rows and three columns, all
+                // scalar: ur - d >= 0 and ur + d < 2 RING
+                const int d = taps.dx[t + 2];
+                constexpr int RY[8] = {0, 0, 0, 1, 1, 2, 2, 2}, CX[8] = {0, 1, 2, 0, 2, 0, 1, 2};
+                const int r3[3] = {(ur - d >= RING ? ur - d - RING : ur - d) * TW, (ur >= RING ? ur - RING : ur) * TW,
+                                   (ur + d >= RING ? ur + d - RING : ur + d) * TW};
+                const int c3[3] = {HL - d, HL, HL + d};
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    // (readfirstlane keeps the wave-uniform part one scalar: reassociated, the lane + column sums become
+                    //  loop invariants held in registers and spill)
+                    const int o = __builtin_amdgcn_readfirstlane(r3[RY[u]] + c3[CX[u]]) + lx;
+#pragma unroll
+                    for (int k = 0; k < CG; ++k) m[u][k] = ring[k * RING * TW + o];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const unsigned q = a[(t + u) >> 1];
+                    const float w = (u & 1) ? (float)(q >> 16) : (float)(q & 0xffffu);
+#pragma unroll
+                    for (int k = 0; k < CG; ++k) acc[k] = fmaf(w, m[u][k], acc[k]);
+                }
+                if (more) load_aff(a, s + 1, t >> 1, 4);
+                // one dilation's 8 * CG LDS reads in flight at a time.  The sums are pinned here: used only by the
+                // conditional store below, the whole FMA chain is otherwise sunk into that branch, behind all 144 LDS
+                // reads of the pixel, whose values then spill
+#pragma unroll
+                for (int k = 0; k < CG; ++k) asm volatile("" : "+v"(acc[k]));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const float qscale = __uint_as_float(a[T / 2]);
+            if (more) load_aff(a, s + 1, T / 2, 1);
+            if (y < H && xg < W) {
+#pragma unroll
+                for (int k = 0; k < CG; ++k)
+                    if (cb + k < C) *reinterpret_cast<float*>(reinterpret_cast<char*>(O + (long)(cb + k) * HW + (long)y * W) + lo) = acc[k] * qscale;
+            }
+        };
+        // (every step but the last prefetches its successor; the last one stands after the loop, so that no register array is
+        //  defined under a condition)
+        for (int s = 0; s + 1 < nsteps; ++s) {
+            float nv[2][CG];                         // the thread's share of the R rows below the window
+            const long ro = (long)clampi(y0 + (s + 1) * R + HL + ly, H - 1) * W;
+#pragma unroll
+            for (int k = 0; k < CG; ++k) {
+                nv[0][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Mc[k] + ro) + c0);
+                nv[1][k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(Mc[k] + ro) + c1);
+            }
+            sweep(cur, s, true);
+            int r = rb + R + 2 * HL + ly;            // < 2 RING
+            r = r >= RING ? r - RING : r;
+#pragma unroll
+            for (int k = 0; k < CG; ++k) {
+                ring[(k * RING + r) * TW + lx] = nv[0][k];
+                if (two) ring[(k * RING + r) * TW + lx + 64] = nv[1][k];
+            }
+            __syncthreads();
+            rb = rb + R >= RING ? rb + R - RING : rb + R;
+        }
+        sweep(cur, nsteps - 1, false);
+    }
+}
+
 // labels[b,y,x] = valid_key[b, argmax_c masks[b,c,y,x]] over the first nch[b] channels
 // (first maximum wins like torch.argmax).  model_attn_aff_voc.py:49-57.
 __global__ __launch_bounds__(256) void par_labels_kernel(const float* __restrict__ masks,
@@ -392,16 +540,106 @@ extern "C" int wc_par_affinity(const float* img, float* aff, int B, int H, int W
     return WC_OK;
 }
 
-static const char* par_iter_name(int C, bool tiled, bool h16) {
-    static const char* hn[3] = {"par_iter_kernel<2, true, true, 8, 12>", "par_iter_kernel<3, true, true, 8, 12>", "par_iter_kernel<4, true, true, 8, 12>"};
+// Form of the H16 sweep: 0 = par_iter_kernel<CG, true, true, 8, 12> (64 x 8 tile, halo 12, far taps gathered; kept as the
+// comparator), 1 = par_strip_kernel<CG>.  Process-wide; -1 / unset: WECLIP_PAR_SWEEP from the environment, else
+// PAR_SWEEP_DEFAULT.  (The variants measured and not kept are in DESIGN.md section 23.)
+#define PAR_SWEEP_DEFAULT 1
+#define PAR_SWEEP_FORMS 2
+static int g_par_form = -1, g_par_seg_rows = 0;
+extern "C" int wc_par_sweep_form(int form, int seg_rows) {
+    WC_CHECK_ARG(form >= -1 && form < PAR_SWEEP_FORMS && seg_rows >= 0, "wc_par_sweep_form: form -1..1, seg_rows >= 0");
+    g_par_form = form;
+    g_par_seg_rows = seg_rows;
+    return WC_OK;
+}
+// the form a sweep with these taps runs in: the strip walk serves taps within its 24-pixel halo only.  Unless a form was set
+// by wc_par_sweep_form, a launch that cannot give every CU a segment of PAR_STRIP_SEG_ROWS rows keeps the tile form: a strip
+// workgroup walks its rows step after step behind a first window of R + 48 rows, and with shorter segments or idle CUs
+// that costs more than the re-reads it saves.  Measured, 20 sweeps, tile / strip: 4 x 256 x 256 (128 segments of 32 rows)
+// 0.227 / 0.273 ms; 2 x 512 x 512 (256 x 32) 0.329 / 0.329; 4 x 512 x 512 (256 x 64) 0.578 / 0.572; 6 x 512 x 512
+// (240 x 104) 0.819 / 0.790; 16 x 512 x 512 in two launches of 8 (256 x 128 each) 2.184 / 2.057
+#define PAR_STRIP_SEG_ROWS 64
+#define PAR_MAX_DEVICES 64
+static int par_device() {
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < PAR_MAX_DEVICES ? dev : -1;
+}
+static int par_cus() {                       // CUs of the current device
+    static int cus[PAR_MAX_DEVICES];
+    const int dev = par_device();
+    if (dev < 0) return 256;
+    if (!cus[dev]) {
+        hipDeviceProp_t pp;
+        cus[dev] = (hipGetDeviceProperties(&pp, dev) == hipSuccess && pp.multiProcessorCount > 0) ? pp.multiProcessorCount : 256;
+    }
+    return cus[dev];
+}
+static int par_sweep_form(const ParTaps& tp, int B, int H, int W) {
+    for (int t = 0; t < tp.n; ++t)
+        if (abs(tp.dy[t]) > PAR_STRIP_HALO || abs(tp.dx[t]) > PAR_STRIP_HALO) return 0;
+    if (g_par_form >= 0) return g_par_form;
+    static int env_form = -1;
+    if (env_form < 0) {
+        const char* e = getenv("WECLIP_PAR_SWEEP");
+        const int f = e && *e ? atoi(e) : PAR_SWEEP_DEFAULT;
+        env_form = f >= 0 && f < PAR_SWEEP_FORMS ? f : PAR_SWEEP_DEFAULT;
+    }
+    return (long)wc_cdiv(W, 64) * B * wc_cdiv(H, PAR_STRIP_SEG_ROWS) >= par_cus() ? env_form : 0;
+}
+
+// kernel names as rocprofv3 prints them (bench.py joins the traffic files by them)
+static const char* par_iter_name(int C, bool tiled, bool h16, int form = 0) {
+    static const char* hn[PAR_SWEEP_FORMS][3] = {
+        {"par_iter_kernel<2, true, true, 8, 12>", "par_iter_kernel<3, true, true, 8, 12>", "par_iter_kernel<4, true, true, 8, 12>"},
+        {"par_strip_kernel<2>", "par_strip_kernel<3>", "par_strip_kernel<4>"}};
     static const char* names[2][3] = {{"par_iter_kernel<2, false>", "par_iter_kernel<3, false>", "par_iter_kernel<4, false>"},
                                       {"par_iter_kernel<2, true>", "par_iter_kernel<3, true>", "par_iter_kernel<4, true>"}};
     const int ci = C <= 2 ? 0 : (C == 3 ? 1 : 2);
-    return h16 ? hn[ci] : names[tiled ? 1 : 0][ci];
+    return h16 ? hn[form][ci] : names[tiled ? 1 : 0][ci];
 }
 // algorithmic bytes of one sweep: the affinities (T 16-bit values + a scale, or T floats) + C mask planes read, C written
 static double par_iter_bytes(int B, int C, int H, int W, const ParTaps& tp, bool h16) {
     return h16 ? B * (double)H * W * (2.0 * tp.n + 4.0 + 8.0 * C) : 4.0 * B * (double)H * W * (tp.n + 2 * C);
+}
+
+// The strip walk: grid (strips, segments, images).  Segment length S (a multiple of R): as many segments as give every CU
+// one workgroup (512 x 512 x 8 images on 256 CUs: 4 segments of 128 rows), not shorter than 32 rows -- a segment re-reads the
+// 48 halo rows of its neighbours.  The ring is more than 64 KiB of LDS: reserved once per kernel and device by
+// par_strip_reserve, at the first (eager) call.
+template <int CG>
+static bool par_strip_reserve_one() {
+    constexpr int LDS = CG * (2 * PAR_STRIP_ROWS + 2 * PAR_STRIP_HALO) * (64 + 2 * PAR_STRIP_HALO) * 4;
+    static bool reserved[PAR_MAX_DEVICES];
+    const int dev = par_device();
+    if (dev >= 0 && reserved[dev]) return true;
+    if (hipFuncSetAttribute((const void*)par_strip_kernel<CG>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return false;
+    if (dev >= 0) reserved[dev] = true;
+    return true;
+}
+static bool par_strip_reserve(int C) {
+    return C <= 2 ? par_strip_reserve_one<2>() : (C == 3 ? par_strip_reserve_one<3>() : par_strip_reserve_one<4>());
+}
+template <int CG>
+static void launch_strip_one(const float* aff, const float* src, float* dst, int B, int C, int H, int W, const ParTaps& tp,
+                             hipStream_t st) {
+    constexpr int R = PAR_STRIP_ROWS, LDS = CG * (2 * R + 2 * PAR_STRIP_HALO) * (64 + 2 * PAR_STRIP_HALO) * 4;
+    const int strips = wc_cdiv(W, 64) * B;
+    int S = g_par_seg_rows;
+    if (S <= 0) {
+        int nseg = par_cus() / strips < 1 ? 1 : par_cus() / strips;
+        const int most = wc_cdiv(H, 32);
+        nseg = nseg > most ? most : nseg;
+        S = wc_cdiv(H, nseg);
+    }
+    S = wc_cdiv(S, R) * R;
+    dim3 grid(wc_cdiv(W, 64), wc_cdiv(H, S), B);
+    hipLaunchKernelGGL((par_strip_kernel<CG>), grid, dim3(64 * R), LDS, st, aff, src, dst, C, H, W, S, tp);
+}
+static void launch_strip(const float* aff, const float* src, float* dst, int B, int C, int H, int W, const ParTaps& tp,
+                         hipStream_t st) {
+    if (C <= 2) launch_strip_one<2>(aff, src, dst, B, C, H, W, tp, st);
+    else if (C == 3) launch_strip_one<3>(aff, src, dst, B, C, H, W, tp, st);
+    else launch_strip_one<4>(aff, src, dst, B, C, H, W, tp, st);
 }
 
 // prof: bracket this launch with its own event pair (a stand-alone sweep); the sweeps of a whole PAR.forward share one pair
@@ -409,14 +647,20 @@ static int launch_iter(const float* aff, const float* src, float* dst, int B, in
                        const ParTaps& tp, hipStream_t st, bool tiled, bool h16 = false, bool prof = true) {
     dim3 grid(wc_cdiv(W, 64), wc_cdiv(H, 4), B);
     if (h16) {       // fp16-pair affinities (tiled layout, 48 taps)
+        const int form = par_sweep_form(tp, B, H, W);
+        WC_CHECK_ARG(!form || par_strip_reserve(C), "wc_par_forward_h: cannot reserve the LDS of the strip sweep");
         const int pr = prof ? wc_prof_begin(st) : -1;
-        // blocks of 64 x 8 pixels with a 12-pixel halo: the tile serves dilations 1..12 (40 of the 48 taps); measured
-        // 2.44 ms (4 rows, halo 4) -> 2.29 ms per 16-image PAR.forward
-        dim3 grid8(wc_cdiv(W, 64), wc_cdiv(H, 8), B);
-        if (C <= 2) hipLaunchKernelGGL((par_iter_kernel<2, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
-        else if (C == 3) hipLaunchKernelGGL((par_iter_kernel<3, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
-        else hipLaunchKernelGGL((par_iter_kernel<4, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
-        wc_prof_end(pr, par_iter_name(C, tiled, true), par_iter_bytes(B, C, H, W, tp, true), st);
+        if (form) {
+            launch_strip(aff, src, dst, B, C, H, W, tp, st);
+        } else {
+            // blocks of 64 x 8 pixels with a 12-pixel halo: the tile serves dilations 1..12 (40 of the 48 taps); measured
+            // 2.44 ms (4 rows, halo 4) -> 2.29 ms per 16-image PAR.forward
+            dim3 grid8(wc_cdiv(W, 64), wc_cdiv(H, 8), B);
+            if (C <= 2) hipLaunchKernelGGL((par_iter_kernel<2, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
+            else if (C == 3) hipLaunchKernelGGL((par_iter_kernel<3, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
+            else hipLaunchKernelGGL((par_iter_kernel<4, true, true, 8, 12>), grid8, dim3(512), 0, st, aff, src, dst, C, H, W, tp);
+        }
+        wc_prof_end(pr, par_iter_name(C, tiled, true, form), par_iter_bytes(B, C, H, W, tp, true), st);
         WC_LAUNCH_CHECK("par_iter_kernel");
         return WC_OK;
     }
@@ -487,7 +731,7 @@ static int par_forward_impl(const float* img, const float* masks, float* out, fl
             if (rc) return rc;
             src = dst;
         }
-        wc_prof_end_n(pr, par_iter_name(C, tiled, h16 && tiled), num_iter * par_iter_bytes(nb, C, H, W, tp, h16 && tiled), st, num_iter);
+        wc_prof_end_n(pr, par_iter_name(C, tiled, h16 && tiled, h16 && tiled ? par_sweep_form(tp, nb, H, W) : 0), num_iter * par_iter_bytes(nb, C, H, W, tp, h16 && tiled), st, num_iter);
     }
     return WC_OK;
 }
